@@ -2,6 +2,7 @@
 """Headline benchmark: env-steps/s of AAURoverEnv-v0 at num_envs=4096 per GPU (BASELINE.json metric, config 2).
 
     python bench.py --gpus 1 --steps 1000 --warmup 100
+    python bench.py --gpus 1 --steps 1000 --warmup 100 --dump-outputs DIR    # + what the last timed step returned, DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -54,6 +55,32 @@ def _load_json(name):
         return None
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs budget; larger batches are written as a fixed, seeded sample of env rows
+
+
+def dump_outputs(out_dir, result):
+    """--dump-outputs: what the timed path's last ``step()`` returned -- obs["policy"], reward, terminated, truncated (as 0 / 1)
+    and the values of extras["log"] -- as float32 ``.npy`` files under ``out_dir``.  If the per-env arrays exceed DUMP_BYTES,
+    the same seeded sample of env rows is taken from each of them and its row ids are written to ``sampled_env_ids.npy``."""
+    import numpy as np
+    import torch
+    obs, rew, term, trunc, extras = result
+    arrays = {name: t.detach().to("cpu", torch.float32).numpy()
+              for name, t in (("obs_policy", obs["policy"]), ("reward", rew), ("terminated", term), ("truncated", trunc))}
+    log = extras["log"]
+    arrays["log"] = np.array([float(log[k]) for k in log.keys()], dtype=np.float32)
+    n = arrays["reward"].shape[0]
+    row_bytes = sum(a.nbytes for k, a in arrays.items() if k != "log") // n
+    budget = DUMP_BYTES - arrays["log"].nbytes - 4096          # 4 KB: the .npy headers
+    if n * row_bytes > budget:
+        keep = np.sort(np.random.RandomState(0).choice(n, budget // (row_bytes + 8), replace=False))
+        arrays = {k: (a if k == "log" else a[keep]) for k, a in arrays.items()}
+        arrays["sampled_env_ids"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def library_digest():
     """Identity of the build this process runs: sha256[:16] over the HIP sources + headers (isaac_rover_orbit_amd.build.source_digest:
     stable across rebuilds) and the file name of the loaded library (a tools/build_diag.py variant carries another name) -- what
@@ -67,7 +94,7 @@ def library_digest():
 
 
 # ------------------------------------------------------------------------------------------------ config 5 (lift)
-def lift_line(num_envs, steps, warmup, profile_steps, cpu_seconds):
+def lift_line(num_envs, steps, warmup, profile_steps, cpu_seconds, dump_dir=None):
     """BASELINE config 5: FrankaCubeLift-v0, num_envs = 2048, 1 x MI355X; env-steps/s through FrankaCubeLiftEnv.step()."""
     import numpy as np
     import torch
@@ -86,9 +113,11 @@ def lift_line(num_envs, steps, warmup, profile_steps, cpu_seconds):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(warmup, total):
-        env.step(acts[k % acts.shape[0]])
+        last = env.step(acts[k % acts.shape[0]])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump_dir:
+        dump_outputs(dump_dir, last)
     out = {"metric": "env-steps/sec FrankaCubeLift-v0 (BASELINE config 5)", "value": n * steps / dt, "unit": "env-steps/s",
            "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": dt / steps * 1e3,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -358,10 +387,16 @@ def main():
                     help="BASELINE.json config: 2 = headline (31x31 rays @0.1 m, sigma_z 0.15 m); "
                          "4 = dense scanner stress (32x32 rays @0.05 m, sigma_z 0.4 m); "
                          "5 = manipulation task FrankaCubeLift-v0 (default num_envs 2048)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB; "
+                         "rank 0's shard when --gpus > 1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == 5:
         n5 = args.num_envs if args.num_envs != 4096 else 2048
-        print(json.dumps(lift_line(n5, args.steps, args.warmup, args.profile_steps, 0.0 if args.no_cpu_baseline else args.cpu_seconds)))
+        print(json.dumps(lift_line(n5, args.steps, args.warmup, args.profile_steps, 0.0 if args.no_cpu_baseline else args.cpu_seconds,
+                                   dump_dir=args.dump_outputs)))
         return
 
     import numpy as np
@@ -404,7 +439,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.warmup, total):
-        env.step(actions[k % n_act])
+        last = env.step(actions[k % n_act])
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
@@ -414,6 +449,8 @@ def main():
         elapsed = float(t.item())
     value = shard.global_num_envs * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)       # before the legs below step the env again (two rotating output sets)
 
     # ---- roofline leg.  HIP-event duration of each kernel (on the stream the kernels are launched on), raw and minus the cost of
     #      an empty event pair.  One launch per step: the roofline figure uses ms_per_step, which bounds the kernel's duration from

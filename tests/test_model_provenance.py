@@ -8,9 +8,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 USD = "/root/reference/rover_envs/assets/robots/aau_rover_simple/rover_instance.usd"
-pytestmark = pytest.mark.skipif(not os.path.exists(USD), reason="reference asset not present")
 
 
+@pytest.mark.skipif(not os.path.exists(USD), reason="reference asset not present")
 @pytest.mark.timeout(120)
 def test_transcribed_tables_match_the_usd_asset():
     import usd_crate_dump as u
