@@ -32,6 +32,8 @@ EXPORTS = [
     "rover_lift_workspace_bytes", "rover_lift_bind", "rover_lift_reset", "rover_lift_step", "rover_lift_terms",   # rover_lift.h
     "rover_lift_model_constants", "rover_lift_set_seed", "rover_lift_profile_step", "rover_lift_kernel_name",
     "rover_lift_set_log_deferred", "rover_lift_flush_log",
+    "rover_camera_default_config", "rover_camera_config_bytes", "rover_camera_workspace_bytes", "rover_camera_prepare",  # rover_camera.h
+    "rover_camera_render",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH = 0, 1, 2
@@ -94,6 +96,13 @@ class RoverConfig(C.Structure):
         ("scan_surface", C.c_int32), ("mass_model", C.c_int32),
         ("rew_success_threshold", C.c_float), ("rew_far_threshold", C.c_float),
     ]
+
+
+class CameraConfig(C.Structure):
+    """Mirror of ``struct rover_camera_config`` (include/rover_camera.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("focal_length", C.c_float), ("horizontal_aperture", C.c_float),
+                ("vertical_aperture", C.c_float), ("mount_pos", C.c_float * 3), ("mount_quat", C.c_float * 4),
+                ("near_clip", C.c_float), ("far_clip", C.c_float)]
 
 
 _lib = None
@@ -186,6 +195,12 @@ def load():
     lib.rover_lift_kernel_name.argtypes = [vp, C.c_char_p, C.c_size_t]
     lib.rover_lift_debug_set_lanes.argtypes = [vp, i32]
     lib.rover_lift_terms.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rover_camera_default_config.argtypes = [C.POINTER(CameraConfig)]
+    lib.rover_camera_config_bytes.restype = C.c_size_t
+    lib.rover_camera_workspace_bytes.argtypes = [vp, C.POINTER(CameraConfig)]
+    lib.rover_camera_workspace_bytes.restype = C.c_size_t
+    lib.rover_camera_prepare.argtypes = [vp, C.POINTER(CameraConfig), vp, C.c_size_t, vp]
+    lib.rover_camera_render.argtypes = [vp, C.POINTER(CameraConfig), vp, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -197,6 +212,8 @@ def load():
         raise RoverHipError("struct rover_config of librover_hip.so does not match the Python mirror")
     if lib.rover_lift_config_bytes() != C.sizeof(LiftConfig) or lib.rover_lift_state_words() != LIFT_STATE_WORDS:
         raise RoverHipError("struct lift_config / lift state layout of librover_hip.so does not match the Python mirror")
+    if lib.rover_camera_config_bytes() != C.sizeof(CameraConfig):
+        raise RoverHipError("struct rover_camera_config of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib
@@ -207,6 +224,12 @@ def check(rc: int, what: str):
     if rc != 0:
         msg = load().rover_last_error().decode("utf-8", "replace")
         raise RoverHipError(f"{what} failed (code {rc}): {msg}")
+
+
+def default_camera_config() -> CameraConfig:
+    cfg = CameraConfig()
+    check(load().rover_camera_default_config(C.byref(cfg)), "rover_camera_default_config")
+    return cfg
 
 
 def default_config() -> RoverConfig:

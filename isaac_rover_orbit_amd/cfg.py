@@ -110,6 +110,58 @@ class TerrainCfg:
     spawn_seed: int = 41
 
 
+@dataclass
+class CameraCfg:
+    """The rover's on-board depth camera (``RoverEnvCamera``, rover_camera_env.py:44-62): a pinhole on the Body link whose
+    ``distance_to_camera`` image is a ray cast against the terrain's triangle mesh (include/rover_camera.h; RGB is not rendered)."""
+    width: int = 160                                   # render product (:62)
+    height: int = 90
+    focal_length: float = 2.12                         # mm (:47)
+    horizontal_aperture: float = 6.055                 # mm (:49): f = 160 * 2.12 / 6.055 = 56.02 px, horizontal FOV 110.0 deg
+    # None = square pixels (Isaac Sim derives the vertical extent from the aspect ratio: vertical FOV 77.5 deg); the stated
+    # verticalAperture of :50 is 2.968879962 (vertical FOV 70.0 deg)
+    vertical_aperture: float | None = None
+    position: tuple = (-0.151, 0.0, 0.73428)           # m, Body frame (:55)
+    orientation: tuple = (0.64086, 0.29884, -0.29884, -0.64086)   # (w, x, y, z), USD camera convention (:56); normalised
+    near_clip: float = 0.01                            # m (:51 clippingRange)
+    far_clip: float = 1000000.0
+    every_n_steps: int = 1                             # re-render on steps with common_step_counter % every_n_steps == 0
+
+    @property
+    def focal_px(self) -> tuple:
+        """(f_x, f_y) in pixels."""
+        fx = self.width * self.focal_length / self.horizontal_aperture
+        fy = fx if self.vertical_aperture is None else self.height * self.focal_length / self.vertical_aperture
+        return fx, fy
+
+    def validate(self):
+        if int(self.width) <= 0 or int(self.height) <= 0:
+            raise ValueError("camera width and height must be positive")
+        if not (self.focal_length > 0 and self.horizontal_aperture > 0):
+            raise ValueError("camera focal_length and horizontal_aperture must be positive")
+        if self.vertical_aperture is not None and not self.vertical_aperture > 0:
+            raise ValueError("camera vertical_aperture must be positive or None (square pixels)")
+        if not (0 <= self.near_clip < self.far_clip):
+            raise ValueError("camera clipping range must satisfy 0 <= near_clip < far_clip")
+        if len(self.position) != 3 or len(self.orientation) != 4 or not any(float(q) != 0.0 for q in self.orientation):
+            raise ValueError("camera position must be (x, y, z) and orientation a non-zero (w, x, y, z) quaternion")
+        if int(self.every_n_steps) < 1:
+            raise ValueError("camera every_n_steps must be >= 1")
+
+    def to_native(self) -> "_lib.CameraConfig":
+        self.validate()
+        c = _lib.CameraConfig()
+        c.width, c.height = int(self.width), int(self.height)
+        c.focal_length, c.horizontal_aperture = self.focal_length, self.horizontal_aperture
+        c.vertical_aperture = 0.0 if self.vertical_aperture is None else self.vertical_aperture
+        for i in range(3):
+            c.mount_pos[i] = self.position[i]
+        for i in range(4):
+            c.mount_quat[i] = self.orientation[i]
+        c.near_clip, c.far_clip = self.near_clip, self.far_clip
+        return c
+
+
 def _default_observations():
     return {
         "actions": TermCfg("last_action"),
@@ -190,6 +242,8 @@ class RoverEnvCfg:
     # multi-GPU sharding: this process simulates global env ids [env_id_offset, env_id_offset + num_envs)
     env_id_offset: int = 0
     global_num_envs: int | None = None
+    # the on-board depth camera (RoverEnvCamera): None = no camera, nothing rendered
+    camera: CameraCfg | None = None
 
     # ------------------------------------------------------------------------------------------------------------
     def custom_terms(self, table: dict, order: list) -> dict:
@@ -228,6 +282,8 @@ class RoverEnvCfg:
             raise ValueError("mass_model must be 'subtree_weights' or 'lumped'")
         if self.commands.simple_heading:
             raise ValueError("simple_heading=True is not supported (the reference cfg uses False, rover_env_cfg.py:195)")
+        if self.camera is not None:
+            self.camera.validate()
 
     def observation_post(self) -> dict:
         """Observation terms whose ORBIT post-processing (ObservationManager.compute_group: noise, then clip, then scale) is not
@@ -295,3 +351,9 @@ class RoverEnvCfg:
 @dataclass
 class AAURoverEnvCfg(RoverEnvCfg):
     """``AAURoverEnv-v0`` (robots/aau_rover/env_cfg.py:10-31): the defaults above already are the AAU values."""
+
+
+@dataclass
+class AAURoverCameraEnvCfg(AAURoverEnvCfg):
+    """``RoverCamera-v0`` (rover_envs/envs/__init__.py:38-42, rover_camera_env.py:18-76): the AAU rover with its depth camera."""
+    camera: CameraCfg | None = field(default_factory=CameraCfg)

@@ -144,11 +144,15 @@ def install(force: bool = False) -> dict:
 
 
 def register_default_tasks():
-    """Register ``AAURoverEnv-v0`` with this package's own cfg (for users who do not have the reference checked out)."""
-    from ..cfg import AAURoverEnvCfg
+    """Register ``AAURoverEnv-v0`` and ``RoverCamera-v0`` with this package's own cfg (for users who do not have the reference
+    checked out)."""
+    from ..cfg import AAURoverCameraEnvCfg, AAURoverEnvCfg
     gym = gym_api()
     gym.register(id="AAURoverEnv-v0", entry_point="isaac_rover_orbit_amd.envs:RoverEnv", disable_env_checker=True,
                  kwargs={"env_cfg_entry_point": AAURoverEnvCfg})
+    # rover_envs/envs/__init__.py:38-42 reserves the id (registration commented out there); entry point rover_camera_env.py:18
+    gym.register(id="RoverCamera-v0", entry_point="isaac_rover_orbit_amd.envs:RoverEnvCamera", disable_env_checker=True,
+                 kwargs={"env_cfg_entry_point": AAURoverCameraEnvCfg})
     from ..envs.lift_env import LiftEnvCfg
     # manipulation/config/franka/__init__.py:6-14 (entry point there: ORBIT's generic RLTaskEnv on FrankaCubeLiftEnvCfg)
     gym.register(id="FrankaCubeLift-v0", entry_point="isaac_rover_orbit_amd.envs:FrankaCubeLiftEnv", disable_env_checker=True,

@@ -3,3 +3,23 @@
 
 // records the text rover_last_error() returns on this thread and hands `code` back
 __attribute__((visibility("hidden"))) int rover_internal_fail(int code, const char *fmt, const char *detail = "");
+
+#include <cstddef>
+#include <cstdint>
+
+struct rover_sim;
+// What another translation unit (camera_kernels.hip) may read of a handle: its bound state and terrain, the call-order flags
+// and the terrain generation (bumped by every rover_set_terrain*), plus the one word of camera bookkeeping the handle keeps
+// for it: which workspace was prepared for which terrain generation.
+struct rover_sim_view {
+    const float *state;      // SoA state words, state[word * n + env]; NULL before rover_bind
+    int n;
+    bool have_terrain, phase_open;
+    const float *height;     // (H, W) fp32 heightfield, row = y
+    int H, W;
+    float res, min_x, min_y;
+    uint64_t terrain_gen;
+    const void **camera_ws;  // the handle's record of the last rover_camera_prepare
+    uint64_t *camera_gen;
+};
+__attribute__((visibility("hidden"))) rover_sim_view rover_internal_view(rover_sim *sim);

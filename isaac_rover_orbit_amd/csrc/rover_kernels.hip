@@ -3772,7 +3772,16 @@ struct rover_sim {
     bool phase_open;     // rover_step_begin has run, rover_step_finish has not
     int launch_error;    // set by launch_step_kernels when a launch could not be made (rover_step returns it)
     float2 *ray_xy;      // [1024] pattern offsets of ray i (rays past the pattern repeat ray 0): the wave-private scan's table (workspace)
+    uint64_t terrain_gen;    // rover_set_terrain* calls so far: a camera workspace is valid for the generation it was prepared for
+    const void *camera_ws;   // rover_camera_prepare's last workspace and the generation it was built for (rover_internal_view)
+    uint64_t camera_gen;
 };
+rover_sim_view rover_internal_view(rover_sim *sim)
+{
+    const RvParams &p = sim->p;
+    return rover_sim_view{sim->state, p.n, sim->have_terrain, sim->phase_open, p.height, p.H, p.W, p.res, p.min_x, p.min_y,
+                          sim->terrain_gen, &sim->camera_ws, &sim->camera_gen};
+}
 
 
 
@@ -4132,6 +4141,7 @@ int rover_set_terrain(rover_sim *sim, const float *height, const float *obstacle
     configure_tile(sim, 4);
     if (sim->lds_bytes > 64 * 1024) return fail(ROVER_ERR_UNSUPPORTED, "ray pattern too large for the LDS tile (64 KiB)");
     sim->have_terrain = true;
+    ++sim->terrain_gen;
     return ROVER_OK;
 }
 
@@ -4140,6 +4150,7 @@ int rover_set_terrain_lookup(rover_sim *sim, const float *lookup_height)
     if (!sim) return fail(ROVER_ERR_INVALID, "sim is NULL");
     if (!sim->have_terrain) return fail(ROVER_ERR_STATE, "rover_set_terrain has not been called");
     sim->p.lookup = lookup_height ? lookup_height : sim->p.height;
+    ++sim->terrain_gen;
     return ROVER_OK;
 }
 
@@ -4151,6 +4162,7 @@ int rover_set_terrain_q16(rover_sim *sim, const int16_t *height_q, float q_scale
         sim->p.height_q = nullptr;
         sim->p.q_scale = 0.0f;
         configure_tile(sim, 4);
+        ++sim->terrain_gen;
         return ROVER_OK;
     }
     int q_exp = 0;
@@ -4159,6 +4171,7 @@ int rover_set_terrain_q16(rover_sim *sim, const int16_t *height_q, float q_scale
     sim->p.height_q = height_q;
     sim->p.q_scale = q_scale;
     configure_tile(sim, 8);
+    ++sim->terrain_gen;
     return ROVER_OK;
 }
 

@@ -401,8 +401,55 @@ class RoverEnv(RLTaskEnv):
         self.action_space = _spaces.Box(-np.inf, np.inf, (n, 2), np.float32)
         self._step_args = None
         self._closed = False
+        self._init_camera()
         if getattr(self.cfg, "roctx_markers", False):
             self.set_markers(True)
+
+    def _init_camera(self):
+        """``cfg.camera``: the workspace (max-height pyramid of the terrain, built here) and two depth buffers that rotate like
+        the observation buffers, so the image handed out by one render stays valid through the next."""
+        cam = self.cfg.camera
+        self._camera_cfg = None
+        self.extras.pop("depth", None)
+        self.extras.pop("rgb", None)
+        if cam is None:
+            return
+        self._camera_cfg = cam.to_native()
+        self._camera_every = int(cam.every_n_steps)
+        with torch.cuda.device(self.device):
+            nb = int(self._lib.rover_camera_workspace_bytes(self._h, C.byref(self._camera_cfg)))
+            if nb == 0:
+                raise _lib.RoverHipError("rover_camera_workspace_bytes: no terrain bound or invalid camera config")
+            self._camera_ws = torch.zeros((nb + 3) // 4, dtype=torch.float32, device=self.device)
+            self._depth = [torch.full((self.num_envs, cam.height, cam.width), float("inf"), dtype=torch.float32, device=self.device)
+                           for _ in range(self._nbuf)]
+            _lib.check(self._lib.rover_camera_prepare(self._h, C.byref(self._camera_cfg), _ptr(self._camera_ws), nb, self._stream()),
+                       "rover_camera_prepare")
+        self._depth_cur = 0
+        self.extras["depth"] = self._depth[0].permute(0, 2, 1)
+        self.extras["rgb"] = None          # what the reference's listener reports without RGB data (rover_camera_env.py:94-98)
+
+    def _render_into(self, buf: torch.Tensor):
+        _lib.check(self._lib.rover_camera_render(self._h, C.byref(self._camera_cfg), _ptr(self._camera_ws), _ptr(buf), self._stream()),
+                   "rover_camera_render")
+
+    def _camera_update(self, force: bool = False):
+        """Render the pose the step (or reset) left behind into the next depth buffer: extras["depth"] is its (N, W, H) view."""
+        if self._camera_cfg is None or not (force or self.common_step_counter % self._camera_every == 0):
+            return
+        self._depth_cur = (self._depth_cur + 1) % self._nbuf
+        buf = self._depth[self._depth_cur]
+        self._render_into(buf)
+        self.extras["depth"] = buf.permute(0, 2, 1)
+
+    def render_depth(self) -> torch.Tensor:
+        """A fresh depth image of the current state, (num_envs, width, height) fp32: the permuted view of a new row-major
+        (num_envs, height, width) buffer, the layout of ``extras["depth"]``."""
+        if self._camera_cfg is None:
+            raise RuntimeError("render_depth needs a camera (cfg.camera)")
+        buf = torch.empty(self.num_envs, self.cfg.camera.height, self.cfg.camera.width, dtype=torch.float32, device=self.device)
+        self._render_into(buf)
+        return buf.permute(0, 2, 1)
 
     # ------------------------------------------------------------------------------------------------------------
     @property
@@ -464,6 +511,7 @@ class RoverEnv(RLTaskEnv):
         if self._obs_post:
             self._post_observations(obs)
         self.obs_buf = {"policy": obs}
+        self._camera_update(force=True)
         return self.obs_buf, self.extras
 
     def reset_with_draws(self, mask, spawn_row, yaw_u, theta_u, heading_u):
@@ -519,6 +567,7 @@ class RoverEnv(RLTaskEnv):
         self.reward_buf = self._rew[k]
         self.reset_terminated = self._term_b[k]
         self.reset_time_outs = self._trunc_b[k]
+        self._camera_update()
         return self.obs_buf, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
 
     def _fresh_scan(self) -> torch.Tensor:
@@ -581,6 +630,7 @@ class RoverEnv(RLTaskEnv):
         self.obs_buf = self._obs_dicts[k]
         if self._obs_post:
             self._post_observations(self.obs_buf["policy"])
+        self._camera_update()
         return self.obs_buf, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
 
     def _post_observations(self, obs: torch.Tensor):
@@ -659,6 +709,7 @@ class RoverEnv(RLTaskEnv):
         self.reward_buf = self._rew[k]
         self.reset_terminated = self._term_b[k]
         self.reset_time_outs = self._trunc_b[k]
+        self._camera_update()
         return a.value, b.value
 
     def profile_event_overhead(self, reps: int = 100) -> float:
@@ -795,3 +846,22 @@ class RoverEnv(RLTaskEnv):
             self.close()
         except Exception:
             pass
+
+
+class RoverEnvCamera(RoverEnv):
+    """``RoverCamera-v0`` (rover_camera_env.py:18-76): ``RoverEnv`` with the reference's on-board camera on by default.  After
+    ``reset()`` and every step ``extras["depth"]`` is the (num_envs, 160, 90) ``distance_to_camera`` image of the pose the
+    observation row was taken at; ``extras["rgb"]`` is None (RGB is not rendered)."""
+
+    def __init__(self, cfg: RoverEnvCfg | None = None, terrain: Terrain | None = None, render_mode=None, **kwargs):
+        if cfg is None:
+            from ..cfg import AAURoverCameraEnvCfg
+            cfg = AAURoverCameraEnvCfg()
+        elif isinstance(cfg, RoverEnvCfg) and cfg.camera is None:
+            from ..cfg import CameraCfg
+            cfg.camera = CameraCfg()
+        super().__init__(cfg, terrain=terrain, render_mode=render_mode, **kwargs)
+        if self.cfg.camera is None:         # a translated reference cfg
+            from ..cfg import CameraCfg
+            self.cfg.camera = CameraCfg()
+            self._init_camera()
