@@ -33,7 +33,8 @@ typedef struct rover_camera_config {
     float mount_pos[3];             /* m, in the Body frame (:55: -0.151, 0, 0.73428)                                   */
     float mount_quat[4];            /* (w, x, y, z) Body <- camera, USD camera convention: looks along -Z, up is +Y
                                        (:56: 0.64086, 0.29884, -0.29884, -0.64086; normalised by the library)           */
-    float near_clip, far_clip;      /* m (:51: clippingRange (0.01, 1000000))                                           */
+    float near_clip, far_clip;      /* m (:51: clippingRange (0.01, 1000000)); 0 <= near_clip < far_clip, far_clip may be
+                                       +inf.  Every other float must be finite, or prepare / render return ROVER_ERR_INVALID */
 } rover_camera_config;
 
 /* The reference's camera prim attributes (rover_camera_env.py:44-56) and render-product size (:62). */

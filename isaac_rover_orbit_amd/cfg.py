@@ -20,6 +20,7 @@ row, in ORBIT's order (noise, clip, scale), for the terms that ask for it (``Rov
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from dataclasses import dataclass, field
 from typing import Any
@@ -135,16 +136,21 @@ class CameraCfg:
         return fx, fy
 
     def validate(self):
+        """The checks of the library's config_ok (camera_kernels.hip), on the values as the fp32 struct holds them."""
+        f32 = lambda x: C.c_float(float(x)).value      # noqa: E731
         if int(self.width) <= 0 or int(self.height) <= 0:
             raise ValueError("camera width and height must be positive")
-        if not (self.focal_length > 0 and self.horizontal_aperture > 0):
-            raise ValueError("camera focal_length and horizontal_aperture must be positive")
-        if self.vertical_aperture is not None and not self.vertical_aperture > 0:
-            raise ValueError("camera vertical_aperture must be positive or None (square pixels)")
-        if not (0 <= self.near_clip < self.far_clip):
-            raise ValueError("camera clipping range must satisfy 0 <= near_clip < far_clip")
-        if len(self.position) != 3 or len(self.orientation) != 4 or not any(float(q) != 0.0 for q in self.orientation):
+        if not (math.isfinite(f32(self.focal_length)) and math.isfinite(f32(self.horizontal_aperture)) and
+                f32(self.focal_length) > 0 and f32(self.horizontal_aperture) > 0):
+            raise ValueError("camera focal_length and horizontal_aperture must be positive and finite")
+        if self.vertical_aperture is not None and not (math.isfinite(f32(self.vertical_aperture)) and f32(self.vertical_aperture) > 0):
+            raise ValueError("camera vertical_aperture must be positive and finite, or None (square pixels)")
+        if not (0 <= f32(self.near_clip) < f32(self.far_clip)):
+            raise ValueError("camera clipping range must satisfy 0 <= near_clip < far_clip (far_clip may be inf)")
+        if len(self.position) != 3 or len(self.orientation) != 4 or not any(f32(q) != 0.0 for q in self.orientation):
             raise ValueError("camera position must be (x, y, z) and orientation a non-zero (w, x, y, z) quaternion")
+        if not all(math.isfinite(f32(v)) for v in (*self.position, *self.orientation)):
+            raise ValueError("camera position and orientation must be finite")
         if int(self.every_n_steps) < 1:
             raise ValueError("camera every_n_steps must be >= 1")
 

@@ -247,10 +247,15 @@ __global__ __launch_bounds__(TILE * TILE * WAVES) void rover_camera_render_kerne
     __builtin_nontemporal_store(depth, p.depth + o);
 }
 
+// far_clip may be +inf; every other float is finite (a non-finite lens or mount would give all-miss or degenerate images)
 bool config_ok(const rover_camera_config *c)
 {
-    return c && c->width > 0 && c->height > 0 && c->focal_length > 0.0f && c->horizontal_aperture > 0.0f &&
-           std::isfinite(c->vertical_aperture) && c->near_clip >= 0.0f && c->near_clip < c->far_clip &&
+    if (!c) return false;
+    for (float v : {c->focal_length, c->horizontal_aperture, c->vertical_aperture, c->mount_pos[0], c->mount_pos[1], c->mount_pos[2],
+                    c->mount_quat[0], c->mount_quat[1], c->mount_quat[2], c->mount_quat[3]})
+        if (!std::isfinite(v)) return false;
+    return c->width > 0 && c->height > 0 && c->focal_length > 0.0f && c->horizontal_aperture > 0.0f && c->near_clip >= 0.0f &&
+           c->near_clip < c->far_clip &&
            (c->mount_quat[0] != 0.0f || c->mount_quat[1] != 0.0f || c->mount_quat[2] != 0.0f || c->mount_quat[3] != 0.0f);
 }
 
@@ -287,6 +292,7 @@ int rover_camera_prepare(rover_sim *sim, const rover_camera_config *cfg, void *w
     if (!config_ok(cfg)) return rover_internal_fail(ROVER_ERR_INVALID, "invalid rover_camera_config");
     const rover_sim_view s = rover_internal_view(sim);
     if (!s.have_terrain) return rover_internal_fail(ROVER_ERR_STATE, "rover_set_terrain has not been called");
+    DeviceGuard guard(s.device);
     const Pyramid py = pyramid_of(s.H, s.W);
     if (bytes < py.bytes) return rover_internal_fail(ROVER_ERR_INVALID, "camera workspace too small");
     if (reinterpret_cast<uintptr_t>(ws) & 255) return rover_internal_fail(ROVER_ERR_INVALID, "camera workspace must be 256-byte aligned");
@@ -314,6 +320,7 @@ int rover_camera_render(rover_sim *sim, const rover_camera_config *cfg, const vo
     if (s.phase_open) return rover_internal_fail(ROVER_ERR_STATE, "rover_camera_render between rover_step_begin and rover_step_finish");
     if (*s.camera_ws != ws || *s.camera_gen != s.terrain_gen)
         return rover_internal_fail(ROVER_ERR_STATE, "camera workspace not prepared for the terrain bound now (call rover_camera_prepare)");
+    DeviceGuard guard(s.device);
     const Pyramid py = pyramid_of(s.H, s.W);
     const char *base = static_cast<const char *>(ws);
     CamParams p;

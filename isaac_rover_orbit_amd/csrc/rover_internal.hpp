@@ -7,11 +7,28 @@ __attribute__((visibility("hidden"))) int rover_internal_fail(int code, const ch
 #include <cstddef>
 #include <cstdint>
 
+#include <hip/hip_runtime_api.h>
+
+// Every entry point that launches work runs on the handle's device, whatever the calling thread's current device is.
+struct DeviceGuard {
+    int prev = -1;
+    bool switched = false;
+    explicit DeviceGuard(int dev)
+    {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard()
+    {
+        if (switched) (void)hipSetDevice(prev);
+    }
+};
+
 struct rover_sim;
-// What another translation unit (camera_kernels.hip) may read of a handle: its bound state and terrain, the call-order flags
-// and the terrain generation (bumped by every rover_set_terrain*), plus the one word of camera bookkeeping the handle keeps
-// for it: which workspace was prepared for which terrain generation.
+// What another translation unit (camera_kernels.hip) may read of a handle: its device, its bound state and terrain, the
+// call-order flags and the terrain generation (bumped by every rover_set_terrain*), plus the one word of camera bookkeeping
+// the handle keeps for it: which workspace was prepared for which terrain generation.
 struct rover_sim_view {
+    int device;              // the handle's HIP device (DeviceGuard)
     const float *state;      // SoA state words, state[word * n + env]; NULL before rover_bind
     int n;
     bool have_terrain, phase_open;

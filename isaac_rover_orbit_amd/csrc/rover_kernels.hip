@@ -3727,20 +3727,6 @@ int fail(int code, const char *fmt, const char *detail = "")
         if (_e != hipSuccess) return fail(ROVER_ERR_HIP, #expr ": %s", hipGetErrorString(_e));                        \
     } while (0)
 
-// Every entry point that launches work runs on the handle's device, whatever the calling thread's current device is.
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-
 }  // namespace
 
 int rover_internal_fail(int code, const char *fmt, const char *detail) { return fail(code, fmt, detail); }
@@ -3779,7 +3765,7 @@ struct rover_sim {
 rover_sim_view rover_internal_view(rover_sim *sim)
 {
     const RvParams &p = sim->p;
-    return rover_sim_view{sim->state, p.n, sim->have_terrain, sim->phase_open, p.height, p.H, p.W, p.res, p.min_x, p.min_y,
+    return rover_sim_view{sim->device, sim->state, p.n, sim->have_terrain, sim->phase_open, p.height, p.H, p.W, p.res, p.min_x, p.min_y,
                           sim->terrain_gen, &sim->camera_ws, &sim->camera_gen};
 }
 

@@ -5,6 +5,8 @@
 * ``cast``:            exact first hit of each ray with the heightfield's triangle mesh (cells split along the (i, j) - (i+1, j+1)
                        diagonal, the mesh of ``oracle.mesh_raycast.heightfield_mesh``) by a cell DDA, plus the ray's clearance:
                        the smallest vertical gap ray - surface before the hit (over the whole march for a miss)
+* ``cast_brute``:      the same depth by brute force, every ray against the mesh's triangle list (Moller-Trumbore): the oracle that
+                       shares no algorithm with ``cast`` or the HIP kernel
 
 A miss (the ray leaves the x-y extent, climbs above the highest node or passes the far clip) is +inf; hits nearer than the near
 clip do not count.  The ray starts on one side of the surface (the side of its first point over the terrain, touching counts as
@@ -143,10 +145,12 @@ def cast(height, res, min_x, min_y, origins, dirs, near=0.01, far=1e6):
             t_c = np.where(crossed(g_m2), tm, tm + (tc - tm) * g_m2 / (g_m2 - g_c))
         hit = hit_a | hit_m | hit_c
         dep = np.where(hit_a, ta, np.where(hit_m, t_m, t_c))
-        # clearance before the hit: gap values at the piece ends passed without a crossing
-        cl = np.where(hit_a, np.inf, np.where(hit_m, g_a, np.minimum(g_a, np.where(split, np.minimum(g_m, g_m2), g_m))))
-        cl = np.where(hit, cl, np.minimum(np.minimum(g_a, g_m), np.where(split, np.minimum(g_m2, g_c), g_m)))
-        cl = np.where(ab, cl, -cl)
+        # clearance before the hit: gap values at the piece ends passed without a crossing, measured on the side the ray
+        # started on (a ray from below has negative gaps: its clearance is the smallest of their magnitudes)
+        sd = np.where(ab, 1.0, -1.0)
+        c_a, c_m, c_m2, c_c = sd * g_a, sd * g_m, sd * g_m2, sd * g_c
+        cl = np.where(hit_a, np.inf, np.where(hit_m, c_a, np.minimum(c_a, np.where(split, np.minimum(c_m, c_m2), c_m))))
+        cl = np.where(hit, cl, np.minimum(np.minimum(c_a, c_m), np.where(split, np.minimum(c_m2, c_c), c_m)))
         clear[a_] = np.minimum(clear[a_], cl)
         depth[a_[hit]] = dep[hit]
         step_x = tx <= ty
@@ -156,6 +160,75 @@ def cast(height, res, min_x, min_y, origins, dirs, near=0.01, far=1e6):
         ix[a_], iy[a_], t[a_] = nix, niy, tc
         act = a_[~hit & ~out]
     return depth, clear
+
+
+def _slab(o, d, lo, hi, t0, t1):
+    """Entry / exit t of rays o + t d (..., 3) through boxes [lo, hi] (..., 3), clipped to [t0, t1]; an axis the ray does not move
+    along admits every t when the origin lies in the slab (boundary included) and none otherwise."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a, b = (lo - o) / d, (hi - o) / d
+    par = d == 0
+    inside = (o >= lo) & (o <= hi)
+    ta = np.where(par, np.where(inside, -np.inf, np.inf), np.minimum(a, b))
+    tb = np.where(par, np.where(inside, np.inf, -np.inf), np.maximum(a, b))
+    return np.maximum(ta.max(-1), t0), np.minimum(tb.min(-1), t1)
+
+
+def cast_brute(height, res, min_x, min_y, origins, dirs, near=0.01, far=1e6, block=8):
+    """Depth of rays ``origins`` (R, 3) + t ``dirs`` (R, 3) (unit): the smallest t in [near, far] at which the ray meets a
+    triangle of ``oracle.mesh_raycast.heightfield_mesh`` (Moller-Trumbore, float64), +inf where there is none.
+
+    An oracle independent of ``cast``: no grid walk and no per-cell diagonal logic, only the mesh's triangle list.  The one
+    culling is conservative: a triangle is tested only when the ray passes through the box of its ``block`` x ``block`` cell
+    block and then of its cell (x-y extent of the nodes, z from their minimum to their maximum, widened by a hair)."""
+    from oracle.mesh_raycast import heightfield_mesh
+    h = np.asarray(height, dtype=np.float64)
+    H, W = h.shape
+    V, F = heightfield_mesh(h, res, min_x, min_y)
+    ncell = (H - 1) * (W - 1)
+    tri = V[F]                                               # (2 * ncell, 3, 3): cell k's triangles are k and ncell + k
+    # cell boxes, then block boxes over them
+    lo_c, hi_c = np.minimum(tri[:ncell].min(1), tri[ncell:].min(1)), np.maximum(tri[:ncell].max(1), tri[ncell:].max(1))
+    pad = 1e-9 * (1.0 + np.abs(V).max())
+    lo_c, hi_c = lo_c - pad, hi_c + pad
+    ci, cj = np.divmod(np.arange(ncell), W - 1)
+    bid = (ci // block) * ((W - 2) // block + 1) + cj // block
+    nb = int(bid.max()) + 1
+    lo_b, hi_b = np.full((nb, 3), np.inf), np.full((nb, 3), -np.inf)
+    np.minimum.at(lo_b, bid, lo_c)
+    np.maximum.at(hi_b, bid, hi_c)
+    cells_of = np.split(np.argsort(bid, kind="stable"), np.cumsum(np.bincount(bid, minlength=nb))[:-1])
+    o = np.asarray(origins, dtype=np.float64)
+    d = np.asarray(dirs, dtype=np.float64)
+    out = np.full(o.shape[0], np.inf)
+    for r in range(o.shape[0]):
+        ta, tb = _slab(o[r], d[r], lo_b, hi_b, near, far)
+        blocks = np.nonzero(ta <= tb)[0]
+        if blocks.size == 0:
+            continue
+        cells = np.concatenate([cells_of[b] for b in blocks])
+        ta, tb = _slab(o[r], d[r], lo_c[cells], hi_c[cells], near, far)
+        cells = cells[ta <= tb]
+        if cells.size == 0:
+            continue
+        t3 = tri[np.concatenate([cells, cells + ncell])]
+        v0 = t3[:, 0]
+        e1, e2 = t3[:, 1] - v0, t3[:, 2] - v0
+        p = np.cross(d[r], e2)
+        det = np.einsum("ij,ij->i", e1, p)
+        ok = det != 0.0                                      # 0: the ray runs in the triangle's plane (touching only)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            inv = 1.0 / det
+            s = o[r] - v0
+            u = np.einsum("ij,ij->i", s, p) * inv
+            q = np.cross(s, e1)
+            v = (q @ d[r]) * inv
+            t = np.einsum("ij,ij->i", e2, q) * inv
+            eps = 1e-12
+            ok &= (u >= -eps) & (v >= -eps) & (u + v <= 1.0 + eps) & (t >= near) & (t <= far)
+        if ok.any():
+            out[r] = t[ok].min()
+    return out
 
 
 def render(cam, height, res, min_x, min_y, pos, quat):
