@@ -22,10 +22,6 @@ extern "C" {
  * (rover_step_scan_kernel) wherever it can run, 2 = one launch, single tile per wave (rover_step_scan1_kernel).  Same results. */
 int rover_debug_set_fused(rover_sim *sim, int fused);
 
-/* Scan kernel of the two-launch path: 0 = automatic, 1 = the generic kernel on the step path as well, 2 = the step form with one
- * env per synchronisation round, 7 = the wave-private scan (the scan phase of the one-launch kernels) as a kernel of its own. */
-int rover_debug_set_scan_form(rover_sim *sim, int form);
-
 /* FrankaCubeLift-v0 step kernel: lanes per env (8 = default, 16) and the two-wave arm / cube pipeline (1 = on, 0 = off,
  * -1 = automatic by batch size).  Same results. */
 int rover_lift_debug_set_lanes(rover_lift_sim *sim, int lanes);

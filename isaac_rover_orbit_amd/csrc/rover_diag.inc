@@ -30,15 +30,5 @@ __device__ __forceinline__ void k1_stamp(int slot)
         g_k1_stamps[(size_t)blockIdx.x * 32 + slot] = t;
     }
 }
-// a stamp that does not wait for the wave's outstanding memory operations (is an instruction's ISSUE what takes the time?)
-__device__ __forceinline__ void k1_stamp_nowait(int slot)
-{
-    if (threadIdx.x == 0) {
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        g_k1_stamps[(size_t)blockIdx.x * 32 + slot] = t;
-    }
-}
 #define K1_STAMP(k) k1_stamp(k)
-#define K1_STAMP_NOWAIT(k) k1_stamp_nowait(k)
 #endif

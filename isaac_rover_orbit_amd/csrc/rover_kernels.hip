@@ -1114,7 +1114,6 @@ __device__ __forceinline__ void slot_sum4(float &a0, float &a1, float &a2, float
 #endif
 #ifndef K1_STAMP
 #define K1_STAMP(k) do { } while (0)
-#define K1_STAMP_NOWAIT(k) do { } while (0)
 #endif
 #ifndef K1_LITE
 #define K1_LITE(k) do { } while (0)
@@ -1538,7 +1537,7 @@ __device__ __forceinline__ float wave_sum(float x)
 
 // ================================================================================================ K1: step kernel
 // PHASE 0: the whole env step.  PHASE 1 / 2: the step in two halves with the caller in between (the product runs phase 1 in the
-// sixteen-lanes-per-env mapping, step_group_body<0, true>: no scratch; phase 1 here is its one-env-per-lane twin) -- the SLOW PATH for user-written
+// sixteen-lanes-per-env mapping, step_group_body<TWO_LAUNCH, false, true>: no scratch; phase 1 here is its one-env-per-lane twin) -- the SLOW PATH for user-written
 // reward / termination terms (rover_env_cfg.py:126-183 are tables of arbitrary `func=`; ORBIT's managers evaluate them on the
 // state the physics left, BEFORE _reset_idx).  1 = action, physics, counters, the built-in terms and their episodic sums: state,
 // reward, flags and forces are stored, nothing is reset.  2 = the rest of rover_env.py:89-99 for the reset mask the caller
@@ -1902,8 +1901,8 @@ __device__ __forceinline__ float patch_height(const cell_t *q, int pitch, float 
 // ------------------------------------------------------------------------------------------------ scan, wave-private form
 // The same rays from the same staged cells as rover_scan_step_kernel<true, TRI, ...>, cast by ONE wave for up to four envs
 // from two wave-private LDS tiles: no workgroup barrier, K1's launch shape (one wave per SIMD).  What hides the LDS latency is
-// the wave's own instruction-level parallelism (sixteen rays per lane, 256 VGPRs to unroll into).  As a kernel of its own
-// (measurement hook, rover_debug_set_scan_form(sim, 7)) and as the last phase of the fused step kernel.
+// the wave's own instruction-level parallelism (sixteen rays per lane, 256 VGPRs to unroll into).  The last phase of the
+// one-launch step kernels.
 struct PrivateWindows {      // wave-uniform: the windows of the wave's four envs
     float px[4], py[4], pz[4], cy[4], sy[4];
     int i_lo[4], j_lo[4], pk[4];
@@ -1950,90 +1949,12 @@ __device__ __forceinline__ float private_ray(const RvParams &p, const int16_t *t
 // compare-and-branch on M0 -- five instructions.  (hipcc's loop around the builtin took fifteen per load -- a mask and a branch
 // around every load, a 64-bit address add, M0 through a move and a nop -- and one wave per SIMD issues them one by one: 2.5 k
 // cycles per window, which round 3 read as the cost of the LDS-DMA instruction itself.)
-#ifdef RV_ROW_SPANS
-// Round 5, MEASURED AND NOT THE PRODUCT FORM (tools/build_diag.py SPANS; DESIGN.md section 6: bit-exact, fewer bytes, +1.0 us per
-// step -- the copy wave's instruction issue is what the staging phase costs, not its bytes): PER-ROW SPANS.  The staged box is the
-// bounding box of the yaw-rotated ray pattern (1.64 x its area averaged over the yaw): a chunk (eight cells of one row) is requested only where a ray can need it.  The LDS layout stays the dense tile the cast
-// addresses -- a lane that is switched off simply does not write its 16 bytes -- so nothing changes for the rays.  Which rows a
-// CHUNK COLUMN needs is an interval (the pattern's rectangle is convex): every lane derives, once per window, the iterations
-// [first, first + span] of the copy loop in which its (row-in-group, chunk) is wanted, and an iteration is the old five instructions
-// plus a subtract, an unsigned compare, two exec moves and a counter -- ten instructions for five, and ~70 per window to set up.
-//   rectangle: centre (uc, vc) in window cells, half extents (Hx, Hy), rotation (c, s);  a ray at (u, v) reads columns floor(u),
-//   floor(u) + 1 and rows floor(v), floor(v) + 1.  For the strip du in [da, db] of a chunk column (one cell + half a cell of slack
-//   each side) the rows' extent is bounded by  max_i min(l_i(da), l_i(db)) .. min_i max(h_i(da), h_i(db))  over the two edge pairs
-//   l_1/h_1 = -(c / s) du -/+ Hx / |s|,  l_2/h_2 = (s / c) du -/+ Hy / |c|  (a pair whose divisor is ~0 is dropped): an OUTER bound,
-//   whatever the rounding (v_rcp is enough); one more row of slack each side.  Windows that touch the map's edge (the cast clamps
-//   there) are copied whole.
-__device__ __forceinline__ void private_issue(const RvParams &p, const PrivateWindows &w, int j, int16_t *tile, int lane)
-{
-    const int th = w.pk[j] & 0x7FFF, tw4 = max(w.pk[j] >> 16, 1);
-    const int rpi = max(64 / tw4, 1);                                  // wave-uniform (tw4 <= 64: checked by the host)
-    const float inv_tw4 = 1.0f / (float)tw4;
-    const int lr = (int)(((float)lane + 0.5f) * inv_tw4);               // lane / tw4, exact
-    const int lc = lane - (int)__umul24(lr, tw4);
-    unsigned voff = (unsigned)(__umul24(lr, p.wq) + lc) * 16u;        // the lane's byte offset from the window's first chunk
-    const int16_t *base = p.height_q + ((size_t)w.i_lo[j] * p.W + w.j_lo[j]);
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) int16_t *)tile;
-    const int groups = __builtin_amdgcn_readfirstlane((th + rpi - 1) / rpi);   // copy-loop iterations: rpi rows each, the last one partial
-    const unsigned dstep = (unsigned)(rpi * tw4) * 16u, vstep = (unsigned)__umul24(rpi, p.wq) * 16u;
-    const float inv_rpi = 1.0f / (float)rpi;
-    // rows this lane's chunk column needs (window rows), then the loop iterations k with row k * rpi + lr among them
-    int r_first = 0, r_last = th - 1;
-    if ((w.pk[j] >> 15) & 1) {   // interior window (wave-uniform)
-        const float uc = (w.px[j] - p.min_x) * p.inv_res - (float)w.j_lo[j], vc = (w.py[j] - p.min_y) * p.inv_res - (float)w.i_lo[j];
-        const float Hx = 0.5f * p.cfg.scan_size_x * p.inv_res, Hy = 0.5f * p.cfg.scan_size_y * p.inv_res;
-        const float c = w.cy[j], sn = w.sy[j];
-        const bool use1 = fabsf(sn) > 1.0e-3f, use2 = fabsf(c) > 1.0e-3f;
-        const float is = __builtin_amdgcn_rcpf(use1 ? sn : 1.0f), ic = __builtin_amdgcn_rcpf(use2 ? c : 1.0f);
-        const float m1 = use1 ? -c * is : 0.0f, w1 = use1 ? Hx * fabsf(is) : 1.0e9f;
-        const float m2 = use2 ? sn * ic : 0.0f, w2 = use2 ? Hy * fabsf(ic) : 1.0e9f;
-        const float da = (float)(8 * lc) - 1.5f - uc, db = (float)(8 * lc + 7) + 1.5f - uc;
-        const float pa = m1 * da, pb = m1 * db, qa = m2 * da, qb = m2 * db;
-        const float lo = fmaxf(fminf(pa, pb) - w1, fminf(qa, qb) - w2), hi = fminf(fmaxf(pa, pb) + w1, fmaxf(qa, qb) + w2);
-        // (slack: the slopes carry v_rcp's ulp and |du| <= ~110 cells: 1e-4 cells; one whole row each side on top of the +1 of floor(v) + 1)
-        r_first = max((int)floorf(vc + lo) - 1, 0);
-        r_last = min((int)floorf(vc + hi) + 2, th - 1);
-    }
-    // k * rpi + lr in [r_first, r_last]:  k >= (r_first - lr) / rpi (floor: one group early at most),  k <= floor((r_last - lr) / rpi)
-    const int kf = max((int)floorf(((float)(r_first - lr) + 0.5f) * inv_rpi), 0);
-    const int kl = (int)floorf(((float)(r_last - lr) + 0.5f) * inv_rpi);
-    const bool never = lr >= rpi || kl < kf || r_last < r_first;
-    const unsigned first = never ? 0x7FFFFFFFu : (unsigned)kf, span = never ? 0u : (unsigned)(kl - kf);
-    unsigned long long saved;
-    unsigned t;
-    unsigned m0_saved;
-    unsigned k = 0u;
-    asm volatile(
-        "s_mov_b64 %[saved], exec\n\t"
-        "s_mov_b32 %[m0s], m0\n\t"
-        "s_mov_b32 m0, %[lds0]\n\t"
-        "s_cmp_lt_u32 %[k], %[groups]\n\t"
-        "s_cbranch_scc0 2f\n"
-        "1:\n\t"
-        "v_sub_u32 %[t], %[k], %[first]\n\t"
-        "v_cmp_le_u32 vcc, %[t], %[span]\n\t"
-        "s_and_b64 exec, %[saved], vcc\n\t"
-        "global_load_lds_dwordx4 %[voff], %[base]\n\t"
-        "s_mov_b64 exec, %[saved]\n\t"
-        "v_add_u32 %[voff], %[vstep], %[voff]\n\t"
-        "s_add_u32 m0, m0, %[dstep]\n\t"
-        "s_add_u32 %[k], %[k], 1\n\t"
-        "s_cmp_lt_u32 %[k], %[groups]\n\t"
-        "s_cbranch_scc1 1b\n"
-        "2:\n\t"
-        "s_mov_b32 m0, %[m0s]"
-        : [saved] "=&s"(saved), [m0s] "=&s"(m0_saved), [voff] "+v"(voff), [k] "+s"(k), [t] "=&v"(t)
-        : [lds0] "s"(lds0), [groups] "s"((unsigned)groups), [base] "s"(base), [vstep] "s"(vstep), [dstep] "s"(dstep),
-          [first] "v"(first), [span] "v"(span)
-        : "memory", "scc", "vcc");
-}
-#else
 __device__ __forceinline__ void private_issue(const RvParams &p, const PrivateWindows &w, int j, int16_t *tile, int lane)
 {
     const int th = w.pk[j] & 0x7FFF, tw4 = max(w.pk[j] >> 16, 1);
     // Quotients of small integers by v_rcp_f32 (a <= tile_dim <= 1024, b <= 64: the exact quotient's fractional part is 0 or >= 1 / 64,
     // the product's error < 1e-4, so floor(a * rcp(b) + 1e-3) IS a / b): four instructions where hipcc's integer division takes ~25 --
-    // three quotients per window, on the copy wave's chain between barrier A and barrier B
+    // three quotients per window, on the copy wave's chain behind barrier A
     const float inv_tw4 = __builtin_amdgcn_rcpf((float)tw4);
     const int rpi = __builtin_amdgcn_readfirstlane(max((int)(64.0f * inv_tw4 + 1.0e-3f), 1));   // 64 / tw4: wave-uniform (tw4 <= 64: checked by the host)
     const int lr = (int)(((float)lane + 0.5f) * inv_tw4);               // lane / tw4 (fractional part >= 0.5 / 64)
@@ -2073,7 +1994,6 @@ __device__ __forceinline__ void private_issue(const RvParams &p, const PrivateWi
           [dstep] "s"(dstep)
         : "memory", "scc");
 }
-#endif
 // (Measured and not kept: the same copy through registers -- 16-byte global loads issued before the rays of the env that still
 // occupies the tile, LDS writes afterwards.  A single wave issues one global_load_lds_dwordx4 every ~145 cycles, 2.6 k cycles per
 // window during which nothing else of the wave issues; the register route was slower still: 53.0 us per step against 48.3 us.
@@ -2203,7 +2123,7 @@ __device__ __forceinline__ float *private_row(float *out, int e, int row_stride,
                      (unsigned)__builtin_amdgcn_readfirstlane((int)a));
 }
 // A lane without a ray in round m repeats ray 0 (the table says so) and stores nothing: no branches inside an env's rounds --
-// one basic block.  Rounds [M0, M1) of the env's sixteen (the step wave and its copy wave share an env's rays).
+// one basic block.
 // The pipelined path is for interior windows of DENSE patterns (961 .. 1024 rays: 31 x 31 and 32 x 32, every round but the last
 // full -- its stores need no lane mask, and a mask costs scalar instructions that one wave per SIMD issues no faster than vector
 // ones); anything else takes the rolled loop below.
@@ -2219,20 +2139,17 @@ __device__ __forceinline__ float *private_row(float *out, int e, int row_stride,
 //   * cell address = ((i0 * pitch + j0) << 1) + (tile - 2 (i_lo * pitch + j_lo)): one v_mad_u32_u24, one v_lshl_add_u32;
 //   * pz - hgt * q_scale as ONE fma: q_scale is a power of two (rover_set_terrain_q16 checks), so the product is exact and the
 //     fused form rounds the same real number once, like the subtraction did.
-template <bool TRI, int M0 = 0, int M1 = PRIVATE_ROUNDS>
+template <bool TRI>
 __device__ __forceinline__ void private_cast(const RvParams &p, const PrivateWindows &w, int j, const int16_t *tile, int lane, int e_base,
                                              float *__restrict__ out, int row_stride, int col0, const f2 (&oxy)[PRIVATE_ROUNDS],
                                              const float2 *__restrict__ ray_xy)
 {
-    if constexpr (M1 <= M0) {   // an empty share
-        return;
-    } else {
     constexpr int CC = 8, G = PRIVATE_GROUP;
-    static_assert(G == 4 && M0 % 4 == 0 && M1 % 4 == 0, "a share is whole quads of rounds");
+    static_assert(G == 4 && PRIVATE_ROUNDS % 4 == 0, "the rounds are whole quads");
     const int th = w.pk[j] & 0x7FFF;
     const int pitch = (w.pk[j] >> 16) * CC;
     float *row = private_row(out, e_base + j, row_stride, col0);   // wave-uniform by construction (e_base is the wave's first env)
-    if (M0 * 64 >= p.rays) return;
+    if (p.rays <= 0) return;
     if (__builtin_expect(((w.pk[j] >> 15) & 1) && p.rays > 64 * (PRIVATE_ROUNDS - 1), 1)) {   // (the common case falls through)
         typedef const __attribute__((address_space(3))) int16_t *lds_cell_ptr;
         const f2 A = {w.cy[j], w.sy[j]}, BN = {-w.sy[j], w.cy[j]}, P = {w.px[j], w.py[j]}, NMIN = {-p.min_x, -p.min_y};
@@ -2246,7 +2163,7 @@ __device__ __forceinline__ void private_cast(const RvParams &p, const PrivateWin
         float fx[2][G], fy[2][G];
         int h00[2][G], h01[2][G], h10[2][G], h11[2][G];   // TRI: h01 holds the ONE middle corner (01 or 10), h10 is unused
         const unsigned row1m = 2u * (unsigned)pitch - 2u;   // byte distance from cell (i, j) to cell (i + 1, j) minus one cell
-        constexpr int NG = (M1 - M0 + G - 1) / G;
+        constexpr int NG = PRIVATE_ROUNDS / G;
 #pragma unroll
         for (int g = 0; g <= NG; ++g) {
             const int b = g & 1;
@@ -2255,7 +2172,7 @@ __device__ __forceinline__ void private_cast(const RvParams &p, const PrivateWin
                 f2 t0[G], t1[G];
                 // stage-major over the group's rays: no packed op reads the result of the one before it
 #define RV_CAST_STAGE(...)                                                                                         \
-    _Pragma("unroll") for (int q = 0; q < G; ++q) { const int m = M0 + g * G + q; if (m < M1) { __VA_ARGS__ } }
+    _Pragma("unroll") for (int q = 0; q < G; ++q) { const int m = g * G + q; __VA_ARGS__ }
                 RV_CAST_STAGE(t0[q] = A * (f2){oxy[m].x, oxy[m].x};)
                 RV_CAST_STAGE(t1[q] = pk_mul_hi(oxy[m], BN);)
                 RV_CAST_STAGE(t0[q] = t0[q] + t1[q];)
@@ -2275,11 +2192,8 @@ __device__ __forceinline__ void private_cast(const RvParams &p, const PrivateWin
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < G; ++q) {
-                    const int m = M0 + g * G + q;
-                    if (m < M1) {
-                        if (TRI) lds_cell3_issue(a0[q], mid[q], r1m[q], h00[b][q], h01[b][q], h11[b][q]);
-                        else lds_cell4_issue(a0[q], a0[q] + 2u * (unsigned)pitch, h00[b][q], h01[b][q], h10[b][q], h11[b][q]);
-                    }
+                    if (TRI) lds_cell3_issue(a0[q], mid[q], r1m[q], h00[b][q], h01[b][q], h11[b][q]);
+                    else lds_cell4_issue(a0[q], a0[q] + 2u * (unsigned)pitch, h00[b][q], h01[b][q], h10[b][q], h11[b][q]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -2298,36 +2212,33 @@ __device__ __forceinline__ void private_cast(const RvParams &p, const PrivateWin
                 }
 #pragma unroll
                 for (int q = 0; q < G; ++q) {
-                    const int m = M0 + (g - 1) * G + q;
-                    if (m < M1) {
-                        float hgt;
-                        const float f00 = (float)h00[pb][q], f11 = (float)h11[pb][q];
-                        if (TRI) {
-                            const bool lower = fx[pb][q] >= fy[pb][q];
-                            const float pm = (float)h01[pb][q];   // the middle corner the address select fetched: 01 (lower) or 10
-                            const float d1 = pm - f00, d2 = f11 - pm;
-                            const float ta = lower ? d1 : d2, tb = lower ? d2 : d1;
-                            hgt = fmaf(fy[pb][q], tb, fmaf(fx[pb][q], ta, f00));
-                        } else {
-                            const float f01 = (float)h01[pb][q], f10 = (float)h10[pb][q];
-                            const float dx0 = f01 - f00, dx1 = f11 - f10;
-                            const float hx0 = f00 + fx[pb][q] * dx0;
-                            const float hx1 = f10 + fx[pb][q] * dx1;
-                            hgt = hx0 + fy[pb][q] * (hx1 - hx0);
-                        }
-                        ov[q] = fmaf(nqs, hgt, pz) - hoff;   // observations.py:45
+                    float hgt;
+                    const float f00 = (float)h00[pb][q], f11 = (float)h11[pb][q];
+                    if (TRI) {
+                        const bool lower = fx[pb][q] >= fy[pb][q];
+                        const float pm = (float)h01[pb][q];   // the middle corner the address select fetched: 01 (lower) or 10
+                        const float d1 = pm - f00, d2 = f11 - pm;
+                        const float ta = lower ? d1 : d2, tb = lower ? d2 : d1;
+                        hgt = fmaf(fy[pb][q], tb, fmaf(fx[pb][q], ta, f00));
+                    } else {
+                        const float f01 = (float)h01[pb][q], f10 = (float)h10[pb][q];
+                        const float dx0 = f01 - f00, dx1 = f11 - f10;
+                        const float hx0 = f00 + fx[pb][q] * dx0;
+                        const float hx1 = f10 + fx[pb][q] * dx1;
+                        hgt = hx0 + fy[pb][q] * (hx1 - hx0);
                     }
+                    ov[q] = fmaf(nqs, hgt, pz) - hoff;   // observations.py:45
                 }
                 {
                     const v4f_t o4 = {ov[0], ov[1], ov[2], ov[3]};
-                    private_store_quad(row, lane, p.rays, (M0 >> 2) + g - 1, o4, p.nt_obs != 0);
+                    private_store_quad(row, lane, p.rays, g - 1, o4, p.nt_obs != 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
     } else {
 #pragma unroll 1
-        for (int m = M0; m < M1; ++m) {
+        for (int m = 0; m < PRIVATE_ROUNDS; ++m) {
             if (private_ray_index(m, 0) < p.rays) {
                 // (the table registers indexed by a loop counter would leave the registers: the slow path re-reads the table)
                 const float2 xy = ray_xy[m * 64 + lane];
@@ -2338,57 +2249,13 @@ __device__ __forceinline__ void private_cast(const RvParams &p, const PrivateWin
             }
         }
     }
-    }
-}
-// ray_xy: 1024 x (x, y) pattern offsets, entry m * 64 + lane = ray private_ray_index(m, lane) (rays past the pattern repeat ray 0), built by the host
-template <bool TRI>
-__device__ __forceinline__ void scan_private_wave(const RvParams &p, int16_t *tile0, int16_t *tile1, int lane, int n_env, int e_base,
-                                                  const PrivateWindows &w, float *__restrict__ out, int row_stride, int col0,
-                                                  const float2 *__restrict__ ray_xy)
-{
-    constexpr int ROUNDS = PRIVATE_ROUNDS;
-    auto issue = [&](int j, int16_t *tile) { private_issue(p, w, j, tile, lane); };
-    f2 oxy[ROUNDS];
-    auto cast = [&](int j, const int16_t *tile) { private_cast<TRI>(p, w, j, tile, lane, e_base, out, row_stride, col0, oxy, ray_xy); };
-    if (n_env <= 0) return;
-    issue(0, tile0);
-    if (n_env > 1) issue(1, tile1);
-#pragma unroll
-    for (int m = 0; m < ROUNDS; ++m) {
-        const float2 v = ray_xy[m * 64 + lane];
-        oxy[m] = (f2){v.x, v.y};
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    K1_STAMP(27);
-    cast(0, tile0);
-    K1_STAMP(28);
-    if (n_env > 2) {   // tile 0 is dead (its LDS reads have returned: their values were consumed); env 2's window lands under env 1's rays
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        issue(2, tile0);
-        K1_STAMP_NOWAIT(19);
-    }
-    if (n_env > 1) cast(1, tile1);
-    K1_STAMP(29);
-    if (n_env > 2) {   // env 2's window was issued before env 1's rays: it has landed; env 3's goes out now and lands under env 2's rays
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        if (n_env > 3) issue(3, tile1);
-        K1_STAMP(30);
-        cast(2, tile0);
-    }
-    K1_STAMP(31);
-    if (n_env > 3) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-        cast(3, tile1);
-    }
 }
 
 // ---- the fused step kernel's scan phase WITHOUT copy waves, ONE tile per wave: for batches of more than one round of workgroups
 // (N > 16 x CUs).  Copy waves would put four 256-VGPR waves on a SIMD (two workgroups per CU); here a workgroup is the four step
 // waves with 4 x 18.9 KB of LDS, two workgroups share a CU as on the two-launch path, and what fills one wave's copy stalls
 // (2.5 k cycles per window) and LDS latencies is the other workgroup's wave on the same SIMD.
+// ray_xy: 1024 x (x, y) pattern offsets, entry m * 64 + lane = ray private_ray_index(m, lane) (rays past the pattern repeat ray 0), built by the host
 template <bool TRI>
 __device__ __forceinline__ void scan_single_tile_wave(const RvParams &p, int16_t *tile, int lane, int n_env, int e_base,
                                                       const PrivateWindows &w, float *__restrict__ out, int row_stride, int col0,
@@ -2423,8 +2290,8 @@ __device__ __forceinline__ void scan_single_tile_wave(const RvParams &p, int16_t
 // the LAST substep, evaluates the link-body sample points and the wheels' obstacle look-ups of the contact report.  The reset is
 // decided by the step wave right after the physics (mdp_terminations: the other termination terms are functions of words loaded
 // before the physics).  Windows travel through LDS (win[wave][env][8 words]).
-// Round 5, the product form (RV_OWN_TILES = 1): TWO workgroup barriers, executed by all eight waves on every path, and ONE polled
-// LDS word per env (word 3 of the env's position slot in the hand-over area):
+// TWO workgroup barriers, executed by all eight waves on every path, and ONE polled LDS word per env (word 3 of the env's position
+// slot in the hand-over area):
 //   L   pose + bogie angles of the last substep's start written | copy: link-point forces, obstacle heights | step: the last substep
 //   A   pose the physics left + link forces written (word = 0)  | step: contact report, collision flag, RESET DECISION -> word = 1 | 2,
 //       manager tail                                            | copy: windows of the four poses, window 0 requested at once into
@@ -2433,8 +2300,8 @@ __device__ __forceinline__ void scan_single_tile_wave(const RvParams &p, int16_t
 //   then each wave OWNS A TILE and runs at its own pace, no barrier:
 //       copy wave, tile 0: wait, rays of env 0, request window 2, wait, rays of env 2
 //       step wave, tile 1: polls the word for 3, reads `win`, requests window 1, wait, rays of env 1, request window 3, wait, rays of env 3
-// The barrier form (RV_OWN_TILES = 0; rounds 4 - 5: the copy wave requests all four windows, the waves meet at barriers B, C, D and
-// split envs 1 - 3 by RV_SHARE_*) is kept as a build variant (tools/build_diag.py BARRIERS): 38.90 -> 37.77 us per step for the own-tiles form.
+// No tile is touched by two waves: only the windows and the word cross between them.  (Rounds 4 - 5 ran a barrier form -- the copy
+// wave requested all four windows, the waves met at three more barriers -- 1.1 us per step slower; docs/history.md section 14.)
 // A single wave's cast is bound by its instruction issue (~5 cycles per instruction); all eight waves of a CU casting at once are bound
 // by the LDS array (three 16-bit reads per ray-round x 8 waves; profiles/r05_exec_probe.txt).
 __device__ __forceinline__ void windows_to_lds(float *win, const ScanWindow &sw, int lane)
@@ -2467,22 +2334,6 @@ __device__ __forceinline__ float *fused_win(float *lds, const RvParams &p, int w
     return reinterpret_cast<float *>(reinterpret_cast<int16_t *>(lds) + (size_t)8 * p.tile_dim * p.tile_pitch) + wv * 64;
 }
 __device__ __forceinline__ float *fused_link(float *lds, const RvParams &p, int wv) { return fused_win(lds, p, 0) + 256 + wv * RV_HAND; }
-// Rounds (whole quads) of an env's sixteen cast by the STEP wave; the copy wave takes the rest.  Env 0 is the copy wave's alone
-// (cast under the manager tail, so that tile 0 is free for window 2 before barrier B); beside env 2 it stages window 3.
-#ifndef RV_OWN_TILES
-#define RV_OWN_TILES 1   // 1: each wave of a pair stages and casts two envs through its own tile, no barrier behind A; 0: the barrier form (B, C, D)
-#endif
-#ifndef RV_SHARE_1
-#define RV_SHARE_1 16
-#endif
-#ifndef RV_SHARE_2
-#define RV_SHARE_2 16
-#endif
-#ifndef RV_SHARE_3
-#define RV_SHARE_3 8
-#endif
-constexpr int SHARE_1 = RV_SHARE_1, SHARE_2 = RV_SHARE_2, SHARE_3 = RV_SHARE_3;
-constexpr int SHARE_MAX = SHARE_1 > SHARE_2 ? (SHARE_1 > SHARE_3 ? SHARE_1 : SHARE_3) : (SHARE_2 > SHARE_3 ? SHARE_2 : SHARE_3);
 template <bool TRI>
 __device__ __forceinline__ void scan_copy_wave(const RvParams &p, const float *__restrict__ state, float *lds, int partner, int lane,
                                                float *__restrict__ obs, const float2 *__restrict__ ray_xy)
@@ -2555,7 +2406,6 @@ __device__ __forceinline__ void scan_copy_wave(const RvParams &p, const float *_
         const ScanWindow sw = scan_window(p, pf, qf);
         private_windows(sw, w);
         if (n_env > 0) private_issue(p, w, 0, tile0, lane);
-        if (!RV_OWN_TILES && n_env > 1) private_issue(p, w, 1, tile1, lane);
         // the step wave's decision (it does not wait for this wave: no barrier): poll the word of this lane's env.  Bounded -- a
         // protocol error must end as a wrong observation the parity tests catch, not as a hung GPU
         float flag = 0.0f;
@@ -2584,66 +2434,34 @@ __device__ __forceinline__ void scan_copy_wave(const RvParams &p, const float *_
             // restage what was requested for a pose that is no longer the final one: the earlier copy into the same tile must have
             // landed first (two LDS-DMA streams into one tile would interleave)
             if (n_env > 0 && (rmask & 0x1ull)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); private_issue(p, w, 0, tile0, lane); }
-            if (!RV_OWN_TILES && n_env > 1 && (rmask & 0x10000ull)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); private_issue(p, w, 1, tile1, lane); }
         } else {
             windows_to_lds(const_cast<float *>(win), sw, lane);
         }
-        if (RV_OWN_TILES) {
-            // "the final windows stand in `win`": the reset word once more (0 -> 1 | 2 by the step wave -> 3 here; a wave's LDS operations
-            // complete in order).  The step wave polls it behind its tail and then stages and casts envs 1 and 3 from ITS tile
-            if ((lane & 15) == 0)
-                *(volatile __attribute__((address_space(3))) float *)(__attribute__((address_space(3))) float *)(lk + 48 + (lane >> 4) * 4 + 3) = 3.0f;
-        }
+        // "the final windows stand in `win`": the reset word once more (0 -> 1 | 2 by the step wave -> 3 here; a wave's LDS operations
+        // complete in order).  The step wave polls it behind its tail and then stages and casts envs 1 and 3 from ITS tile
+        if ((lane & 15) == 0)
+            *(volatile __attribute__((address_space(3))) float *)(__attribute__((address_space(3))) float *)(lk + 48 + (lane >> 4) * 4 + 3) = 3.0f;
     }
     K1_LITE(3);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     K1_LITE(4);
-    if (RV_OWN_TILES) {
-        // EACH WAVE OWNS A TILE (round 5): this wave stages and casts envs 0 and 2 through tile 0, the step wave envs 1 and 3 through tile 1,
-        // each at its own pace -- no barrier behind A.  (The barrier form below had this wave request all four windows and the two waves
-        // meet at B, C, D: the step wave idled ~4 k cycles at B behind its tail while this wave's chain ran.)
-        if (n_env > 0) private_cast<TRI, 0, PRIVATE_ROUNDS>(p, w, 0, tile0, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
-        K1_LITE(5);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // this wave's reads of tile 0 have returned: the tile is free
-        K1_LITE(6);
-        K1_LITE(7);
-        if (n_env > 2) private_issue(p, w, 2, tile0, lane);
-        K1_LITE(8);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        K1_LITE(9);
-        K1_LITE(10);
-        K1_LITE(11);
-        if (n_env > 2) private_cast<TRI, 0, PRIVATE_ROUNDS>(p, w, 2, tile0, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
-        K1_LITE(12);
-        K1_LITE(13);
-        K1_LITE(14);
-        K1_LITE(15);
-        return;
-    }
-    // env 0 under the step wave's manager tail.  (Measured, us per step at 4096 envs: this order 33.8; window 2 requested before
-    // barrier B as well 34.35 -- the step wave waits for the request's issue; window 1 requested only after env 0's cast 34.35.)
-    if (n_env > 0) private_cast<TRI, 0, PRIVATE_ROUNDS>(p, w, 0, tile0, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
+    // EACH WAVE OWNS A TILE: this wave stages and casts envs 0 and 2 through tile 0, the step wave envs 1 and 3 through tile 1, each
+    // at its own pace -- no barrier behind A
+    if (n_env > 0) private_cast<TRI>(p, w, 0, tile0, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
     K1_LITE(5);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // this wave's reads of tile 0 have returned: the tile is free
     K1_LITE(6);
-    __syncthreads();                                                    // B: env 0 is cast, tile 0 is free
     K1_LITE(7);
     if (n_env > 2) private_issue(p, w, 2, tile0, lane);
-    if (n_env > 1) private_cast<TRI, SHARE_1, PRIVATE_ROUNDS>(p, w, 1, tile1, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
     K1_LITE(8);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     K1_LITE(9);
-    __syncthreads();                                                    // C: window 2 has landed, tile 1 is free
     K1_LITE(10);
-    if (n_env > 3) private_issue(p, w, 3, tile1, lane);
     K1_LITE(11);
-    if (n_env > 2) private_cast<TRI, SHARE_2, PRIVATE_ROUNDS>(p, w, 2, tile0, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
+    if (n_env > 2) private_cast<TRI>(p, w, 2, tile0, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
     K1_LITE(12);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     K1_LITE(13);
-    __syncthreads();                                                    // D: window 3 has landed
     K1_LITE(14);
-    if (n_env > 3) private_cast<TRI, SHARE_3, PRIVATE_ROUNDS>(p, w, 3, tile1, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
     K1_LITE(15);
 }
 
@@ -2654,12 +2472,14 @@ __device__ __forceinline__ void scan_copy_wave(const RvParams &p, const float *_
 // the younger one starves behind the older one's VALU stream (measured: 61 us instead of 30 us).
 // Physics: one wheel slot x role per lane, chassis replicated; MDP tail (terminations, rewards, reset, command):
 // replicated in the 16 lanes, stored by lane 0 of the group.
-// FUSE: 0 = the step alone (the scan kernel follows as a second launch and reads the 32-byte descriptors); 1 / 2 = the height
-// scan of the wave's four envs (bilinear patch / triangle mesh, int16 terrain copy) is the LAST PHASE of the same wave, from two
-// wave-private LDS tiles (scan_private_wave): one launch per env step, no descriptor round trip, no second dispatch.
+// FORM: TWO_LAUNCH = the step alone (the scan kernel follows as a second launch and reads the 32-byte descriptors); COPY_WAVES /
+// SINGLE_TILE = the height scan of the wave's four envs (int16 terrain copy) is the LAST PHASE of the same wave, from wave-private
+// LDS tiles filled by a copy wave (scan_copy_wave) or by the wave itself (scan_single_tile_wave): one launch per env step, no
+// descriptor round trip, no second dispatch.  TRI: the scan's surface is the triangle mesh, else the bilinear patch (one-launch forms).
 // BEGIN_ONLY: the first half of the two-phase step (rover_step_begin; see step_lane_body): everything up to the reset decision
 // is stored -- physical state, manager words, reward, flags, force rows -- and nothing is reset.
-template <int FUSE, bool BEGIN_ONLY = false>
+enum StepForm { TWO_LAUNCH, COPY_WAVES, SINGLE_TILE };
+template <StepForm FORM, bool TRI, bool BEGIN_ONLY = false>
 __device__ __forceinline__ void step_group_body(const RvParams &p, float *__restrict__ state, const float *__restrict__ action,
                                                 float *__restrict__ obs, float *__restrict__ reward, uint8_t *__restrict__ terminated,
                                                 uint8_t *__restrict__ truncated, float *__restrict__ force,
@@ -2713,7 +2533,7 @@ __device__ __forceinline__ void step_group_body(const RvParams &p, float *__rest
 #pragma unroll
     for (int i = ROVER_TIME_LEFT; i < ROVER_LAMBDA_N; ++i) S[i] = state[(size_t)i * N + e];
     S[ROVER_RESET_COUNT] = state[(size_t)ROVER_RESET_COUNT * N + e];
-    if constexpr (FUSE == 1 || FUSE == 2) {
+    if constexpr (FORM == COPY_WAVES) {
         // copy-wave form: the link-body sample points of the contact report (evaluated at the pose of the last substep's START)
         // are the copy wave's work -- it is asleep until now; this wave goes straight into the substep
         const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -2732,7 +2552,7 @@ __device__ __forceinline__ void step_group_body(const RvParams &p, float *__rest
     }
     K1_STAMP(20);
     K1_LITE(1);
-    if constexpr (FUSE == 1 || FUSE == 2) {
+    if constexpr (FORM == COPY_WAVES) {
         // the pose the physics left: handed to the copy wave, which derives the scan windows itself and requests the first two right
         // behind barrier A -- before the reset decision exists; an env that then resets (rare) gets its window restaged
         const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -2780,7 +2600,7 @@ __device__ __forceinline__ void step_group_body(const RvParams &p, float *__rest
         }
     }
     int coll_known = -1;   // one-launch forms: the collision flag, evaluated ahead of the other terms
-    if constexpr (FUSE == 1 || FUSE == 2) {
+    if constexpr (FORM == COPY_WAVES) {
         // The reset is decided NOW -- time-out / success / far are functions of words loaded before the physics (B-13: the terms
         // see the previous step's command), the collision flag of the report just gathered -- so the FINAL pose is known here: the
         // pose the physics left, or the spawn pose the copy wave drew.  Its windows go to the copy wave, which stages them and
@@ -2800,11 +2620,8 @@ __device__ __forceinline__ void step_group_body(const RvParams &p, float *__rest
         // the ray table of the scan phase: requested now, so that it arrives under the manager tail
 #pragma unroll
         for (int m = 0; m < PRIVATE_ROUNDS; ++m) {
-            oxy[m] = (f2){0.0f, 0.0f};
-            if (m < SHARE_MAX) {
-                const float2 v = ray_xy[m * 64 + lane];
-                oxy[m] = (f2){v.x, v.y};
-            }
+            const float2 v = ray_xy[m * 64 + lane];
+            oxy[m] = (f2){v.x, v.y};
         }
     }
     K1_LITE_F(11);
@@ -2886,7 +2703,7 @@ __device__ __forceinline__ void step_group_body(const RvParams &p, float *__rest
     }
     const uint32_t gid = (uint32_t)(p.env_id_offset + e);
     if (__builtin_expect(any_reset, 0) && do_reset) {   // (any_reset: some env of the wave resets -- wave-uniform, rare)
-        if constexpr (FUSE == 1 || FUSE == 2) {   // drawn by the copy wave during the physics (scan_copy_wave)
+        if constexpr (FORM == COPY_WAVES) {   // drawn by the copy wave during the physics (scan_copy_wave)
             const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
             const float4 *d = reinterpret_cast<const float4 *>(fused_link(lds, p, wv) + 256 + (lane >> 4) * 12);
             const float4 d0 = d[0], d1 = d[1], d2 = d[2];
@@ -2947,7 +2764,7 @@ __device__ __forceinline__ void step_group_body(const RvParams &p, float *__rest
             const float x = pick_by_lane<1, 4, 0, 4>(r, head, head[0]);
             if (r < 4) o[r] = x;
         }
-        if (FUSE == 0 && r == 0) write_scan_desc(p, S + ROVER_POS, S + ROVER_QUAT, e);
+        if (FORM == TWO_LAUNCH && r == 0) write_scan_desc(p, S + ROVER_POS, S + ROVER_QUAT, e);
         if (do_reset) store_rows_by_lane<ROVER_POS, 7, ROVER_POS>(state, N, e, r, S);
         static_assert(ROVER_LAMBDA_N - ROVER_TARGET_W == 26, "manager words 39..64");
         store_rows_by_lane<ROVER_TARGET_W, 16, ROVER_TARGET_W>(state, N, e, r, S);
@@ -2960,17 +2777,17 @@ __device__ __forceinline__ void step_group_body(const RvParams &p, float *__rest
         }
     }
     K1_STAMP(25);
-    if constexpr (FUSE == 3 || FUSE == 4) {   // no copy waves, one tile per wave (more than one round of workgroups)
+    if constexpr (FORM == SINGLE_TILE) {   // no copy waves, one tile per wave (more than one round of workgroups)
         const int tile_cells = p.tile_dim * p.tile_pitch;
         const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         int16_t *tile = reinterpret_cast<int16_t *>(lds) + (size_t)wv * tile_cells;
         PrivateWindows pw;
         private_windows(scan_window(p, S + ROVER_POS, S + ROVER_QUAT), pw);
-        scan_single_tile_wave<FUSE == 4>(p, tile, lane, max(0, min(4, p.n - wave * 4)), wave * 4, pw, obs, p.obs_w, 4, ray_xy);
+        scan_single_tile_wave<TRI>(p, tile, lane, max(0, min(4, p.n - wave * 4)), wave * 4, pw, obs, p.obs_w, 4, ray_xy);
         K1_STAMP(26);
     }
-    if constexpr (FUSE == 1 || FUSE == 2) {
-        // ---- height scan of the wave's envs 1, 2, 3 (env 0: the copy wave's, under the tail above; see scan_copy_wave for the protocol)
+    if constexpr (FORM == COPY_WAVES) {
+        // ---- height scan of the wave's envs 1 and 3 (envs 0 and 2: the copy wave's; see scan_copy_wave for the protocol)
         const int tile_cells = p.tile_dim * p.tile_pitch;
         const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         int16_t *tile0 = reinterpret_cast<int16_t *>(lds) + (size_t)(2 * wv) * tile_cells, *tile1 = tile0 + tile_cells;
@@ -2978,64 +2795,40 @@ __device__ __forceinline__ void step_group_body(const RvParams &p, float *__rest
         const int n_scan = max(0, min(4, p.n - wave * 4));
         const int e_base = wave * 4;
         K1_LITE(3);
-        if (!RV_OWN_TILES) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ray table (own-tiles form: the cast's first use waits for it; the stores need not retire before the window request)
+        // (no wait for the ray table here: the cast's first use waits for it, and the stores need not retire before the window request)
         K1_LITE(4);
-        if (RV_OWN_TILES) {
-            // this wave owns tile 1: envs 1 and 3, staged and cast here, at this wave's own pace (scan_copy_wave: envs 0 and 2 through tile 0).
-            // The windows are the copy wave's: read once its word says they stand (bounded poll: a protocol error ends as a wrong
-            // observation the parity tests catch, not as a hung GPU)
-            PrivateWindows pw;
-            {
-                const float *lk = fused_link(lds, p, wv);
-                for (int spin = 0; spin < (1 << 20); ++spin) {
-                    const float f = *(volatile __attribute__((address_space(3))) float *)(__attribute__((address_space(3))) float *)(const_cast<float *>(lk) + 48 + (lane >> 4) * 4 + 3);
-                    if (__builtin_amdgcn_ballot_w64(f != 3.0f) == 0ull) break;
-                    __builtin_amdgcn_s_sleep(1);
-                }
-            }
-            windows_from_lds(win, pw);
-            K1_LITE(5);
-            K1_STAMP(27);
-            if (n_scan > 1) {
-                private_issue(p, pw, 1, tile1, lane);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                private_cast<FUSE == 2, 0, PRIVATE_ROUNDS>(p, pw, 1, tile1, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's reads of tile 1 have returned: the tile is free
-            }
-            K1_STAMP(28);
-            K1_LITE(6);
-            K1_LITE(7);
-            if (n_scan > 3) {
-                private_issue(p, pw, 3, tile1, lane);
-                K1_LITE(8);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                K1_STAMP(29);
-                K1_LITE(9);
-                private_cast<FUSE == 2, 0, PRIVATE_ROUNDS>(p, pw, 3, tile1, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
-            }
-            K1_STAMP(26);
-            K1_LITE(10);
-            return;
-        }
-        __syncthreads();                                                // B: the copy wave has cast env 0 and requested window 2
-        K1_LITE(5);
-        // (barrier form) the windows of the final poses: written by the copy wave (it owns them), read behind barrier B
+        // this wave owns tile 1: envs 1 and 3, staged and cast here, at this wave's own pace (scan_copy_wave: envs 0 and 2 through tile 0).
+        // The windows are the copy wave's: read once its word says they stand (bounded poll: a protocol error ends as a wrong
+        // observation the parity tests catch, not as a hung GPU)
         PrivateWindows pw;
+        {
+            const float *lk = fused_link(lds, p, wv);
+            for (int spin = 0; spin < (1 << 20); ++spin) {
+                const float f = *(volatile __attribute__((address_space(3))) float *)(__attribute__((address_space(3))) float *)(const_cast<float *>(lk) + 48 + (lane >> 4) * 4 + 3);
+                if (__builtin_amdgcn_ballot_w64(f != 3.0f) == 0ull) break;
+                __builtin_amdgcn_s_sleep(1);
+            }
+        }
         windows_from_lds(win, pw);
+        K1_LITE(5);
         K1_STAMP(27);
-        if (n_scan > 1) private_cast<FUSE == 2, 0, SHARE_1>(p, pw, 1, tile1, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (n_scan > 1) {
+            private_issue(p, pw, 1, tile1, lane);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            private_cast<TRI>(p, pw, 1, tile1, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this wave's reads of tile 1 have returned: the tile is free
+        }
         K1_STAMP(28);
         K1_LITE(6);
-        __syncthreads();                                                // C: window 2 has landed, tile 1 is free
         K1_LITE(7);
-        if (n_scan > 2) private_cast<FUSE == 2, 0, SHARE_2>(p, pw, 2, tile0, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        K1_STAMP(29);
-        K1_LITE(8);
-        __syncthreads();                                                // D: window 3 has landed
-        K1_LITE(9);
-        if (n_scan > 3) private_cast<FUSE == 2, 0, SHARE_3>(p, pw, 3, tile1, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
+        if (n_scan > 3) {
+            private_issue(p, pw, 3, tile1, lane);
+            K1_LITE(8);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            K1_STAMP(29);
+            K1_LITE(9);
+            private_cast<TRI>(p, pw, 3, tile1, lane, e_base, obs, p.obs_w, 4, oxy, ray_xy);
+        }
         K1_STAMP(26);
         K1_LITE(10);
     }
@@ -3047,7 +2840,7 @@ __global__ __launch_bounds__(RV_K1G_THREADS) void rover_step_begin_kernel(RvPara
                                                                           uint8_t *__restrict__ terminated, uint8_t *__restrict__ truncated,
                                                                           float *__restrict__ force)
 {
-    step_group_body<0, true>(p, state, action, nullptr, reward, terminated, truncated, force, nullptr, nullptr, nullptr);
+    step_group_body<TWO_LAUNCH, false, true>(p, state, action, nullptr, reward, terminated, truncated, force, nullptr, nullptr, nullptr);
 }
 __global__ __launch_bounds__(RV_K1G_THREADS) void rover_step_kernel_group(RvParams p, float *__restrict__ state,
                                                               const float *__restrict__ action, float *__restrict__ obs,
@@ -3055,7 +2848,7 @@ __global__ __launch_bounds__(RV_K1G_THREADS) void rover_step_kernel_group(RvPara
                                                               uint8_t *__restrict__ truncated, float *__restrict__ force,
                                                               float *__restrict__ log_partial)
 {
-    step_group_body<0>(p, state, action, obs, reward, terminated, truncated, force, log_partial, nullptr, nullptr);
+    step_group_body<TWO_LAUNCH, false>(p, state, action, obs, reward, terminated, truncated, force, log_partial, nullptr, nullptr);
 }
 // One launch per env step: the group-mapped step with the height scan as its last phase (TRI: triangle-mesh surface).
 template <bool TRI>
@@ -3069,7 +2862,7 @@ __global__ __launch_bounds__(2 * RV_K1G_THREADS) RV_FUSED_ATTR void rover_step_s
     if (wv < RV_K1G_THREADS / 64) {  // waves 0..3: the step (threadIdx.x < 256: the group kernel's own indexing); waves 4..7: their copy waves
         // (s_setprio 3 for the step wave during the physics, so that its copy wave only gets the issue slots it leaves empty: measured,
         // 83.8 k vs 84.0 k stamped cycles -- nothing)
-        step_group_body<TRI ? 2 : 1>(p, state, action, obs, reward, terminated, truncated, force, log_partial, lds, ray_xy);
+        step_group_body<COPY_WAVES, TRI>(p, state, action, obs, reward, terminated, truncated, force, log_partial, lds, ray_xy);
     } else {
         scan_copy_wave<TRI>(p, state, lds, wv - RV_K1G_THREADS / 64, (int)(threadIdx.x & 63), obs, ray_xy);
     }
@@ -3619,7 +3412,7 @@ __global__ __launch_bounds__(RV_K1G_THREADS) RV_FUSED_ATTR void rover_step_scan1
     const float2 *__restrict__ ray_xy)
 {
     extern __shared__ __align__(16) float lds[];
-    step_group_body<TRI ? 4 : 3>(p, state, action, obs, reward, terminated, truncated, force, log_partial, lds, ray_xy);
+    step_group_body<SINGLE_TILE, TRI>(p, state, action, obs, reward, terminated, truncated, force, log_partial, lds, ray_xy);
 }
 // extras["log"] behind the fused step kernel (the scan kernel's workgroup 0 does this on the two-launch path)
 // (1024 threads: the summation order of the scan kernel's reduction, so that both paths produce the same bits)
@@ -3628,31 +3421,6 @@ __global__ __launch_bounds__(1024) void rover_log_kernel(RvParams p, const float
 {
     __shared__ float lds[1024 + 16];
     reduce_log_partials<1024>(p, lds, threadIdx.x, log_partial, n_waves, log_out);
-}
-template <bool TRI>
-__global__ __launch_bounds__(RV_K1G_THREADS) RV_FUSED_ATTR void rover_scan_private_kernel(
-    RvParams p, float *__restrict__ out, int row_stride, int col0, const float *__restrict__ log_partial, int n_waves,
-    float *__restrict__ log_out, const float *__restrict__ scan_desc, const float2 *__restrict__ ray_xy)
-{
-    extern __shared__ __align__(16) float lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int e_base = (blockIdx.x * (RV_K1G_THREADS / 64) + wv) * 4;
-    const int tile_cells = p.tile_dim * p.tile_pitch;
-    int16_t *tile0 = reinterpret_cast<int16_t *>(lds) + (size_t)(2 * wv) * tile_cells, *tile1 = tile0 + tile_cells;
-    const int n_env = max(0, min(4, p.n - e_base));
-    PrivateWindows w;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float4 *d = reinterpret_cast<const float4 *>(scan_desc + (size_t)min(e_base + j, p.n - 1) * 8);
-        const float4 d0 = d[0], d1 = d[1];
-        w.px[j] = d0.x; w.py[j] = d0.y; w.pz[j] = d0.z; w.cy[j] = d0.w; w.sy[j] = d1.x;
-        w.i_lo[j] = __float_as_int(d1.y); w.j_lo[j] = __float_as_int(d1.z); w.pk[j] = __float_as_int(d1.w);
-    }
-    scan_private_wave<TRI>(p, tile0, tile1, lane, n_env, e_base, w, out, row_stride, col0, ray_xy);
-    if (blockIdx.x == 0 && log_out) {   // workgroup 0: extras["log"] of this step (usually one counter read)
-        __syncthreads();     // the tiles are dead: the reduction reuses the LDS
-        reduce_log_partials<RV_K1G_THREADS>(p, lds, tid, log_partial, n_waves, log_out);
-    }
 }
 
 // ================================================================================================ unit kernels
@@ -3747,13 +3515,11 @@ struct rover_sim {
     size_t lds_bytes;
     int n_cu;          // compute units of the device
     int scan_wgs;      // persistent scan workgroups: what the device holds at once
-    int scan_form;     // measurement hook: 1 = the generic scan kernel on the step path too
     bool markers;      // roctx ranges around the launches of rover_step (rover_set_markers)
     uint32_t log_serial; // tag of the log-partial rows of the launch under way
     size_t max_lds;      // LDS a workgroup may allocate on this device (hipDeviceAttributeMaxSharedMemoryPerBlock)
     int fused;           // one launch per step (rover_step_scan_kernel): -1 = decide (group mapping, int16 terrain copy, <= 1024 rays,
                          // the four waves' eight tiles fit the LDS, one workgroup per CU holds the batch), 0 = off, 1 = on where possible
-    bool single_tile_ok; // the single-tile one-launch form may be chosen automatically beyond one round of workgroups (measured: see fused_form)
     bool log_deferred;   // rover_set_log_deferred: rover_step leaves `log` alone, rover_flush_log reduces it on demand
     bool phase_open;     // rover_step_begin has run, rover_step_finish has not
     int launch_error;    // set by launch_step_kernels when a launch could not be made (rover_step returns it)
@@ -3806,10 +3572,10 @@ static ScanForm scan_form_of(const rover_sim *sim, int mode)
     f.tri = sim->p.cfg.scan_surface == 0;
     const int cc = f.q16 ? 8 : 4;
     const uintptr_t base = f.q16 ? reinterpret_cast<uintptr_t>(sim->p.height_q) : reinterpret_cast<uintptr_t>(sim->p.height);
-    f.simple = mode == 2 && (sim->p.W & (cc - 1)) == 0 && (base & 15) == 0 && sim->p.rays <= 1024 && sim->scan_form != 1;
+    f.simple = mode == 2 && (sim->p.W & (cc - 1)) == 0 && (base & 15) == 0 && sim->p.rays <= 1024;
     const size_t tile_bytes = (size_t)sim->p.tile_dim * sim->p.tile_pitch * (f.q16 ? 2 : 4);
-    // two envs per iteration when two workgroups with two tiles each fit the CU's LDS (measurement hook: form 2 = one env)
-    f.epi = (sim->scan_form != 2 && 2 * (192 * sizeof(float) + 2 * tile_bytes) <= sim->max_lds) ? 2 : 1;
+    // two envs per iteration when two workgroups with two tiles each fit the CU's LDS
+    f.epi = 2 * (192 * sizeof(float) + 2 * tile_bytes) <= sim->max_lds ? 2 : 1;
     f.step_lds = 192 * sizeof(float) + f.epi * tile_bytes < (1024 + 16) * sizeof(float) ? (1024 + 16) * sizeof(float)
                                                                                          : 192 * sizeof(float) + f.epi * tile_bytes;
     if (f.simple) {
@@ -3826,7 +3592,7 @@ static size_t fused_lds_bytes(const rover_sim *sim) { return (size_t)(RV_K1G_THR
 // 0 = two launches, 1 = one launch with copy waves (one workgroup per CU), 2 = one launch, one tile per wave (two workgroups per CU)
 static int fused_form(const rover_sim *sim)
 {
-    if (sim->fused == 0 || !sim->group_mapping || sim->scan_form != 0) return 0;
+    if (sim->fused == 0 || !sim->group_mapping) return 0;
     const ScanForm f = scan_form_of(sim, 2);
     if (!f.simple || !f.q16 || sim->p.rays > 1024) return 0;
     if (sim->p.tile_pitch / 8 > 64) return 0;   // private_issue stages whole rows per instruction: a row must fit a wave's 64 lanes
@@ -3842,15 +3608,13 @@ static int fused_form(const rover_sim *sim)
     if (fits1 && sim->step_blocks <= sim->n_cu) return 2 * sim->step_blocks >= sim->n_cu ? 1 : 0;
     // More than one round of workgroups: the single-tile form keeps the two-launch path's two workgroups per CU (N sweep, us per
     // step, one launch / two: 8192 envs 62.7 / 70.4, 16384 envs 112.0 / 125.6, 32768 envs 197.6 / 228.6).
-    return (sim->single_tile_ok && fits2) ? 2 : 0;
+    return fits2 ? 2 : 0;
 }
-static bool fused_step(const rover_sim *sim) { return fused_form(sim) != 0; }
 // The automatic mapping (cfg.step_mapping = 0) is sixteen lanes per env at every batch size: as one launch wherever the terrain /
 // pattern allow it (fused_form), else as the two launches of the group mapping.  One env per lane (cfg.step_mapping = 1) is faster
 // than those two launches from ~65536 envs on (tools/n_sweep.py: 164 against 131 M env-steps/s at 65536 envs; slower at 32768:
 // 116 against 142 M) but its kernels carry 728 - 984 bytes of scratch per lane: an explicit choice, never the automatic one.
 // Both mappings produce the same bits from the same state layout.
-static void refresh_mapping(rover_sim *) {}
 // the kernel launches of one env step (rover_step / rover_profile_step); ev: optional event recorded between the two launches
 static void launch_step_kernels(rover_sim *sim, hipStream_t st, const float *action, float *obs, float *reward, uint8_t *terminated,
                                 uint8_t *truncated, float *force, float *log, hipEvent_t mid);
@@ -3864,24 +3628,6 @@ static void launch_scan(rover_sim *sim, int grid, hipStream_t st, float *out, in
     const bool q16 = f.q16, tri = f.tri, simple = f.simple;
     const int epi = f.epi;
     const size_t step_lds = f.step_lds;
-    if (MODE == 2 && sim->scan_form == 7 && simple && q16) {   // measurement hook: the wave-private form as a kernel of its own
-        const size_t tile_bytes = (size_t)sim->p.tile_dim * sim->p.tile_pitch * 2;
-        size_t lds = (RV_K1G_THREADS / 64) * 2 * tile_bytes;
-        if (lds < (RV_K1G_THREADS + 16) * sizeof(float)) lds = (RV_K1G_THREADS + 16) * sizeof(float);
-        if (lds <= sim->max_lds) {
-            const int blocks = (sim->p.n + RV_K1G_ENVS - 1) / RV_K1G_ENVS;
-            if (tri) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&rover_scan_private_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL((rover_scan_private_kernel<true>), dim3(blocks), dim3(RV_K1G_THREADS), lds, st, sim->p, out, row_stride, col0,
-                                   log_partial, n_waves, log_out, sim->p.scan_desc, sim->ray_xy);
-            } else {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&rover_scan_private_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL((rover_scan_private_kernel<false>), dim3(blocks), dim3(RV_K1G_THREADS), lds, st, sim->p, out, row_stride, col0,
-                                   log_partial, n_waves, log_out, sim->p.scan_desc, sim->ray_xy);
-            }
-            return;
-        }
-    }
 #define RV_LAUNCH_STEP(Q, T, E)                                                                                               \
     hipLaunchKernelGGL((rover_scan_step_kernel<Q, T, 1024, E>), dim3(grid), dim3(1024), step_lds, st, sim->p, out, row_stride, \
                        col0, log_partial, n_waves, log_out, sim->p.scan_desc)
@@ -3961,7 +3707,6 @@ static bool raise_dynamic_lds(rover_sim *sim, int form, size_t lds)
 static void launch_step_kernels(rover_sim *sim, hipStream_t st, const float *action, float *obs, float *reward, uint8_t *terminated,
                                 uint8_t *truncated, float *force, float *log, hipEvent_t mid)
 {
-    refresh_mapping(sim);
     const RvParams &p = sim->p;
     const int form = fused_form(sim);
     if (form == 2) {
@@ -4084,7 +3829,7 @@ int rover_create(const rover_config *cfg, int32_t num_envs, int32_t env_id_offse
     }
     if (cfg->step_mapping < 0 || cfg->step_mapping > 2) { delete s; return fail(ROVER_ERR_INVALID, "step_mapping must be 0, 1 or 2"); }
     // latency mapping (16 lanes per env) while one-env-per-lane would leave most SIMDs without a wave
-    s->group_mapping = cfg->step_mapping != 1;   // one env per lane only on request (its kernels spill: see refresh_mapping)
+    s->group_mapping = cfg->step_mapping != 1;   // one env per lane only on request (its kernels spill: see launch_step_kernels)
     // log-partial rows = waves launched (the group mapping launches whole 256-thread workgroups)
     s->step_blocks = s->group_mapping ? (num_envs + RV_K1G_ENVS - 1) / RV_K1G_ENVS : (num_envs + 63) / 64;
     s->n_waves = s->group_mapping ? s->step_blocks * (RV_K1G_THREADS / 64) : s->step_blocks;
@@ -4095,7 +3840,6 @@ int rover_create(const rover_config *cfg, int32_t num_envs, int32_t env_id_offse
     s->ws_bytes = (((s->ws_log_floats + (size_t)num_envs * 8) * sizeof(float) + 127) & ~(size_t)127) + 1024 * sizeof(float2) + 128;
     s->ray_xy = nullptr;
     s->fused = -1;
-    s->single_tile_ok = true;
     s->log_deferred = false;
     *out = s;
     return ROVER_OK;
@@ -4384,18 +4128,15 @@ int rover_kernel_names(const rover_sim *sim, char *step_kernel, char *scan_kerne
     // and of profiles/hbm_traffic.json.
     if (!sim || !step_kernel || !scan_kernel || cap < 8) return fail(ROVER_ERR_INVALID, "bad argument");
     if (!sim->have_terrain) return fail(ROVER_ERR_STATE, "rover_set_terrain has not been called");
-    refresh_mapping(const_cast<rover_sim *>(sim));
-    if (fused_step(sim)) {   // one launch: the scan is the last phase of the step kernel; the second name is the log reduction's
-        snprintf(step_kernel, cap, "%s<%s>", fused_form(sim) == 2 ? "rover_step_scan1_kernel" : "rover_step_scan_kernel",
+    if (const int form = fused_form(sim)) {   // one launch: the scan is the last phase of the step kernel; the second name is the log reduction's
+        snprintf(step_kernel, cap, "%s<%s>", form == 2 ? "rover_step_scan1_kernel" : "rover_step_scan_kernel",
                  sim->p.cfg.scan_surface == 0 ? "true" : "false");
         snprintf(scan_kernel, cap, "%s", sim->log_deferred ? "" : "rover_log_kernel");
         return ROVER_OK;
     }
     snprintf(step_kernel, cap, "%s", sim->group_mapping ? "rover_step_kernel_group" : "rover_step_kernel");
     const ScanForm f = scan_form_of(sim, 2);
-    if (sim->scan_form == 7 && f.simple && f.q16)   // measurement hook: the wave-private scan as a kernel of its own
-        snprintf(scan_kernel, cap, "rover_scan_private_kernel<%s>", f.tri ? "true" : "false");
-    else if (f.simple)
+    if (f.simple)
         snprintf(scan_kernel, cap, "rover_scan_step_kernel<%s, %s, 1024, %d>", f.q16 ? "true" : "false", f.tri ? "true" : "false", f.epi);
     else
         snprintf(scan_kernel, cap, "rover_scan_obs_kernel<2, %s, %s>", f.q16 ? "true" : "false", f.tri ? "true" : "false");
@@ -4492,16 +4233,6 @@ int rover_height_scan(rover_sim *sim, float *scan, void *stream)
     return ROVER_OK;
 }
 
-// measurement hook (tools/n_sweep.py): 0 = automatic choice, 1 = the generic scan kernel on the step path as well, 2 = the
-// step form with one env per iteration, 7 = the wave-private scan (the scan phase of the one-launch kernels) as a kernel of its
-// own behind the group-mapped step kernel.  (Forms 3 .. 6 -- 8 x 8 ray blocks per wave, XCD-aware pair dealing off / on -- were
-// round-3 experiments; their outcome is in docs/history.md section 10, their code is gone.)
-int rover_debug_set_scan_form(rover_sim *sim, int form)
-{
-    if (!sim || !(form == 0 || form == 1 || form == 2 || form == 7)) return ROVER_ERR_INVALID;
-    sim->scan_form = form;
-    return ROVER_OK;
-}
 // measurement hook: -1 = automatic, 0 = two launches per step, 1 / 2 = one launch (copy-wave form / single-tile form) wherever it can run
 int rover_debug_set_fused(rover_sim *sim, int fused)
 {

@@ -37,7 +37,7 @@ def test_library_exports_every_declared_symbol():
     # hooks of include/rover_debug.h (marked test-only there)
     import subprocess
     debug = declared_symbols(debug=True)
-    assert debug == ["rover_debug_set_fused", "rover_debug_set_scan_form", "rover_lift_debug_set_lanes", "rover_lift_debug_set_pipeline"]
+    assert debug == ["rover_debug_set_fused", "rover_lift_debug_set_lanes", "rover_lift_debug_set_pipeline"]
     for n in debug:
         assert hasattr(lib, n), f"{n} declared in include/{DEBUG_HEADER} but not exported"
     nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout

@@ -492,32 +492,15 @@ def test_scan_step_kernel_forms(oracle, quantize, res, grid_m, n):
     env.close()
 
 
-def test_private_scan_kernel_measurement_form(oracle):
-    """rover_debug_set_scan_form(sim, 7): the wave-private scan (the scan phase of the one-launch kernels) as a kernel of its own
-    behind the group-mapped step kernel -- a measurement form, kept honest: closed loop against the oracle, ragged batch."""
-    import ctypes as C
-    ter = small_procedural()
-    n = 203
-    env = make_env(n, ter, seed=8, step_mapping="group2")
-    fn = C.CDLL(env._lib._name).rover_debug_set_scan_form
-    fn.argtypes = [C.c_void_p, C.c_int]
-    assert fn(env._h, 7) == 0
-    assert env.kernel_names()[1].startswith("rover_scan_private_kernel"), env.kernel_names()   # the form IS selected (it silently was not, round 3)
-    rng = np.random.RandomState(4)
-    actions = rng.uniform(-1, 1, (10, n, 2)).astype(np.float32)
-    assert rollout_compare(oracle, env, 10, actions, 0.0, 0.0, resync=False) == 0
-    env.close()
-
-
-@pytest.mark.parametrize("form,scan", [("group", (0.1, 3.0, 3.0)), ("group", (0.1, 4.0, 1.0)), ("group", (0.2, 1.2, 5.0)), ("group2", (0.1, 3.0, 3.0))])
+@pytest.mark.parametrize("form,scan", [("group", (0.1, 3.0, 3.0)), ("group", (0.1, 4.0, 1.0)), ("group", (0.2, 1.2, 5.0)), ("group1", (0.1, 3.0, 3.0))])
 def test_window_spans_cover_every_yaw(oracle, form, scan):
-    """Round 5: the window copy of the wave-private scan requests, per chunk column, only the rows the yaw-rotated pattern can
-    touch (rover_kernels.hip: private_issue).  A chunk dropped wrongly leaves stale LDS under a ray -- on rough terrain that is
-    a wrong scan value.  Poses at sub-cell offsets, headings at and around every degenerate direction (axis-aligned: one edge
-    pair of the rectangle is dropped below |sin|, |cos| = 1e-3; diagonal), a sweep, and a random rest; square and elongated
-    patterns; one step with zero action, observation bit-exact against the oracle.  "group2" + form 7 = the same copy in the
-    stand-alone scan kernel."""
-    import ctypes as C
+    """The window copy of the wave-private scan (rover_kernels.hip: private_issue) stages the bounding box of the yaw-rotated
+    pattern, whole rows per instruction.  A cell a ray reads outside the staged rows leaves stale LDS under that ray -- on rough
+    terrain that is a wrong scan value.  Poses at sub-cell offsets, headings at and around every degenerate direction
+    (axis-aligned and diagonal, 1e-3 either side), a sweep, and a random rest; square and elongated patterns; one step with zero
+    action, observation bit-exact against the oracle.  "group" = the copy-wave one-launch form where its eight tiles fit the
+    LDS (the 1.2 x 5 m pattern's do not: that case runs as two launches), "group1" = the single-tile one-launch form (the
+    product form beyond one round of workgroups): the same private_issue."""
     from isaac_rover_orbit_amd import terrain as T
     ter = T.make_procedural_terrain((1024, 1024), seed=13, sigma_z=0.5, n_rocks=200)
     n = 1024
@@ -528,14 +511,10 @@ def test_window_spans_cover_every_yaw(oracle, form, scan):
     cfg.scene.num_envs, cfg.terrain.kind, cfg.seed = n, "custom", 3
     cfg.height_scanner.resolution, cfg.height_scanner.size = res, (sx, sy)
     cfg.step_mapping = "group"
-    if form == "group2":
-        cfg.log_reduction = "every_step"
     env = RoverEnv(cfg, terrain=ter)
-    if form == "group2":
-        _set_fused(env, 0)
-        fn = C.CDLL(env._lib._name).rover_debug_set_scan_form
-        fn.argtypes = [C.c_void_p, C.c_int]
-        assert fn(env._h, 7) == 0
+    if form == "group1":
+        _set_fused(env, 2)
+        assert env.kernel_names()[0].startswith("rover_step_scan1_kernel<"), env.kernel_names()   # the form IS selected
     else:
         _set_fused(env, 1)
     env.reset()
@@ -561,7 +540,7 @@ def test_window_spans_cover_every_yaw(oracle, form, scan):
         obs, rew, term, trunc, info = env.step(torch.from_numpy(a).to(env.device))
         obs_o, rew_o, term_o, trunc_o, force_o, log_o = oracle.step(ocfg, oter, Sw, a)
         assert np.array_equal(term.cpu().numpy().astype(np.uint8), term_o)
-        assert_close(obs["policy"].cpu().numpy(), obs_o, 0, 0, "observation (scan through the span-limited window copy)")
+        assert_close(obs["policy"].cpu().numpy(), obs_o, 0, 0, "observation (scan through the wave-private window copy)")
     assert_close(state_np(env), Sw, 0, 0, "state")
     env.close()
 

@@ -23,17 +23,11 @@ VARIANTS = {"K1STAMP": ("rover_kernels.hip", "-DRV_K1_STAMP"),            # s_me
             "LIFTSTAMP": ("lift_kernels.hip", "-DLF_STAMP"),               # ... in the lift step kernel (tools/lift_stamps.py)
             "POLSTAMP": ("policy_kernels.hip", "-DPOL_STAMP"),             # ... in the policy kernels (tools/policy_stamps.py [pair])
             "NOSLP": ("rover_kernels.hip", "-fno-slp-vectorize"),
-            # the window copy limited to the rows each chunk column needs (bit-exact; fewer bytes, more instructions: measured slower)
-            "SPANS": ("rover_kernels.hip", "-DRV_ROW_SPANS"),
-            "BARRIERS": ("rover_kernels.hip", "-DRV_OWN_TILES=0"),        # the one-launch kernel's scan phase in its barrier form (B, C, D: rounds 4 - 5)
             # whole-file code generation switches tried on top of the product flags (profiles/r05_sched_strategy.txt; the strategy itself,
             # -amdgpu-sched-strategy=max-ilp, is a product flag since: isaac_rover_orbit_amd/build.py)
             "F_IFCVT": ("rover_kernels.hip", "-mllvm -amdgpu-early-ifcvt=1"), "F_NOLICM": ("rover_kernels.hip", "-mllvm -disable-machine-licm"),
             "F_PRELOAD": ("rover_kernels.hip", "-mllvm -amdgpu-kernarg-preload-count=16"),
             "UNROLL4": ("rover_kernels.hip", "-DRV_SOLVER_UNROLL=4"), "UNROLL2": ("rover_kernels.hip", "-DRV_SOLVER_UNROLL=2"),   # solver iterations per loop trip (default 8)
-            # rounds (whole quads) of envs 1 / 2 / 3 cast by the step wave, the rest by its copy wave (tools/quick_bench.py)
-            **{f"SH_{a}_{b_}_{c}": ("rover_kernels.hip", f"-DRV_SHARE_1={a} -DRV_SHARE_2={b_} -DRV_SHARE_3={c}")
-               for (a, b_, c) in ((12, 16, 12), (12, 16, 16), (8, 16, 12), (12, 16, 8), (8, 16, 8), (16, 16, 12), (12, 12, 12))},
             # policy pair kernel: round 3's sequential form; queue depths of the weight fragments
             # timing experiment (WRONG results): the pair kernel's layer 1 does not wait for the observation tile -- the upper bound of what
             # starting layer 1 on the landed part of the tile could gain
@@ -41,8 +35,10 @@ VARIANTS = {"K1STAMP": ("rover_kernels.hip", "-DRV_K1_STAMP"),            # s_me
             "P_SEQ": ("policy_kernels.hip", "-DPOL_PAIR_SEQUENTIAL"), "P_QD1_3": ("policy_kernels.hip", "-DPOL_STAMP -DPOL_QD1=3"),
             "P_QD4_8": ("policy_kernels.hip", "-DPOL_STAMP -DPOL_QD4=8 -DPOL_QD5=10")}
 # (The round-2 / round-3 timing builds of the two-launch scan kernel -- RV_K2_EMPTY / PROLOGUE_ONLY / NO_COPY / NO_RAYS / STORE4 /
-# NT_STORE / NOREDUCE / STAMP --, RV_K1_NOTERRAIN / CONSTS_IN_KERNEL and round 4's RV_X_NOLDS / NOSTORE / NOLINK / NODRAW have been
-# removed from the sources together with their variants here: what they measured is recorded in docs/history.md sections 3.3 - 3.7 and 10.)
+# NT_STORE / NOREDUCE / STAMP --, RV_K1_NOTERRAIN / CONSTS_IN_KERNEL, round 4's RV_X_NOLDS / NOSTORE / NOLINK / NODRAW and round 5's
+# SPANS (per-row window spans), BARRIERS (the barrier form of the one-launch scan phase) and SH_* (that form's split of envs 1 - 3
+# between the two waves) have been removed from the sources together with their variants here:
+# what they measured is recorded in docs/history.md sections 3.3 - 3.7, 10 and 14.)
 
 
 def main():

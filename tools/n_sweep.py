@@ -19,12 +19,11 @@ CASES = [(1024, "auto"), (1024, "group1"), (2048, "auto"), (2048, "group2"), (40
          (4096, "lane"), (8192, "auto"), (8192, "groupf"), (8192, "group2"), (16384, "auto"), (16384, "group2"), (32768, "auto"),
          (32768, "group2"), (32768, "lane"), (65536, "auto"), (65536, "group2"), (65536, "lane"), (131072, "auto"), (131072, "group2"),
          (131072, "lane")]
-if len(sys.argv) > 1:   # e.g. 1024:group 2048:group:wave  (third field: scan kernel of the step path, auto | generic | epi1)
+if len(sys.argv) > 1:   # e.g. 1024:group1 2048:group2
     CASES = [tuple(a.split(":")) for a in sys.argv[1:]]
 import ctypes as C
-FORMS = {"auto": 0, "generic": 1, "epi1": 2}
 for case in CASES:
-    n, mapping, form = int(case[0]), case[1], (case[2] if len(case) > 2 else "auto")
+    n, mapping = int(case[0]), case[1]
     ter.make_spawns(2 * n)
     cfg = RoverEnvCfg(); cfg.scene.num_envs = n; cfg.terrain.kind = "custom"; cfg.step_mapping = "group" if mapping.startswith("group") else mapping   # "auto" = the product's own choice
     if mapping == "group2":
@@ -33,9 +32,6 @@ for case in CASES:
     if mapping in ("groupf", "group1", "group2"):      # forced: one launch, copy-wave form / single-tile form; two launches
         ff = C.CDLL(env._lib._name).rover_debug_set_fused; ff.argtypes = [C.c_void_p, C.c_int]
         assert ff(env._h, {"groupf": 1, "group1": 2, "group2": 0}[mapping]) == 0
-    fn = C.CDLL(env._lib._name).rover_debug_set_scan_form
-    fn.argtypes = [C.c_void_p, C.c_int]
-    assert fn(env._h, FORMS[form]) == 0
     env.reset()
     g = torch.Generator(device="cuda").manual_seed(0)
     acts = torch.rand(16, n, 2, device="cuda", generator=g) * 2 - 1
@@ -50,7 +46,7 @@ for case in CASES:
     a = b = 0.0
     for k in range(20):
         x, y = env.profile_step(acts[k % 16]); a += x; b += y
-    r = {"num_envs": n, "mapping": mapping, "kernels": list(env.kernel_names()), "scan_form": form, "env_steps_per_s": n * steps / dt, "us_per_step": dt / steps * 1e6,
+    r = {"num_envs": n, "mapping": mapping, "kernels": list(env.kernel_names()), "env_steps_per_s": n * steps / dt, "us_per_step": dt / steps * 1e6,
          "step_kernel_us": a / 20 * 1e3, "scan_kernel_us": b / 20 * 1e3}
     print(json.dumps(r)); out.append(r)
     env.close(); del env; torch.cuda.empty_cache()

@@ -18,10 +18,6 @@ if os.environ.get("QB_ITERS"): cfg.solver_iterations = int(os.environ["QB_ITERS"
 if os.environ.get("QB_MASS"): cfg.mass_model = os.environ["QB_MASS"]
 cfg.roctx_markers = len(sys.argv) > 3 and sys.argv[3] == "markers"     # rocprofv3 --marker-trace: one range per env step
 env = RoverEnv(cfg, terrain=ter)
-if os.environ.get("ROVER_SCAN_FORM"):   # 3 = 8 x 8 ray blocks per wave, 4 = lines (rover_debug_set_scan_form)
-    import ctypes as C
-    fn = C.CDLL(env._lib._name).rover_debug_set_scan_form; fn.argtypes = [C.c_void_p, C.c_int]
-    assert fn(env._h, int(os.environ["ROVER_SCAN_FORM"])) == 0
 def cluster_by_xcd(env, n):
     """QB_CLUSTER=1 (experiment): permute the envs' states after the reset so that the envs of the workgroups one XCD runs (workgroup
     b = envs 16 b .. 16 b + 15 runs on XCD b mod 8) stand in one x-strip of the terrain -- what the L2 fetch would be if env -> XCD
