@@ -34,6 +34,8 @@ EXPORTS = [
     "rover_lift_set_log_deferred", "rover_lift_flush_log",
     "rover_camera_default_config", "rover_camera_config_bytes", "rover_camera_workspace_bytes", "rover_camera_prepare",  # rover_camera.h
     "rover_camera_render",
+    "rover_viewer_default_config", "rover_viewer_config_bytes", "rover_viewer_workspace_bytes", "rover_viewer_prepare",  # rover_viewer.h
+    "rover_viewer_render",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH = 0, 1, 2
@@ -103,6 +105,17 @@ class CameraConfig(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("focal_length", C.c_float), ("horizontal_aperture", C.c_float),
                 ("vertical_aperture", C.c_float), ("mount_pos", C.c_float * 3), ("mount_quat", C.c_float * 4),
                 ("near_clip", C.c_float), ("far_clip", C.c_float)]
+
+
+VIEWER_ORIGIN_WORLD, VIEWER_ORIGIN_ENV = 0, 1
+VIEWER_MAX_SIZE = 8192
+
+
+class ViewerConfig(C.Structure):
+    """Mirror of ``struct rover_viewer_config`` (include/rover_viewer.h)."""
+    _fields_ = [("eye", C.c_float * 3), ("lookat", C.c_float * 3), ("origin_type", C.c_int32), ("env_index", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("focal_length", C.c_float), ("horizontal_aperture", C.c_float),
+                ("near_clip", C.c_float), ("far_clip", C.c_float), ("draw_targets", C.c_int32)]
 
 
 _lib = None
@@ -201,6 +214,12 @@ def load():
     lib.rover_camera_workspace_bytes.restype = C.c_size_t
     lib.rover_camera_prepare.argtypes = [vp, C.POINTER(CameraConfig), vp, C.c_size_t, vp]
     lib.rover_camera_render.argtypes = [vp, C.POINTER(CameraConfig), vp, vp, vp]
+    lib.rover_viewer_default_config.argtypes = [C.POINTER(ViewerConfig)]
+    lib.rover_viewer_config_bytes.restype = C.c_size_t
+    lib.rover_viewer_workspace_bytes.argtypes = [vp, C.POINTER(ViewerConfig)]
+    lib.rover_viewer_workspace_bytes.restype = C.c_size_t
+    lib.rover_viewer_prepare.argtypes = [vp, C.POINTER(ViewerConfig), vp, C.c_size_t, vp]
+    lib.rover_viewer_render.argtypes = [vp, C.POINTER(ViewerConfig), vp, vp, vp, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -214,6 +233,8 @@ def load():
         raise RoverHipError("struct lift_config / lift state layout of librover_hip.so does not match the Python mirror")
     if lib.rover_camera_config_bytes() != C.sizeof(CameraConfig):
         raise RoverHipError("struct rover_camera_config of librover_hip.so does not match the Python mirror")
+    if lib.rover_viewer_config_bytes() != C.sizeof(ViewerConfig):
+        raise RoverHipError("struct rover_viewer_config of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib
@@ -229,6 +250,12 @@ def check(rc: int, what: str):
 def default_camera_config() -> CameraConfig:
     cfg = CameraConfig()
     check(load().rover_camera_default_config(C.byref(cfg)), "rover_camera_default_config")
+    return cfg
+
+
+def default_viewer_config() -> ViewerConfig:
+    cfg = ViewerConfig()
+    check(load().rover_viewer_default_config(C.byref(cfg)), "rover_viewer_default_config")
     return cfg
 
 

@@ -168,6 +168,60 @@ class CameraCfg:
         return c
 
 
+@dataclass
+class ViewerCfg:
+    """The rgb_array viewer (``RoverEnv(render_mode="rgb_array").render()``): ORBIT's ``ViewerCfg`` (eye, lookat, resolution,
+    origin) with the lens of Kit's default perspective camera; the image contract is DESIGN.md section 11 (include/rover_viewer.h)."""
+    eye: tuple = (7.5, 7.5, 7.5)                       # m (ORBIT ViewerCfg)
+    lookat: tuple = (0.0, 0.0, 0.0)
+    resolution: tuple = (1280, 720)                    # (width, height) pixels
+    origin_type: str = "world"                         # "world" | "env": eye and lookat relative to env `env_index`'s root position
+    env_index: int = 0
+    # Kit's default /OmniverseKit_Persp camera, which ORBIT's viewport renders from (an assumption: the values of that prim as Kit
+    # creates it, not in the reference checkout): horizontal FOV 2 atan(20.955 / (2 x 18.147562)) = 60.0 deg, square pixels
+    focal_length: float = 18.147562                    # mm
+    horizontal_aperture: float = 20.955                # mm
+    near_clip: float = 0.01                            # m
+    far_clip: float = 1000000.0                        # m; may be inf
+    draw_targets: bool = True                          # one sphere per env at its target (the command term's debug_vis=True)
+
+    def validate(self, num_envs: int | None = None):
+        """The checks of the library's config_ok (viewer_kernels.hip), on the values as the fp32 struct holds them; the env index
+        is checked against ``num_envs`` when it is given."""
+        f32 = lambda x: C.c_float(float(x)).value      # noqa: E731
+        if len(self.eye) != 3 or len(self.lookat) != 3:
+            raise ValueError("viewer eye and lookat must be (x, y, z)")
+        eye, at = [f32(v) for v in self.eye], [f32(v) for v in self.lookat]
+        if not all(math.isfinite(v) for v in eye + at):
+            raise ValueError("viewer eye and lookat must be finite")
+        if at[0] - eye[0] == 0.0 and at[1] - eye[1] == 0.0:
+            raise ValueError("viewer lookat - eye must have a horizontal component (eye == lookat, or a view along the Z axis)")
+        if len(self.resolution) != 2 or not all(1 <= int(x) <= _lib.VIEWER_MAX_SIZE for x in self.resolution):
+            raise ValueError(f"viewer resolution must be (width, height), each in 1 .. {_lib.VIEWER_MAX_SIZE}")
+        if not (math.isfinite(f32(self.focal_length)) and math.isfinite(f32(self.horizontal_aperture)) and
+                f32(self.focal_length) > 0 and f32(self.horizontal_aperture) > 0):
+            raise ValueError("viewer focal_length and horizontal_aperture must be positive and finite")
+        if not (0 <= f32(self.near_clip) < f32(self.far_clip)):
+            raise ValueError("viewer clipping range must satisfy 0 <= near_clip < far_clip (far_clip may be inf)")
+        if self.origin_type not in ("world", "env"):
+            raise ValueError("viewer origin_type must be 'world' or 'env'")
+        if self.origin_type == "env" and (int(self.env_index) < 0 or (num_envs is not None and int(self.env_index) >= num_envs)):
+            raise ValueError(f"viewer env_index {self.env_index} is out of range for {num_envs} envs")
+
+    def to_native(self, num_envs: int | None = None) -> "_lib.ViewerConfig":
+        self.validate(num_envs)
+        c = _lib.ViewerConfig()
+        for i in range(3):
+            c.eye[i], c.lookat[i] = self.eye[i], self.lookat[i]
+        c.origin_type = _lib.VIEWER_ORIGIN_ENV if self.origin_type == "env" else _lib.VIEWER_ORIGIN_WORLD
+        c.env_index = int(self.env_index)
+        c.width, c.height = int(self.resolution[0]), int(self.resolution[1])
+        c.focal_length, c.horizontal_aperture = self.focal_length, self.horizontal_aperture
+        c.near_clip, c.far_clip = self.near_clip, self.far_clip
+        c.draw_targets = int(bool(self.draw_targets))
+        return c
+
+
 def _default_observations():
     return {
         "actions": TermCfg("last_action"),
@@ -250,6 +304,8 @@ class RoverEnvCfg:
     global_num_envs: int | None = None
     # the on-board depth camera (RoverEnvCamera): None = no camera, nothing rendered
     camera: CameraCfg | None = None
+    # the rgb_array viewer's camera (render_mode="rgb_array"): ORBIT's ViewerCfg defaults
+    viewer: ViewerCfg = field(default_factory=ViewerCfg)
 
     # ------------------------------------------------------------------------------------------------------------
     def custom_terms(self, table: dict, order: list) -> dict:
@@ -290,6 +346,7 @@ class RoverEnvCfg:
             raise ValueError("simple_heading=True is not supported (the reference cfg uses False, rover_env_cfg.py:195)")
         if self.camera is not None:
             self.camera.validate()
+        self.viewer.validate(self.scene.num_envs)
 
     def observation_post(self) -> dict:
         """Observation terms whose ORBIT post-processing (ObservationManager.compute_group: noise, then clip, then scale) is not
@@ -356,7 +413,9 @@ class RoverEnvCfg:
 
 @dataclass
 class AAURoverEnvCfg(RoverEnvCfg):
-    """``AAURoverEnv-v0`` (robots/aau_rover/env_cfg.py:10-31): the defaults above already are the AAU values."""
+    """``AAURoverEnv-v0`` (robots/aau_rover/env_cfg.py:10-31): the defaults above already are the AAU values, and the viewer's eye
+    is the one rover_env_cfg.py:272 sets."""
+    viewer: ViewerCfg = field(default_factory=lambda: ViewerCfg(eye=(-6.0, -6.0, 3.5)))
 
 
 @dataclass

@@ -28,8 +28,110 @@ class _Spec:
         self.id, self.entry_point, self.kwargs = id, entry_point, dict(kwargs or {})
 
 
+def _capped_cubic_video_schedule(episode_id: int) -> bool:
+    """gymnasium's default episode trigger: episodes 0, 1, 8, 27, ... up to 1000, then every 1000th."""
+    if episode_id < 1000:
+        return int(round(episode_id ** (1.0 / 3))) ** 3 == episode_id
+    return episode_id % 1000 == 0
+
+
+def _episode_ended(terminated, truncated) -> bool:
+    """Whether the (first) episode ended in this step: a batched env's flags are tensors / arrays, env 0's episode counts."""
+    def first(x):
+        if hasattr(x, "reshape"):
+            x = x.reshape(-1)
+            return bool(x[0]) if len(x) else False
+        return bool(x)
+    return first(terminated) or first(truncated)
+
+
+class _RecordVideo:
+    """``gymnasium.wrappers.RecordVideo`` for the minimal registry (no gymnasium, no video encoder installed): the reference's
+    ``video_record()`` (examples/02_train/train.py:73-97) wraps the env in it when ``--video`` is given.
+
+    When a trigger fires (``step_trigger(global step)`` or ``episode_trigger(episode)``; gymnasium's capped cubic episode schedule when
+    neither is given) it collects ``env.render()`` frames -- the frame of the state at the trigger, then one per step -- until it holds
+    ``video_length`` of them (0: until the episode ends), and writes them to ``{video_folder}/{name_prefix}-step-{k}.npz`` (or
+    ``-episode-{k}``) as ``frames`` (T, H, W, 3) uint8.  Every other attribute, and ``unwrapped``, is the env's."""
+
+    def __init__(self, env, video_folder, episode_trigger=None, step_trigger=None, video_length=0, name_prefix="rl-video", **_):
+        import os
+        if getattr(env, "render_mode", None) != "rgb_array":
+            raise ValueError(f"RecordVideo needs an env with render_mode='rgb_array' (got {getattr(env, 'render_mode', None)!r})")
+        if episode_trigger is None and step_trigger is None:
+            episode_trigger = _capped_cubic_video_schedule
+        self.env = env
+        self.video_folder = os.path.abspath(video_folder)
+        os.makedirs(self.video_folder, exist_ok=True)
+        self.episode_trigger, self.step_trigger = episode_trigger, step_trigger
+        self.video_length, self.name_prefix = int(video_length), name_prefix
+        self.step_id = self.episode_id = 0
+        self.recording, self.frames, self.video_name = False, [], None
+        self.written = []                                  # paths of the npz files written so far
+
+    def __getattr__(self, name):
+        if name.startswith("__") or name == "env":
+            raise AttributeError(name)
+        return getattr(self.env, name)
+
+    @property
+    def unwrapped(self):
+        return self.env.unwrapped
+
+    def _triggered(self) -> bool:
+        if self.step_trigger is not None:
+            return bool(self.step_trigger(self.step_id))
+        return bool(self.episode_trigger(self.episode_id))
+
+    def _start(self):
+        self.recording, self.frames = True, []
+        self.video_name = (f"{self.name_prefix}-step-{self.step_id}" if self.step_trigger is not None
+                           else f"{self.name_prefix}-episode-{self.episode_id}")
+        self._capture()
+
+    def _capture(self):
+        import numpy as np
+        self.frames.append(np.ascontiguousarray(self.env.render(), dtype=np.uint8))
+        if self.video_length > 0 and len(self.frames) >= self.video_length:
+            self._write()
+
+    def _write(self):
+        import os
+        import numpy as np
+        if self.recording and self.frames:
+            path = os.path.join(self.video_folder, self.video_name + ".npz")
+            np.savez(path, frames=np.stack(self.frames))
+            self.written.append(path)
+        self.recording, self.frames = False, []
+
+    def reset(self, **kwargs):
+        out = self.env.reset(**kwargs)
+        if not self.recording and self._triggered():
+            self._start()
+        return out
+
+    def step(self, action):
+        out = self.env.step(action)
+        self.step_id += 1
+        ended = _episode_ended(out[2], out[3])
+        if ended:
+            self.episode_id += 1
+        if self.recording:
+            self._capture()
+            if self.recording and self.video_length == 0 and ended:
+                self._write()
+        elif self._triggered():
+            self._start()
+        return out
+
+    def close(self):
+        self._write()
+        return self.env.close()
+
+
 class _MiniGym(types.ModuleType):
-    """The three calls the reference makes on ``gymnasium``: register / make / spec (+ spaces.Box)."""
+    """The three calls the reference makes on ``gymnasium``: register / make / spec (+ spaces.Box), and
+    ``wrappers.RecordVideo`` for its ``--video`` flag."""
 
     def __init__(self, name="gymnasium"):
         super().__init__(name)
@@ -42,6 +144,8 @@ class _MiniGym(types.ModuleType):
         self.spaces.box = types.ModuleType(name + ".spaces.box")
         self.spaces.box.Box = _spaces.Box
         self.Env = object
+        self.wrappers = types.ModuleType(name + ".wrappers")
+        self.wrappers.RecordVideo = _RecordVideo
         self.__path__ = []
 
     def register(self, id, entry_point=None, disable_env_checker=True, kwargs=None, **_):
@@ -76,6 +180,7 @@ def gym_api():
             sys.modules.setdefault("gymnasium", _gym)
             sys.modules.setdefault("gymnasium.spaces", _gym.spaces)
             sys.modules.setdefault("gymnasium.spaces.box", _gym.spaces.box)
+            sys.modules.setdefault("gymnasium.wrappers", _gym.wrappers)
     return _gym
 
 

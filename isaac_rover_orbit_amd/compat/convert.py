@@ -21,7 +21,7 @@ of the step (the slow path).  A built-in reward that the cfg omits is switched o
 """
 from __future__ import annotations
 
-from ..cfg import OBS_ORDER, REWARD_FUNCS, REWARD_ORDER, TERMINATION_FUNCS, TERMINATION_ORDER, RoverEnvCfg, TermCfg
+from ..cfg import OBS_ORDER, REWARD_FUNCS, REWARD_ORDER, TERMINATION_FUNCS, TERMINATION_ORDER, RoverEnvCfg, TermCfg, ViewerCfg
 
 
 def is_reference_cfg(cfg) -> bool:
@@ -124,5 +124,17 @@ def from_reference_cfg(ref) -> RoverEnvCfg:
     # step (~290 us), with the pinned host mirror one copy and one synchronisation (~100 us) -- same numbers, and 0-d CPU tensors
     # satisfy the isinstance / numel() checks of that loop.  The native RoverEnvCfg keeps ORBIT's "device".
     out.log_values = "host"
+    vw = getattr(ref, "viewer", None)
+    if vw is not None:
+        out.viewer = viewer_from_reference(vw)
     out.validate()
+    return out
+
+
+def viewer_from_reference(vw) -> ViewerCfg:
+    """ORBIT's ``cfg.viewer`` (eye, lookat, resolution; rover_env_cfg.py:272 sets the eye) as the rgb_array viewer's cfg."""
+    out = ViewerCfg()
+    out.eye = tuple(float(x) for x in vw.eye)
+    out.lookat = tuple(float(x) for x in getattr(vw, "lookat", out.lookat))
+    out.resolution = tuple(int(x) for x in getattr(vw, "resolution", out.resolution))
     return out

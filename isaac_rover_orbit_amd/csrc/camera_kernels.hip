@@ -5,7 +5,7 @@
 // rover_sim handle with every cell split along its (i, j) - (i+1, j+1) diagonal -- the surface the height scanner casts against.
 //
 // prepare: a max-height pyramid over the heightfield (8 x 8 and 64 x 64 cells per block, plus the global maximum).
-// render:  one wave = one 8 x 8 pixel tile of one env; each lane marches its pixel's ray with a 2-D DDA over the cells,
+// render:  one wave = one 8 x 8 pixel tile of one env; each lane marches its pixel's ray (terrain_march.hpp) with a 2-D DDA over the cells,
 //          skipping a 64 x 64 or 8 x 8 block whenever the ray stays above the block's maximum over the block's whole t-range.
 //          Inside a cell the ray is split at the cell's diagonal and tested against the plane of each triangle it passes.
 //          The signed vertical gap ray - surface is continuous along the ray (the mesh is), so it is carried from one cell
@@ -18,8 +18,14 @@
 #include "../../include/rover_camera.h"
 #include "../../include/rover_hip.h"
 #include "rover_internal.hpp"
+#include "terrain_march.hpp"
 
 namespace {
+
+using terrain_march::L1;
+using terrain_march::L2;
+using terrain_march::Pyramid;
+using terrain_march::pyramid_of;
 
 #define HIP_TRY(expr)                                                                                                  \
     do {                                                                                                               \
@@ -27,27 +33,8 @@ namespace {
         if (_e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, #expr ": %s", hipGetErrorString(_e));         \
     } while (0)
 
-constexpr int L1 = 8;        // cells per side of a fine block
-constexpr int L2 = 64;       // cells per side of a coarse block
 constexpr int TILE = 8;      // pixels per side of a wave's tile
 constexpr int WAVES = 4;     // waves (tiles) per workgroup
-
-struct Pyramid {
-    int c1x, c1y, c2x, c2y;  // blocks per row / column of each level
-    size_t off1, off2, offz, bytes;
-};
-
-Pyramid pyramid_of(int H, int W)
-{
-    Pyramid p;
-    p.c1x = (W - 1 + L1 - 1) / L1; p.c1y = (H - 1 + L1 - 1) / L1;
-    p.c2x = (W - 1 + L2 - 1) / L2; p.c2y = (H - 1 + L2 - 1) / L2;
-    p.off1 = 0;
-    p.off2 = (p.off1 + (size_t)p.c1x * p.c1y * sizeof(float) + 255) & ~(size_t)255;
-    p.offz = (p.off2 + (size_t)p.c2x * p.c2y * sizeof(float) + 255) & ~(size_t)255;
-    p.bytes = p.offz + 256;
-    return p;
-}
 
 // block (bx, by) of `level` cells per side: max over the heightfield NODES of its cells, nodes [level * b, level * b + level]
 __global__ void camera_block_max_kernel(const float *__restrict__ height, int H, int W, int level, int cx, int cy,
@@ -93,8 +80,6 @@ struct CamParams {
     float near_clip, far_clip;
 };
 
-__device__ __forceinline__ float lo_boundary_t(float k, float g0, float inv_gd, bool par) { return par ? INFINITY : (k - g0) * inv_gd; }
-
 // One wave per 8 x 8 tile of one env.  Every loop below is per lane; a lane leaves it at its ray's hit or miss.
 __global__ __launch_bounds__(TILE * TILE * WAVES) void rover_camera_render_kernel(CamParams p)
 {
@@ -135,114 +120,8 @@ __global__ __launch_bounds__(TILE * TILE * WAVES) void rover_camera_render_kerne
     const float dy = Rb[3] * bx + Rb[4] * by + Rb[5] * bz;
     const float dz = Rb[6] * bx + Rb[7] * by + Rb[8] * bz;
 
-    // ---- grid coordinates (cells), the ray's t-range over the terrain's x-y extent and below its maximum
-    const float gox = (ox - p.min_x) * p.inv_res, goy = (oy - p.min_y) * p.inv_res;
-    const float gdx = dx * p.inv_res, gdy = dy * p.inv_res;
-    const bool parx = gdx == 0.0f, pary = gdy == 0.0f;
-    const float igx = parx ? 0.0f : 1.0f / gdx, igy = pary ? 0.0f : 1.0f / gdy;
-    const float xmax = (float)(p.W - 1), ymax = (float)(p.H - 1);
-    const float zmax = *p.zmax;
-    float t_lo = p.near_clip, t_hi = p.far_clip;
-    bool miss = !(isfinite(gox) && isfinite(goy) && isfinite(oz) && isfinite(gdx) && isfinite(gdy) && isfinite(dz));
-    if (parx) miss |= !(gox >= 0.0f && gox <= xmax);
-    else { const float a = -gox * igx, b = (xmax - gox) * igx; t_lo = fmaxf(t_lo, fminf(a, b)); t_hi = fminf(t_hi, fmaxf(a, b)); }
-    if (pary) miss |= !(goy >= 0.0f && goy <= ymax);
-    else { const float a = -goy * igy, b = (ymax - goy) * igy; t_lo = fmaxf(t_lo, fminf(a, b)); t_hi = fminf(t_hi, fmaxf(a, b)); }
-    // a ray whose range starts where it descends through the terrain's maximum was above the surface before: it starts above
-    // (decided here, not from the gap at t_lo, which rounding may put a hair below a surface that reaches the maximum there)
-    bool from_top = false;
-    if (dz > 0.0f) t_hi = fminf(t_hi, (zmax - oz) / dz);
-    else if (dz < 0.0f) { const float tz = (zmax - oz) / dz; from_top = tz >= t_lo; t_lo = fmaxf(t_lo, tz); }
-    else miss |= oz > zmax;
-    miss |= !(t_lo <= t_hi);
-
-    float depth = INFINITY;
-    if (!miss) {
-        const int sx = gdx > 0.0f ? 1 : -1, sy = gdy > 0.0f ? 1 : -1;
-        const int ux = sx > 0, uy = sy > 0;           // next boundary of cell i in the direction of travel: i + ux
-        int ix = min(max((int)floorf(fmaf(t_lo, gdx, gox)), 0), p.W - 2);
-        int iy = min(max((int)floorf(fmaf(t_lo, gdy, goy)), 0), p.H - 2);
-        float t = t_lo;
-        float g = 0.0f;          // gap at t, valid when have_g
-        bool have_g = false;
-        int above = from_top ? 1 : -1;   // side of the surface the ray starts on (-1: not known yet; touching counts as above)
-        bool check_blocks = true;
-        const float *hf = p.height;
-        const int W = p.W;
-        for (;;) {
-            if (check_blocks && above != 0) {
-                // a block is skipped while the ray's lower end over the block's t-range is above the block's maximum
-                bool skipped = false;
-                for (int lv = 0; lv < 2 && !skipped; ++lv) {
-                    const int B = lv == 0 ? L2 : L1;
-                    const int bxi = ix / B, byi = iy / B;
-                    const float bmax = lv == 0 ? p.l2[byi * p.c2x + bxi] : p.l1[byi * p.c1x + bxi];
-                    const float tx = lo_boundary_t((float)((bxi + ux) * B), gox, igx, parx);
-                    const float ty = lo_boundary_t((float)((byi + uy) * B), goy, igy, pary);
-                    const float te = fminf(fminf(tx, ty), t_hi);
-                    if (fminf(fmaf(t, dz, oz), fmaf(te, dz, oz)) > bmax) {
-                        skipped = true;
-                        above = 1;
-                        have_g = false;
-                        t = te;
-                        if (te >= t_hi) break;
-                        if (tx <= ty) {
-                            ix = (bxi + ux) * B - (1 - ux);
-                            const int jy = (int)floorf(fmaf(te, gdy, goy));
-                            iy = sy > 0 ? min(max(jy, iy), byi * B + B - 1) : max(min(jy, iy), byi * B);
-                        } else {
-                            iy = (byi + uy) * B - (1 - uy);
-                            const int jx = (int)floorf(fmaf(te, gdx, gox));
-                            ix = sx > 0 ? min(max(jx, ix), bxi * B + B - 1) : max(min(jx, ix), bxi * B);
-                        }
-                    }
-                }
-                if (skipped) {
-                    if (t >= t_hi || ix < 0 || iy < 0 || ix > p.W - 2 || iy > p.H - 2) break;
-                    continue;
-                }
-                check_blocks = false;
-            }
-            // ---- cell (ix, iy) over [t, tc]
-            const float tx = lo_boundary_t((float)(ix + ux), gox, igx, parx);
-            const float ty = lo_boundary_t((float)(iy + uy), goy, igy, pary);
-            const float tc = fmaxf(fminf(fminf(tx, ty), t_hi), t);
-            const float *q = hf + (size_t)iy * W + ix;
-            const float h00 = q[0], h01 = q[1], h10 = q[W], h11 = q[W + 1];
-            const float fx0 = gox - (float)ix, fy0 = goy - (float)iy;
-            // lower triangle (fx >= fy): corners 00, 01, 11; upper: 00, 10, 11
-            auto gap = [&](float tt, bool lower) {
-                const float a = lower ? h01 - h00 : h11 - h10, b = lower ? h11 - h01 : h10 - h00;
-                const float fx = fmaf(tt, gdx, fx0), fy = fmaf(tt, gdy, fy0);
-                return fmaf(tt, dz, oz) - fmaf(fy, b, fmaf(fx, a, h00));
-            };
-            // the diagonal fx = fy splits [t, tc] at tm
-            const float e0 = fx0 - fy0, de = gdx - gdy;
-            const float ea = fmaf(t, de, e0), eb = fmaf(tc, de, e0);
-            float tm = tc;
-            bool lowerA = ea + eb >= 0.0f;
-            if ((ea >= 0.0f) != (eb >= 0.0f)) {
-                tm = fminf(fmaxf(-e0 / de, t), tc);
-                lowerA = eb < 0.0f;          // the second piece lies on the side eb is on
-            }
-            if (!have_g) g = gap(t, lowerA);
-            if (above < 0) above = g >= 0.0f;
-            const float gm = gap(tm, lowerA);
-            const float gc = tm < tc ? gap(tc, !lowerA) : gm;
-            auto crossed = [&](float gg) { return above ? gg <= 0.0f : gg > 0.0f; };
-            if (crossed(g)) { depth = t; break; }
-            if (crossed(gm)) { depth = fmaf(tm - t, g / (g - gm), t); break; }
-            if (crossed(gc)) { depth = fmaf(tc - tm, gm / (gm - gc), tm); break; }
-            if (tc >= t_hi) break;
-            g = gc;
-            have_g = true;
-            t = tc;
-            const int bx0 = ix / L1, by0 = iy / L1;
-            if (tx <= ty) ix += sx; else iy += sy;
-            if (ix < 0 || iy < 0 || ix > p.W - 2 || iy > p.H - 2) break;
-            check_blocks = ix / L1 != bx0 || iy / L1 != by0;
-        }
-    }
+    terrain_march::MarchHit hit;
+    const float depth = terrain_march::march_terrain<false>(p, ox, oy, oz, dx, dy, dz, hit);
     const size_t o = ((size_t)env * p.img_h + v) * p.img_w + u;   // 64-bit: N x 14 400 passes 2^31 at 149 k envs
     __builtin_nontemporal_store(depth, p.depth + o);
 }
@@ -260,6 +139,22 @@ bool config_ok(const rover_camera_config *c)
 }
 
 }  // namespace
+
+// the max-height pyramid of the terrain bound to `s` into ws[0, pyramid_of(H, W).bytes) (camera and viewer workspaces alike)
+int rover_internal_build_pyramid(const rover_sim_view &s, void *ws, void *stream)
+{
+    const Pyramid py = pyramid_of(s.H, s.W);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *base = static_cast<char *>(ws);
+    float *l1 = reinterpret_cast<float *>(base + py.off1), *l2 = reinterpret_cast<float *>(base + py.off2);
+    float *zmax = reinterpret_cast<float *>(base + py.offz);
+    const int n1 = py.c1x * py.c1y, n2 = py.c2x * py.c2y;
+    hipLaunchKernelGGL(camera_block_max_kernel, dim3((n1 + 255) / 256), dim3(256), 0, st, s.height, s.H, s.W, L1, py.c1x, py.c1y, l1);
+    hipLaunchKernelGGL(camera_block_max_kernel, dim3((n2 + 255) / 256), dim3(256), 0, st, s.height, s.H, s.W, L2, py.c2x, py.c2y, l2);
+    hipLaunchKernelGGL(camera_global_max_kernel, dim3(1), dim3(256), 0, st, l2, n2, zmax);
+    HIP_TRY(hipGetLastError());
+    return ROVER_OK;
+}
 
 extern "C" {
 
@@ -296,15 +191,8 @@ int rover_camera_prepare(rover_sim *sim, const rover_camera_config *cfg, void *w
     const Pyramid py = pyramid_of(s.H, s.W);
     if (bytes < py.bytes) return rover_internal_fail(ROVER_ERR_INVALID, "camera workspace too small");
     if (reinterpret_cast<uintptr_t>(ws) & 255) return rover_internal_fail(ROVER_ERR_INVALID, "camera workspace must be 256-byte aligned");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char *base = static_cast<char *>(ws);
-    float *l1 = reinterpret_cast<float *>(base + py.off1), *l2 = reinterpret_cast<float *>(base + py.off2);
-    float *zmax = reinterpret_cast<float *>(base + py.offz);
-    const int n1 = py.c1x * py.c1y, n2 = py.c2x * py.c2y;
-    hipLaunchKernelGGL(camera_block_max_kernel, dim3((n1 + 255) / 256), dim3(256), 0, st, s.height, s.H, s.W, L1, py.c1x, py.c1y, l1);
-    hipLaunchKernelGGL(camera_block_max_kernel, dim3((n2 + 255) / 256), dim3(256), 0, st, s.height, s.H, s.W, L2, py.c2x, py.c2y, l2);
-    hipLaunchKernelGGL(camera_global_max_kernel, dim3(1), dim3(256), 0, st, l2, n2, zmax);
-    HIP_TRY(hipGetLastError());
+    const int rc = rover_internal_build_pyramid(s, ws, stream);
+    if (rc != ROVER_OK) return rc;
     *s.camera_ws = ws;
     *s.camera_gen = s.terrain_gen;
     return ROVER_OK;

@@ -25,18 +25,23 @@ struct DeviceGuard {
 
 struct rover_sim;
 // What another translation unit (camera_kernels.hip) may read of a handle: its device, its bound state and terrain, the
-// call-order flags and the terrain generation (bumped by every rover_set_terrain*), plus the one word of camera bookkeeping
-// the handle keeps for it: which workspace was prepared for which terrain generation.
+// call-order flags and the terrain generation (bumped by every rover_set_terrain*), plus the bookkeeping the handle keeps for
+// the camera and the viewer: which workspace was prepared for which terrain generation.
 struct rover_sim_view {
     int device;              // the handle's HIP device (DeviceGuard)
     const float *state;      // SoA state words, state[word * n + env]; NULL before rover_bind
     int n;
     bool have_terrain, phase_open;
     const float *height;     // (H, W) fp32 heightfield, row = y
+    const float *obstacle;   // (H, W) fp32 obstacle layer (rock height above the ground), row = y
     int H, W;
     float res, min_x, min_y;
     uint64_t terrain_gen;
     const void **camera_ws;  // the handle's record of the last rover_camera_prepare
     uint64_t *camera_gen;
+    const void **viewer_ws;  // ... and of the last rover_viewer_prepare
+    uint64_t *viewer_gen;
 };
 __attribute__((visibility("hidden"))) rover_sim_view rover_internal_view(rover_sim *sim);
+// camera_kernels.hip: the terrain's max-height pyramid (terrain_march.hpp layout) into `ws`, asynchronously on `stream`
+__attribute__((visibility("hidden"))) int rover_internal_build_pyramid(const rover_sim_view &s, void *ws, void *stream);

@@ -3527,12 +3527,14 @@ struct rover_sim {
     uint64_t terrain_gen;    // rover_set_terrain* calls so far: a camera workspace is valid for the generation it was prepared for
     const void *camera_ws;   // rover_camera_prepare's last workspace and the generation it was built for (rover_internal_view)
     uint64_t camera_gen;
+    const void *viewer_ws;   // rover_viewer_prepare's, likewise
+    uint64_t viewer_gen;
 };
 rover_sim_view rover_internal_view(rover_sim *sim)
 {
     const RvParams &p = sim->p;
-    return rover_sim_view{sim->device, sim->state, p.n, sim->have_terrain, sim->phase_open, p.height, p.H, p.W, p.res, p.min_x, p.min_y,
-                          sim->terrain_gen, &sim->camera_ws, &sim->camera_gen};
+    return rover_sim_view{sim->device, sim->state, p.n, sim->have_terrain, sim->phase_open, p.height, p.obstacle, p.H, p.W, p.res,
+                          p.min_x, p.min_y, sim->terrain_gen, &sim->camera_ws, &sim->camera_gen, &sim->viewer_ws, &sim->viewer_gen};
 }
 
 

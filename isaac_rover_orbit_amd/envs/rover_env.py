@@ -248,9 +248,15 @@ LOG_KEYS = ([f"Episode Reward/{k}" for k in REWARD_ORDER] + [f"Episode Terminati
 
 
 class RoverEnv(RLTaskEnv):
-    """MI355X-native ``AAURoverEnv-v0``.  ``RoverEnv(cfg)`` / ``gym.make("AAURoverEnv-v0", cfg=cfg)``."""
+    """MI355X-native ``AAURoverEnv-v0``.  ``RoverEnv(cfg)`` / ``gym.make("AAURoverEnv-v0", cfg=cfg)``.
+
+    ``render_mode="rgb_array"`` (or the reference's ``viewport=True``): ``render()`` returns the (H, W, 3) uint8 frame of the camera
+    ``cfg.viewer`` places, which ``gymnasium.wrappers.RecordVideo`` records."""
+    metadata = {"render_modes": [None, "rgb_array"]}
 
     def __init__(self, cfg: RoverEnvCfg | None = None, terrain: Terrain | None = None, render_mode=None, **kwargs):
+        if render_mode is None and kwargs.pop("viewport", False):
+            render_mode = "rgb_array"          # what the reference passes viewport=args_cli.video for (train.py:123-125)
         if cfg is not None and not isinstance(cfg, RoverEnvCfg):
             # a reference-style cfg (the reference's AAURoverEnvCfg on ORBIT / compat configclasses): translate it
             from ..compat.convert import from_reference_cfg, is_reference_cfg
@@ -832,7 +838,58 @@ class RoverEnv(RLTaskEnv):
         return self.obs_buf
 
     def render(self):
-        return None
+        """``"rgb_array"``: the (H, W, 3) uint8 frame of the current state (a numpy view of a host copy, as ORBIT returns
+        ``rgb_data[:, :, :3]``); otherwise None."""
+        if self.render_mode != "rgb_array":
+            return None
+        return self.render_rgb().cpu().numpy()[:, :, :3]
+
+    def _viewer_native(self):
+        return self.cfg.viewer.to_native(self.num_envs)
+
+    def _viewer_workspace(self, vc):
+        """The viewer's workspace (terrain pyramid + per-frame bins), allocated and prepared on the first render."""
+        if getattr(self, "_viewer_ws", None) is None:
+            with torch.cuda.device(self.device):
+                nb = int(self._lib.rover_viewer_workspace_bytes(self._h, C.byref(vc)))
+                if nb == 0:
+                    raise _lib.RoverHipError("rover_viewer_workspace_bytes: no terrain bound or invalid viewer config")
+                ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=self.device)
+                _lib.check(self._lib.rover_viewer_prepare(self._h, C.byref(vc), _ptr(ws), nb, self._stream()), "rover_viewer_prepare")
+            self._viewer_ws = ws
+            self._viewer_buf = []
+            self._viewer_cur = 0
+        return self._viewer_ws
+
+    def render_frame(self, depth: bool = False, object_id: bool = False):
+        """A fresh viewer frame of the current state in new device buffers: (rgba (H, W, 4) uint8, depth (H, W) fp32 or None,
+        object_id (H, W) int32 or None), asynchronous on the current stream."""
+        vc = self._viewer_native()
+        ws = self._viewer_workspace(vc)
+        h, w = vc.height, vc.width
+        rgba = torch.empty(h, w, 4, dtype=torch.uint8, device=self.device)
+        dep = torch.empty(h, w, dtype=torch.float32, device=self.device) if depth else None
+        ids = torch.empty(h, w, dtype=torch.int32, device=self.device) if object_id else None
+        self._viewer_render(vc, ws, rgba, dep, ids)
+        return rgba, dep, ids
+
+    def _viewer_render(self, vc, ws, rgba, dep=None, ids=None):
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rover_viewer_render(self._h, C.byref(vc), _ptr(ws), _ptr(rgba), _ptr(dep), _ptr(ids),
+                                                     self._stream()), "rover_viewer_render")
+
+    def render_rgb(self) -> torch.Tensor:
+        """The viewer frame of the current state as a device (H, W, 4) uint8 RGBA tensor, without a host synchronisation.  Two
+        buffers rotate, so the frame one call returns stays valid through the next call."""
+        vc = self._viewer_native()
+        ws = self._viewer_workspace(vc)
+        shape = (vc.height, vc.width, 4)
+        if not self._viewer_buf or tuple(self._viewer_buf[0].shape) != shape:
+            self._viewer_buf = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self._viewer_cur ^= 1
+        buf = self._viewer_buf[self._viewer_cur]
+        self._viewer_render(vc, ws, buf)
+        return buf
 
     def close(self):
         if not self._closed and getattr(self, "_h", None):
