@@ -3,7 +3,9 @@
 hyper-parameters (learning/skrl/rover_ppo.yaml: rollouts 60, 4 epochs, 60 mini-batches, gamma 0.99, lambda 0.95,
 lr 1e-4, clip 0.2, grad-norm 0.5, KL-adaptive learning rate, kl_threshold 0.008).  Rollouts run entirely on the fused
 kernels (policy mean and value through ``RoverNet``, re-packed after every update; env.step = two HIP kernels); only
-the PPO update itself uses torch autograd.  A stand-in for the reference's skrl trainer (examples/02_train/train.py),
+the PPO update itself uses torch autograd (``--update torch``, the default) or the fused HIP update of
+``isaac_rover_orbit_amd.ppo.FusedPPO`` (``--update fused``: GAE, loss, backward, clip and Adam as HIP kernels; the rollout reads
+the trainer's parameters directly, no re-packing).  A stand-in for the reference's skrl trainer (examples/02_train/train.py),
 which needs packages that are not part of this repository.
 
     python examples/04_train_ppo.py --num_envs 4096 --iterations 100
@@ -22,6 +24,8 @@ from isaac_rover_orbit_amd import terrain as T  # noqa: E402
 from isaac_rover_orbit_amd.cfg import RoverEnvCfg  # noqa: E402
 from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
 from isaac_rover_orbit_amd.policy import RoverNet  # noqa: E402
+
+GAMMA, LAM, CLIP, VCLIP, KL_THR = 0.99, 0.95, 0.2, 0.2, 0.008
 
 
 class Net(nn.Module):
@@ -47,6 +51,22 @@ class Net(nn.Module):
         return x
 
 
+def ppo_loss(policy, value, o, a, old_lp, old_v, ret, adv, clip=CLIP, vclip=VCLIP):
+    """The clipped PPO loss of one minibatch (skrl PPO with clip_predicted_values, value-loss scale 1, entropy scale 0) and the
+    minibatch KL estimate ((r - 1) - log r).mean() (no gradient)."""
+    mean = policy(o)
+    ls = policy.log_std_parameter.clamp(-20.0, 2.0)
+    lp = (-0.5 * ((a - mean) / ls.exp()) ** 2 - ls - 0.9189385332).sum(1)
+    ratio = (lp - old_lp).exp()
+    with torch.no_grad():
+        kl = ((ratio - 1) - (lp - old_lp)).mean()
+    pl = -torch.min(ratio * adv, ratio.clamp(1 - clip, 1 + clip) * adv).mean()
+    v = value(o).squeeze(1)
+    v = old_v + (v - old_v).clamp(-vclip, vclip)
+    vl = ((ret - v) ** 2).mean()
+    return pl + vl, kl
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--num_envs", type=int, default=4096)
@@ -54,6 +74,8 @@ def main():
     ap.add_argument("--rollouts", type=int, default=60)
     ap.add_argument("--out", default=None, help="write the per-iteration statistics as JSON lines")
     ap.add_argument("--save", default=None, help="write a skrl-style checkpoint {'policy': state_dict, 'value': state_dict}")
+    ap.add_argument("--update", choices=("torch", "fused"), default="torch",
+                    help="PPO update: torch autograd + torch.optim.Adam, or the fused HIP kernels (isaac_rover_orbit_amd.ppo)")
     args = ap.parse_args()
     torch.manual_seed(42)
     dev = torch.device("cuda")
@@ -64,7 +86,11 @@ def main():
     env = RoverEnv(cfg, terrain=terrain)
     policy, value = Net(2, True).to(dev), Net(1, False).to(dev)
     opt = torch.optim.Adam(list(policy.parameters()) + list(value.parameters()), lr=1e-4)
-    gamma, lam, clip, vclip, kl_thr = 0.99, 0.95, 0.2, 0.2, 0.008
+    gamma, lam, clip, vclip, kl_thr = GAMMA, LAM, CLIP, VCLIP, KL_THR
+    fused = None
+    if args.update == "fused":
+        from isaac_rover_orbit_amd.ppo import FusedPPO
+        fused = FusedPPO(policy.state_dict(), value.state_dict(), lr=1e-4)
 
     obs_buf = torch.empty(Tn, n, 965, device=dev)
     act_buf = torch.empty(Tn, n, 2, device=dev)
@@ -76,9 +102,13 @@ def main():
     for it in range(args.iterations):
         t0 = time.perf_counter()
         # ---- rollout on the fused kernels
-        actor = RoverNet.from_state_dict(policy.state_dict(), final_act="tanh")
-        critic = RoverNet.from_state_dict(value.state_dict(), final_act="none")
-        log_std = policy.log_std_parameter.detach().clamp(-20.0, 2.0)
+        if fused is None:
+            actor = RoverNet.from_state_dict(policy.state_dict(), final_act="tanh")
+            critic = RoverNet.from_state_dict(value.state_dict(), final_act="none")
+            log_std = policy.log_std_parameter.detach().clamp(-20.0, 2.0)
+        else:                                   # the trainer's own parameters: nothing to re-pack
+            actor, critic = fused.actor, fused.critic
+            log_std = fused.log_std.clamp(-20.0, 2.0)
         std = log_std.exp()
         ep_count = torch.zeros((), device=dev); ep_stats = torch.zeros(4, device=dev)
         for t in range(Tn):
@@ -93,55 +123,56 @@ def main():
             lv = env.episode_log_vector
             ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
         torch.cuda.synchronize(); t_roll = time.perf_counter() - t0
-        # ---- GAE (skrl PPO: bootstraps through time-outs like the reference's config)
-        with torch.no_grad():
-            last_v = critic(o).squeeze(1)
-            adv = torch.zeros_like(rew_buf); gae = torch.zeros(n, device=dev)
-            for t in reversed(range(Tn)):
-                nv = last_v if t == Tn - 1 else val_buf[t + 1]
-                nd = 1.0 - done_buf[t]
-                delta = rew_buf[t] + gamma * nv * nd - val_buf[t]
-                gae = delta + gamma * lam * nd * gae
-                adv[t] = gae
-            ret = adv + val_buf
-            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
-        # ---- PPO update (torch autograd)
-        B = Tn * n
-        fo, fa, flp, fv, fr, fadv = (x.reshape(B, *x.shape[2:]) for x in (obs_buf, act_buf, logp_buf, val_buf, ret, adv))
-        kl_mean = 0.0
-        for epoch in range(4):
-            perm = torch.randperm(B, device=dev)
-            kls = []
-            for mb in perm.chunk(60):
-                mean = policy(fo[mb])
-                ls = policy.log_std_parameter.clamp(-20.0, 2.0)
-                lp = (-0.5 * ((fa[mb] - mean) / ls.exp()) ** 2 - ls - 0.9189385332).sum(1)
-                ratio = (lp - flp[mb]).exp()
-                with torch.no_grad():
-                    kls.append(((ratio - 1) - (lp - flp[mb])).mean())
-                pl = -torch.min(ratio * fadv[mb], ratio.clamp(1 - clip, 1 + clip) * fadv[mb]).mean()
-                v = value(fo[mb]).squeeze(1)
-                v = fv[mb] + (v - fv[mb]).clamp(-vclip, vclip)
-                vl = ((fr[mb] - v) ** 2).mean()
-                opt.zero_grad(set_to_none=True)
-                (pl + vl).backward()
-                nn.utils.clip_grad_norm_(list(policy.parameters()) + list(value.parameters()), 0.5)
-                opt.step()
-            kl_mean = torch.stack(kls).mean().item()
-            lr = opt.param_groups[0]["lr"]                     # KLAdaptiveRL
-            if kl_mean > 2 * kl_thr: lr = max(lr / 1.5, 1e-6)
-            elif kl_mean < 0.5 * kl_thr: lr = min(lr * 1.5, 1e-2)
-            for g in opt.param_groups: g["lr"] = lr
+        if fused is not None:
+            # ---- GAE and the PPO update on the fused HIP kernels (isaac_rover_orbit_amd.ppo)
+            with torch.no_grad():
+                last_v = critic(o).squeeze(1)
+                adv, ret = fused.gae(rew_buf, done_buf, val_buf, last_v)
+                adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+            kls, _ = fused.update(obs_buf, act_buf, logp_buf, val_buf, ret, adv)
+            kl_mean = kls[-1]
+        else:
+            # ---- GAE (skrl PPO: bootstraps through time-outs like the reference's config)
+            with torch.no_grad():
+                last_v = critic(o).squeeze(1)
+                adv = torch.zeros_like(rew_buf); gae = torch.zeros(n, device=dev)
+                for t in reversed(range(Tn)):
+                    nv = last_v if t == Tn - 1 else val_buf[t + 1]
+                    nd = 1.0 - done_buf[t]
+                    delta = rew_buf[t] + gamma * nv * nd - val_buf[t]
+                    gae = delta + gamma * lam * nd * gae
+                    adv[t] = gae
+                ret = adv + val_buf
+                adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+            # ---- PPO update (torch autograd)
+            B = Tn * n
+            fo, fa, flp, fv, fr, fadv = (x.reshape(B, *x.shape[2:]) for x in (obs_buf, act_buf, logp_buf, val_buf, ret, adv))
+            kl_mean = 0.0
+            for epoch in range(4):
+                perm = torch.randperm(B, device=dev)
+                kls = []
+                for mb in perm.chunk(60):
+                    loss, kl = ppo_loss(policy, value, fo[mb], fa[mb], flp[mb], fv[mb], fr[mb], fadv[mb], clip, vclip)
+                    kls.append(kl)
+                    opt.zero_grad(set_to_none=True)
+                    loss.backward()
+                    nn.utils.clip_grad_norm_(list(policy.parameters()) + list(value.parameters()), 0.5)
+                    opt.step()
+                kl_mean = torch.stack(kls).mean().item()
+                lr = opt.param_groups[0]["lr"]                     # KLAdaptiveRL
+                if kl_mean > 2 * kl_thr: lr = max(lr / 1.5, 1e-6)
+                elif kl_mean < 0.5 * kl_thr: lr = min(lr * 1.5, 1e-2)
+                for g in opt.param_groups: g["lr"] = lr
         torch.cuda.synchronize()
         st = {"iteration": it, "mean_step_reward": rew_buf.mean().item(), "episodes": ep_count.item(),
               "time_out": ep_stats[0].item(), "success": ep_stats[1].item(), "far": ep_stats[2].item(),
-              "collision": ep_stats[3].item(), "kl": kl_mean, "lr": opt.param_groups[0]["lr"],
+              "collision": ep_stats[3].item(), "kl": kl_mean, "lr": opt.param_groups[0]["lr"] if fused is None else fused.lr,
               "rollout_s": t_roll, "rollout_env_steps_per_s": Tn * n / t_roll, "iteration_s": time.perf_counter() - t0}
         print(json.dumps(st), flush=True)
         if out:
             out.write(json.dumps(st) + "\n"); out.flush()
     if args.save:
-        torch.save({"policy": policy.state_dict(), "value": value.state_dict()}, args.save)
+        torch.save(fused.state_dict() if fused is not None else {"policy": policy.state_dict(), "value": value.state_dict()}, args.save)
     env.close()
 
 

@@ -36,6 +36,9 @@ EXPORTS = [
     "rover_camera_render",
     "rover_viewer_default_config", "rover_viewer_config_bytes", "rover_viewer_workspace_bytes", "rover_viewer_prepare",  # rover_viewer.h
     "rover_viewer_render",
+    "rover_ppo_default_hparams", "rover_ppo_hparams_bytes", "rover_ppo_state_bytes", "rover_ppo_param_floats",  # rover_train.h
+    "rover_ppo_workspace_bytes", "rover_ppo_minibatch", "rover_ppo_apply", "rover_ppo_gae", "rover_ppo_kl_schedule",
+    "rover_policy_unpack",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH = 0, 1, 2
@@ -53,6 +56,19 @@ class PolicyDesc(C.Structure):
                 ("n_enc", C.c_int32), ("n_mlp", C.c_int32), ("leaky_slope", C.c_float),
                 ("layers", PolicyLayer * POLICY_MAX_LAYERS)]
 
+
+class PpoHparams(C.Structure):
+    """Mirror of ``struct rover_ppo_hparams`` (include/rover_train.h)."""
+    _fields_ = [("gamma", C.c_float), ("lam", C.c_float), ("clip_ratio", C.c_float), ("value_clip", C.c_float),
+                ("value_loss_scale", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
+                ("max_grad_norm", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("kl_threshold", C.c_float), ("lr_factor", C.c_float), ("lr_min", C.c_float), ("lr_max", C.c_float)]
+
+
+class PpoState(C.Structure):
+    """Mirror of ``struct rover_ppo_state`` (include/rover_train.h; it lives in device memory)."""
+    _fields_ = [("lr", C.c_double), ("step", C.c_int32), ("grad_norm", C.c_float), ("clip_coef", C.c_float),
+                ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("reserved", C.c_float)]
 
 
 class RoverHipError(RuntimeError):
@@ -220,6 +236,20 @@ def load():
     lib.rover_viewer_workspace_bytes.restype = C.c_size_t
     lib.rover_viewer_prepare.argtypes = [vp, C.POINTER(ViewerConfig), vp, C.c_size_t, vp]
     lib.rover_viewer_render.argtypes = [vp, C.POINTER(ViewerConfig), vp, vp, vp, vp, vp]
+    lib.rover_ppo_default_hparams.argtypes = [C.POINTER(PpoHparams)]
+    lib.rover_ppo_hparams_bytes.restype = C.c_size_t
+    lib.rover_ppo_state_bytes.restype = C.c_size_t
+    lib.rover_ppo_param_floats.argtypes = [C.POINTER(PolicyDesc), C.POINTER(PolicyDesc)]
+    lib.rover_ppo_param_floats.restype = C.c_size_t
+    lib.rover_ppo_workspace_bytes.argtypes = [i32]
+    lib.rover_ppo_workspace_bytes.restype = C.c_size_t
+    lib.rover_ppo_minibatch.argtypes = [C.POINTER(PolicyDesc), C.POINTER(PolicyDesc), C.POINTER(PpoHparams), vp, vp, vp, vp, vp, vp,
+                                        vp, vp, i32, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    lib.rover_ppo_apply.argtypes = [C.POINTER(PolicyDesc), C.POINTER(PolicyDesc), C.POINTER(PpoHparams), vp, vp, vp, vp, vp, vp, vp,
+                                    i32, vp, C.c_size_t, vp]
+    lib.rover_ppo_gae.argtypes = [C.POINTER(PpoHparams), vp, vp, vp, vp, i32, i32, vp, vp, vp]
+    lib.rover_ppo_kl_schedule.argtypes = [C.POINTER(PpoHparams), vp, i32, vp, vp, vp]
+    lib.rover_policy_unpack.argtypes = [C.POINTER(PolicyDesc), vp, C.POINTER(vp), C.POINTER(vp)]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -235,6 +265,8 @@ def load():
         raise RoverHipError("struct rover_camera_config of librover_hip.so does not match the Python mirror")
     if lib.rover_viewer_config_bytes() != C.sizeof(ViewerConfig):
         raise RoverHipError("struct rover_viewer_config of librover_hip.so does not match the Python mirror")
+    if lib.rover_ppo_hparams_bytes() != C.sizeof(PpoHparams) or lib.rover_ppo_state_bytes() != C.sizeof(PpoState):
+        raise RoverHipError("struct rover_ppo_hparams / rover_ppo_state of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib

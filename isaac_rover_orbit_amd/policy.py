@@ -69,6 +69,25 @@ class RoverNet:
         return cls(ws, bs, n_enc=n_enc, final_act=final_act, **kw)
 
     @classmethod
+    def from_packed(cls, desc: "_lib.PolicyDesc", packed: torch.Tensor, n_copies: int, obs_dim: int = 965) -> "RoverNet":
+        """A network over an EXISTING device buffer of ``n_copies`` packed replicas (no copy, no host packing): the buffer is
+        aliased, so whoever writes it (``ppo.FusedPPO`` after every optimiser step) changes what this network computes."""
+        if not packed.is_cuda or packed.dtype != torch.float32 or not packed.is_contiguous():
+            raise ValueError("packed must be a contiguous float32 cuda tensor")
+        n_floats = int(_lib.load().rover_policy_packed_floats(C.byref(desc)))
+        if n_floats == 0 or packed.numel() != n_floats * n_copies:
+            raise ValueError(f"packed holds {packed.numel()} floats, expected {n_copies} x {n_floats}")
+        net = cls.__new__(cls)
+        net._lib = _lib.load()
+        net.device = packed.device
+        net.desc = desc
+        net.n_copies = int(n_copies)
+        net.packed = packed
+        net.out_dim = int(desc.layers[desc.n_enc + desc.n_mlp - 1].N)
+        net.obs_dim = obs_dim
+        return net
+
+    @classmethod
     def from_checkpoint(cls, path: str, role: str = "policy", **kw) -> "RoverNet":
         """skrl agent checkpoint (``agent.save``): ``{"policy": state_dict, "value": state_dict, ...}`` (eval.py:146-155)."""
         ck = torch.load(path, map_location="cpu", weights_only=False)
