@@ -27,7 +27,9 @@ extern "C" {
 #endif
 
 enum { ROVER_POLICY_MAX_LAYERS = 8 };
-enum { ROVER_ACT_NONE = 0, ROVER_ACT_LEAKY_RELU = 1, ROVER_ACT_TANH = 2 };
+/* ROVER_ACT_ELU: torch.nn.ELU() (alpha 1), evaluated as v > 0 ? v : expm1f(v) in fp32 (the device libm's expm1f, not
+ * expf(v) - 1) -- part of the numerics contract. */
+enum { ROVER_ACT_NONE = 0, ROVER_ACT_LEAKY_RELU = 1, ROVER_ACT_TANH = 2, ROVER_ACT_ELU = 3 };
 
 typedef struct rover_policy_layer {
     int32_t K, N;        /* in / out features of the Linear (torch weight shape (N, K)) */
@@ -52,6 +54,12 @@ typedef struct rover_policy_desc {
 /* Fills `d` with the reference architecture (get_models.py:36-62): out_dim 2 + final tanh = policy mean,
  * out_dim 1 + no final activation = value. */
 int rover_policy_default_desc(rover_policy_desc *d, int32_t out_dim, int32_t final_tanh);
+
+/* Fills `d` with the lift task's layout (skrl_ppo_cfg.yaml of FrankaCubeLift-v0, skrl gaussian / deterministic model):
+ * obs_dim = prop_dim = 36, no encoder, MLP 36 -> 256 -> 128 -> 64 -> out_dim, ELU on the hidden layers, no final activation
+ * (out_dim 8 = policy mean, 1 = value).  No layer is split-K: the widest K is 256 and every layer but the last has >= 4 column
+ * tiles for the 8 waves, so the one-chain form (split_k = 0) keeps the k order of a plain fmaf chain. */
+int rover_lift_policy_desc(rover_policy_desc *d, int32_t out_dim);
 
 /* Host-side packing (pure CPU, no GPU needed): weights[i] = torch `weight` of layer i, row-major (N, K); biases[i] (N,).
  * Sets w_off / b_off in `d` and writes rover_policy_packed_floats(d) floats to `packed` (host memory), which the caller

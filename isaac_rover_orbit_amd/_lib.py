@@ -27,7 +27,7 @@ EXPORTS = [
     "rover_terrain_rasterize", "rover_terrain_surface", "rover_terrain_rock_mask", "rover_terrain_scratch_bytes",   # rover_terrain.h
     "rover_set_terrain_lookup",
     "rover_policy_default_desc", "rover_policy_packed_floats", "rover_policy_pack", "rover_policy_forward",  # rover_policy.h
-    "rover_policy_forward_pair",
+    "rover_policy_forward_pair", "rover_lift_policy_desc",
     "rover_lift_default_config", "rover_lift_config_bytes", "rover_lift_state_words", "rover_lift_create", "rover_lift_destroy",
     "rover_lift_workspace_bytes", "rover_lift_bind", "rover_lift_reset", "rover_lift_step", "rover_lift_terms",   # rover_lift.h
     "rover_lift_model_constants", "rover_lift_set_seed", "rover_lift_profile_step", "rover_lift_kernel_name",
@@ -39,9 +39,12 @@ EXPORTS = [
     "rover_ppo_default_hparams", "rover_ppo_hparams_bytes", "rover_ppo_state_bytes", "rover_ppo_param_floats",  # rover_train.h
     "rover_ppo_workspace_bytes", "rover_ppo_minibatch", "rover_ppo_apply", "rover_ppo_gae", "rover_ppo_kl_schedule",
     "rover_policy_unpack",
+    "rover_lift_ppo_default_hparams", "rover_lift_ppo_hparams_bytes", "rover_lift_ppo_state_bytes",  # rover_lift_train.h
+    "rover_lift_ppo_param_floats", "rover_lift_ppo_workspace_bytes", "rover_lift_ppo_scaler_doubles", "rover_lift_ppo_standardize",
+    "rover_lift_ppo_minibatch", "rover_lift_ppo_apply", "rover_lift_ppo_kl_schedule",
 ]
 POLICY_MAX_LAYERS = 8
-ACT_NONE, ACT_LEAKY_RELU, ACT_TANH = 0, 1, 2
+ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
 
 
 class PolicyLayer(C.Structure):
@@ -69,6 +72,22 @@ class PpoState(C.Structure):
     """Mirror of ``struct rover_ppo_state`` (include/rover_train.h; it lives in device memory)."""
     _fields_ = [("lr", C.c_double), ("step", C.c_int32), ("grad_norm", C.c_float), ("clip_coef", C.c_float),
                 ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("reserved", C.c_float)]
+
+
+class LiftPpoHparams(C.Structure):
+    """Mirror of ``struct rover_lift_ppo_hparams`` (include/rover_lift_train.h)."""
+    _fields_ = [("gamma", C.c_float), ("lam", C.c_float), ("clip_ratio", C.c_float), ("value_clip", C.c_float),
+                ("value_loss_scale", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
+                ("max_grad_norm", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("kl_threshold", C.c_float), ("lr_factor", C.c_float), ("lr_min", C.c_float), ("lr_max", C.c_float),
+                ("kl_early_stop", C.c_float), ("reward_scale", C.c_float), ("scaler_eps", C.c_float), ("scaler_clip", C.c_float)]
+
+
+class LiftPpoState(C.Structure):
+    """Mirror of ``struct rover_lift_ppo_state`` (include/rover_lift_train.h; it lives in device memory)."""
+    _fields_ = [("lr", C.c_double), ("step", C.c_int32), ("grad_norm", C.c_float), ("clip_coef", C.c_float),
+                ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("stop", C.c_int32), ("recorded", C.c_int32),
+                ("epochs", C.c_int32), ("stopped_epochs", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RoverHipError(RuntimeError):
@@ -250,6 +269,22 @@ def load():
     lib.rover_ppo_gae.argtypes = [C.POINTER(PpoHparams), vp, vp, vp, vp, i32, i32, vp, vp, vp]
     lib.rover_ppo_kl_schedule.argtypes = [C.POINTER(PpoHparams), vp, i32, vp, vp, vp]
     lib.rover_policy_unpack.argtypes = [C.POINTER(PolicyDesc), vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.rover_lift_policy_desc.argtypes = [C.POINTER(PolicyDesc), i32]
+    lib.rover_lift_ppo_default_hparams.argtypes = [C.POINTER(LiftPpoHparams)]
+    lib.rover_lift_ppo_hparams_bytes.restype = C.c_size_t
+    lib.rover_lift_ppo_state_bytes.restype = C.c_size_t
+    lib.rover_lift_ppo_param_floats.argtypes = [C.POINTER(PolicyDesc), C.POINTER(PolicyDesc)]
+    lib.rover_lift_ppo_param_floats.restype = C.c_size_t
+    lib.rover_lift_ppo_workspace_bytes.argtypes = [i32]
+    lib.rover_lift_ppo_workspace_bytes.restype = C.c_size_t
+    lib.rover_lift_ppo_scaler_doubles.argtypes = [i32]
+    lib.rover_lift_ppo_scaler_doubles.restype = C.c_size_t
+    lib.rover_lift_ppo_standardize.argtypes = [C.POINTER(LiftPpoHparams), vp, i32, vp, i32, i32, i32, vp, vp, C.c_size_t, vp]
+    lib.rover_lift_ppo_minibatch.argtypes = [C.POINTER(PolicyDesc), C.POINTER(PolicyDesc), C.POINTER(LiftPpoHparams), vp, vp, vp, vp,
+                                             vp, vp, vp, vp, vp, i32, i32, vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+    lib.rover_lift_ppo_apply.argtypes = [C.POINTER(PolicyDesc), C.POINTER(PolicyDesc), C.POINTER(LiftPpoHparams), vp, vp, vp, vp, vp,
+                                         vp, vp, i32, vp, C.c_size_t, vp]
+    lib.rover_lift_ppo_kl_schedule.argtypes = [C.POINTER(LiftPpoHparams), vp, i32, vp, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -267,6 +302,8 @@ def load():
         raise RoverHipError("struct rover_viewer_config of librover_hip.so does not match the Python mirror")
     if lib.rover_ppo_hparams_bytes() != C.sizeof(PpoHparams) or lib.rover_ppo_state_bytes() != C.sizeof(PpoState):
         raise RoverHipError("struct rover_ppo_hparams / rover_ppo_state of librover_hip.so does not match the Python mirror")
+    if lib.rover_lift_ppo_hparams_bytes() != C.sizeof(LiftPpoHparams) or lib.rover_lift_ppo_state_bytes() != C.sizeof(LiftPpoState):
+        raise RoverHipError("struct rover_lift_ppo_hparams / rover_lift_ppo_state of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib

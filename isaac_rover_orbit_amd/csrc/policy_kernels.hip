@@ -84,6 +84,12 @@ __device__ __forceinline__ float activate(float v, int act, float slope)
     if (act == ROVER_ACT_TANH) return rv_tanhf(v);
     return v;
 }
+// activate() plus ELU: the descriptor-driven kernel only (the reference-architecture kernels never see ELU, their code stays as it was)
+__device__ __forceinline__ float activate_any(float v, int act, float slope)
+{
+    if (act == ROVER_ACT_ELU) return v > 0.0f ? v : expm1f(v);   // rover_policy.h: expm1f, not expf(v) - 1
+    return activate(v, act, slope);
+}
 
 #ifdef POL_STAMP
 __device__ unsigned long long *g_pol_stamps = nullptr;
@@ -207,6 +213,7 @@ struct SplitKArgs {
     const float *arow_ptr;
 };
 // combine step of a split-K pass: thread -> (row, column) with the column fastest; 16 * nt columns starting at tile t0
+template <bool ANY_ACT = false>   // true: the descriptor-driven kernel (ELU allowed)
 __device__ __forceinline__ void split_k_combine(const SplitKArgs &A, int t0, int nt, int tid)
 {
     constexpr int ppitch = 16 * POL_MAXT + 4;
@@ -220,7 +227,7 @@ __device__ __forceinline__ void split_k_combine(const SplitKArgs &A, int t0, int
         for (int w = 0; w < POL_WAVES; ++w) q[w] = A.part[(w * POL_ROWS + r) * ppitch + c];
         const float sum = ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
         if (r < A.rows && col < A.N) {
-            const float v = activate(sum + A.bias[col], A.act, A.slope);
+            const float v = ANY_ACT ? activate_any(sum + A.bias[col], A.act, A.slope) : activate(sum + A.bias[col], A.act, A.slope);
             if (A.last) A.dst_out[r * A.dst_pitch + col] = v;
             else A.dst_act[r * A.dst_pitch + col] = v;
         }
@@ -262,7 +269,7 @@ __device__ __forceinline__ void split_k_layer(const SplitKArgs &A, int tid, int 
             case 5: pass(std::integral_constant<int, 5>{}); break;
             default: pass(std::integral_constant<int, 6>{}); break;
         }
-        split_k_combine(A, t0, nt, tid);
+        split_k_combine<true>(A, t0, nt, tid);
     }
 }
 
@@ -375,13 +382,14 @@ __global__ __launch_bounds__(POL_THREADS) void rover_policy_kernel(rover_policy_
 #pragma unroll
                                 for (int j = 0; j < 4; ++j)
                                     if (4 * akq + j < rows && 16 * (t0 + POL_WAVES * i) + arow < N)
-                                        pd[j * dst_pitch + 16 * POL_WAVES * i] = activate(acc[i][j] + bv[i], ACT, d.leaky_slope);
+                                        pd[j * dst_pitch + 16 * POL_WAVES * i] = activate_any(acc[i][j] + bv[i], ACT, d.leaky_slope);
                         };
                         if (last) stores(dst_out + pd_off);
                         else stores(dst_act + pd_off);
                     };
                     if (lay.act == ROVER_ACT_LEAKY_RELU) epi(std::integral_constant<int, ROVER_ACT_LEAKY_RELU>{});
                     else if (lay.act == ROVER_ACT_TANH) epi(std::integral_constant<int, ROVER_ACT_TANH>{});
+                    else if (lay.act == ROVER_ACT_ELU) epi(std::integral_constant<int, ROVER_ACT_ELU>{});
                     else epi(std::integral_constant<int, ROVER_ACT_NONE>{});
                 };
                 switch (nt) {
@@ -1033,7 +1041,7 @@ int check_desc(const rover_policy_desc *d)
         width = d->layers[i].N;
     }
     for (int i = 0; i < nl; ++i)
-        if (d->layers[i].act < 0 || d->layers[i].act > 2) return rover_internal_fail(ROVER_ERR_INVALID, "unknown activation");
+        if (d->layers[i].act < 0 || d->layers[i].act > ROVER_ACT_ELU) return rover_internal_fail(ROVER_ERR_INVALID, "unknown activation");
     return ROVER_OK;
 }
 
@@ -1059,6 +1067,21 @@ int rover_policy_default_desc(rover_policy_desc *d, int32_t out_dim, int32_t fin
     d->layers[0].split_k = 1;   // 307 KB of weights: a quarter per wave
     d->layers[5].split_k = 1;   // one column tile only
     d->layers[5].act = final_tanh ? ROVER_ACT_TANH : ROVER_ACT_NONE;
+    return ROVER_OK;
+}
+
+int rover_lift_policy_desc(rover_policy_desc *d, int32_t out_dim)
+{
+    if (!d || out_dim < 1) return rover_internal_fail(ROVER_ERR_INVALID, "bad argument");
+    memset(d, 0, sizeof(*d));
+    d->obs_dim = 36; d->prop_dim = 36;   // the lift observation (rover_lift.h), no encoder
+    d->n_enc = 0; d->n_mlp = 4; d->leaky_slope = 0.01f;
+    const int K[4] = {36, 256, 128, 64}, N[4] = {256, 128, 64, out_dim};
+    for (int i = 0; i < 4; ++i) {
+        d->layers[i].K = K[i]; d->layers[i].N = N[i];
+        d->layers[i].act = i < 3 ? ROVER_ACT_ELU : ROVER_ACT_NONE;
+        d->layers[i].split_k = 0;
+    }
     return ROVER_OK;
 }
 

@@ -30,14 +30,14 @@ class RoverNet:
     """
 
     def __init__(self, weights: Sequence, biases: Sequence, n_enc: int = 2, final_act: str = "tanh", obs_dim: int = 965,
-                 prop_dim: int = 4, leaky_slope: float = 0.01, device="cuda", n_copies: int = 4):
+                 prop_dim: int = 4, leaky_slope: float = 0.01, device="cuda", n_copies: int = 4, hidden_act: str = "leaky_relu"):
         if not torch.cuda.is_available():
             raise _lib.RoverHipError("RoverNet needs a ROCm GPU (no CPU fallback)")
         self._lib = _lib.load()
         self.device = torch.device(device)
         ws = [np.ascontiguousarray(torch.as_tensor(w).detach().cpu().numpy(), dtype=np.float32) for w in weights]
         bs = [np.ascontiguousarray(torch.as_tensor(b).detach().cpu().numpy(), dtype=np.float32) for b in biases]
-        self.desc = make_desc([w.shape for w in ws], n_enc, final_act, obs_dim, prop_dim, leaky_slope)
+        self.desc = make_desc([w.shape for w in ws], n_enc, final_act, obs_dim, prop_dim, leaky_slope, hidden_act)
         nl = len(ws)
         n_floats = int(self._lib.rover_policy_packed_floats(C.byref(self.desc)))
         packed = np.empty(n_floats, dtype=np.float32)
@@ -69,7 +69,7 @@ class RoverNet:
         return cls(ws, bs, n_enc=n_enc, final_act=final_act, **kw)
 
     @classmethod
-    def from_packed(cls, desc: "_lib.PolicyDesc", packed: torch.Tensor, n_copies: int, obs_dim: int = 965) -> "RoverNet":
+    def from_packed(cls, desc: "_lib.PolicyDesc", packed: torch.Tensor, n_copies: int, obs_dim: int | None = None) -> "RoverNet":
         """A network over an EXISTING device buffer of ``n_copies`` packed replicas (no copy, no host packing): the buffer is
         aliased, so whoever writes it (``ppo.FusedPPO`` after every optimiser step) changes what this network computes."""
         if not packed.is_cuda or packed.dtype != torch.float32 or not packed.is_contiguous():
@@ -84,7 +84,7 @@ class RoverNet:
         net.n_copies = int(n_copies)
         net.packed = packed
         net.out_dim = int(desc.layers[desc.n_enc + desc.n_mlp - 1].N)
-        net.obs_dim = obs_dim
+        net.obs_dim = int(desc.obs_dim) if obs_dim is None else obs_dim
         return net
 
     @classmethod
@@ -147,7 +147,13 @@ def forward_pair(net_a: RoverNet, net_b: RoverNet, obs: torch.Tensor, out_a: tor
     return out_a, out_b
 
 
-def make_desc(shapes, n_enc: int, final_act: str, obs_dim: int, prop_dim: int, leaky_slope: float) -> "_lib.PolicyDesc":
+HIDDEN_ACTS = {"leaky_relu": _lib.ACT_LEAKY_RELU, "elu": _lib.ACT_ELU, "tanh": _lib.ACT_TANH, "none": _lib.ACT_NONE}
+
+
+def make_desc(shapes, n_enc: int, final_act: str, obs_dim: int, prop_dim: int, leaky_slope: float,
+              hidden_act: str = "leaky_relu") -> "_lib.PolicyDesc":
+    """Descriptor of a network with the given (N, K) layer shapes: ``hidden_act`` after every layer but the last ("leaky_relu" for
+    the rover's networks, "elu" for the lift task's), ``final_act`` after the last; ``n_enc = 0``: the MLP reads obs[:, :prop_dim]."""
     nl = len(shapes)
     if nl > _lib.POLICY_MAX_LAYERS or nl - n_enc < 1:
         raise ValueError("unsupported number of layers")
@@ -160,9 +166,10 @@ def make_desc(shapes, n_enc: int, final_act: str, obs_dim: int, prop_dim: int, l
             raise ValueError(f"encoder width {d.enc_dim} does not match obs[:, {d.enc_offset}:-1] of a {obs_dim}-wide row")
     for i, (n, k) in enumerate(shapes):
         lay = d.layers[i]
-        lay.K, lay.N, lay.act = int(k), int(n), _lib.ACT_LEAKY_RELU
+        lay.K, lay.N, lay.act = int(k), int(n), HIDDEN_ACTS[hidden_act]
         # numerics contract (rover_policy.h): wide-K layers with few column tiles split K over the four waves
         tiles = (int(n) + 15) // 16
         lay.split_k = 1 if tiles <= 6 and (int(k) >= 512 or (tiles < 4 and int(k) >= 128)) else 0
     d.layers[nl - 1].act = {"tanh": _lib.ACT_TANH, "none": _lib.ACT_NONE}[final_act]
+
     return d

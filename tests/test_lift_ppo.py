@@ -1,0 +1,156 @@
+"""Lift-task PPO, CPU side: the float64 reference (tests/lift_ppo_reference.py) is pinned to the torch spec's loss, the torch
+RunningStandardScaler to a numpy restatement, the lift descriptor (ELU) packs and unpacks, and the sizes and refusals of the
+C ABI (include/rover_lift_train.h) hold."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from lift_ppo_reference import NumpyScaler, loss_and_grads
+
+
+def _nets(seed=0):
+    from isaac_rover_orbit_amd import lift_ppo as LP
+    torch.manual_seed(seed)
+    pol, val = LP.LiftMLP(8, log_std=True), LP.LiftMLP(1)
+    with torch.no_grad():
+        pol.log_std_parameter.copy_(torch.linspace(-0.5, 0.4, 8))
+    return pol, val
+
+
+def _lib():
+    from isaac_rover_orbit_amd import _lib as L, build
+    build.build_extension()
+    return L, L.load()
+
+
+def test_float64_reference_matches_the_torch_spec_loss():
+    from isaac_rover_orbit_amd import lift_ppo as LP
+    pol, val = _nets(1)
+    g = torch.Generator().manual_seed(2)
+    n = 300
+    s = torch.randn(n, 36, generator=g)
+    with torch.no_grad():
+        mean = pol(s)
+        a = mean + torch.randn(n, 8, generator=g) * 0.7
+        lp = LP.gaussian_logp(mean, pol.log_std_parameter, a) + 0.3 * torch.randn(n, generator=g)
+        oldv = val(s)[:, 0] + 0.4 * torch.randn(n, generator=g)
+    ret, adv = oldv + torch.randn(n, generator=g), torch.randn(n, generator=g)
+    pol64, val64 = pol.double(), val.double()
+    args64 = [x.double() for x in (s, a, lp, oldv, ret, adv)]
+    loss, kl, _, _ = LP.lift_ppo_loss(pol64, val64, *args64)
+    loss.backward()
+    ref_loss, ref_kl, grads = loss_and_grads(pol.state_dict(), val.state_dict(), *args64)
+    assert torch.allclose(loss.detach(), ref_loss, rtol=1e-12, atol=1e-12)
+    assert torch.allclose(kl, ref_kl, rtol=1e-12, atol=1e-12)
+    for name, p in pol64.named_parameters():
+        assert torch.allclose(p.grad, grads["policy"][name], rtol=1e-10, atol=1e-12), name
+    for name, p in val64.named_parameters():
+        assert torch.allclose(p.grad, grads["value"][name], rtol=1e-10, atol=1e-12), name
+
+
+def test_torch_scaler_matches_numpy_float64():
+    from isaac_rover_orbit_amd.lift_ppo import RunningStandardScaler
+    rng = np.random.RandomState(3)
+    ts, ns = RunningStandardScaler(36, device="cpu"), NumpyScaler(36)
+    for i in range(5):
+        x = (rng.randn(257 + 31 * i, 36) * rng.uniform(0.1, 20, 36) + rng.uniform(-10, 10, 36)).astype(np.float32)
+        x[0, 0] = 1e4                                        # a value outside the clamp
+        out = ts(torch.from_numpy(x), train=True).numpy()
+        ns.train(x)
+        np.testing.assert_allclose(ts.running_mean.numpy(), ns.mean, rtol=1e-6, atol=1e-6)
+        np.testing.assert_allclose(ts.running_variance.numpy(), ns.var, rtol=1e-5)
+        assert float(ts.current_count) == ns.count
+        np.testing.assert_allclose(out, ns.forward(x), rtol=1e-5, atol=1e-5)
+        assert out.max() <= 5.0 and out.min() >= -5.0
+        y = rng.randn(64, 36).astype(np.float32) * 4
+        np.testing.assert_allclose(ts(torch.from_numpy(y), inverse=True).numpy(), ns.inverse(y), rtol=1e-5, atol=1e-4)
+
+
+def test_lift_descriptor_packs_and_unpacks_with_zero_padding():
+    L, lib = _lib()
+    from isaac_rover_orbit_amd import lift_ppo as LP
+    pol, val = _nets(4)
+    for net, out_dim in ((pol, 8), (val, 1)):
+        sd = net.state_dict()
+        desc, packed = LP.pack(sd)
+        ref = L.PolicyDesc()
+        assert lib.rover_lift_policy_desc(C.byref(ref), out_dim) == 0
+        assert (ref.obs_dim, ref.prop_dim, ref.n_enc, ref.n_mlp) == (36, 36, 0, 4)
+        for i in range(4):
+            a, b = desc.layers[i], ref.layers[i]
+            assert (a.K, a.N, a.act, a.split_k) == (b.K, b.N, b.act, b.split_k)
+            assert a.act == (L.ACT_ELU if i < 3 else L.ACT_NONE)
+        back = LP.unpack(desc, packed)
+        for k, v in back.items():
+            assert torch.equal(v, sd[k]), k
+        used = np.zeros(packed.size, bool)
+        for i in range(4):
+            ly = desc.layers[i]
+            G = (ly.K + 15) // 16
+            n, k = np.meshgrid(np.arange(ly.N), np.arange(ly.K), indexing="ij")
+            pos = ly.w_off + ((((n >> 4) * G + (k >> 4)) * 64 + (n & 15) + 16 * (k & 3)) << 2) + ((k >> 2) & 3)
+            used[pos.ravel()] = True
+            used[ly.b_off:ly.b_off + ly.N] = True
+        assert np.all(packed[~used] == 0.0)
+
+
+def test_elu_is_accepted_by_the_descriptor_check():
+    L, lib = _lib()
+    from isaac_rover_orbit_amd import lift_ppo as LP
+    pol, _ = _nets(5)
+    desc, packed = LP.pack(pol.state_dict())                  # rover_policy_pack runs the descriptor check
+    assert packed.size == lib.rover_policy_packed_floats(C.byref(desc))
+    bad = L.PolicyDesc()
+    lib.rover_lift_policy_desc(C.byref(bad), 8)
+    bad.layers[0].act = 4
+    ws = [np.zeros((bad.layers[i].N, bad.layers[i].K), np.float32) for i in range(4)]
+    bs = [np.zeros(bad.layers[i].N, np.float32) for i in range(4)]
+    wp = (C.c_void_p * 4)(*[w.ctypes.data for w in ws])
+    bp = (C.c_void_p * 4)(*[b.ctypes.data for b in bs])
+    out = np.empty(packed.size, np.float32)
+    assert lib.rover_policy_pack(C.byref(bad), wp, bp, out.ctypes.data) == 1
+    assert b"unknown activation" in lib.rover_last_error()
+
+
+def test_sizes_and_refusals():
+    L, lib = _lib()
+    from isaac_rover_orbit_amd import lift_ppo as LP
+    pol, val = _nets(6)
+    dp, pa = LP.pack(pol.state_dict())
+    dv, pv = LP.pack(val.state_dict())
+    assert (pa.size, pv.size) == (54728, 54724)
+    assert lib.rover_lift_ppo_param_floats(C.byref(dp), C.byref(dv)) == pa.size + pv.size + 8
+    assert lib.rover_lift_ppo_param_floats(C.byref(dv), C.byref(dp)) == 0           # swapped roles
+    assert lib.rover_lift_ppo_workspace_bytes(0) == 0
+    assert lib.rover_lift_ppo_workspace_bytes(4096) == 4 * (512 + 2 * 940 * 4096 + 16 * 256)
+    assert lib.rover_lift_ppo_scaler_doubles(36) == 73 and lib.rover_lift_ppo_scaler_doubles(1) == 3
+    assert lib.rover_lift_ppo_scaler_doubles(0) == 0 and lib.rover_lift_ppo_scaler_doubles(65) == 0
+    assert lib.rover_lift_ppo_hparams_bytes() == C.sizeof(L.LiftPpoHparams) == 76
+    assert lib.rover_lift_ppo_state_bytes() == C.sizeof(L.LiftPpoState) == 48
+    h = LP.default_hparams()
+    assert (h.value_loss_scale, h.max_grad_norm, h.kl_early_stop, h.reward_scale, h.scaler_clip) == \
+        (2.0, 1.0, pytest.approx(0.008), pytest.approx(0.01), 5.0)
+    # the rover pair is refused by the lift entries, the lift pair by the rover entries (host-side checks, no GPU needed)
+    rp, rv = L.PolicyDesc(), L.PolicyDesc()
+    lib.rover_policy_default_desc(C.byref(rp), 2, 1)
+    lib.rover_policy_default_desc(C.byref(rv), 1, 0)
+    assert lib.rover_lift_ppo_param_floats(C.byref(rp), C.byref(rv)) == 0
+    assert lib.rover_ppo_param_floats(C.byref(dp), C.byref(dv)) == 0
+    vp = C.c_void_p(16)
+    assert lib.rover_lift_ppo_minibatch(C.byref(rp), C.byref(rv), C.byref(h), vp, vp, vp, vp, vp, vp, vp, vp, vp, 16, 0, vp, vp, 1 << 30,
+                                        vp, vp, None, None, None) == 4
+    assert lib.rover_lift_ppo_apply(C.byref(rp), C.byref(rv), C.byref(h), vp, vp, vp, vp, vp, None, None, 1, vp, 1 << 30, None) == 4
+    hr = L.PpoHparams()
+    lib.rover_ppo_default_hparams(C.byref(hr))
+    assert lib.rover_ppo_minibatch(C.byref(dp), C.byref(dv), C.byref(hr), vp, vp, vp, vp, vp, vp, vp, vp, 16, vp, 1 << 30, vp, vp,
+                                   None, None, None) == 4
+    assert lib.rover_ppo_apply(C.byref(dp), C.byref(dv), C.byref(hr), vp, vp, vp, vp, vp, None, None, 1, vp, 1 << 30, None) == 4
+    # bad arguments of the lift entries
+    assert lib.rover_lift_ppo_standardize(None, vp, 36, vp, 10, 0, 0, vp, None, 0, None) == 1
+    assert lib.rover_lift_ppo_standardize(C.byref(h), vp, 0, vp, 10, 0, 0, vp, None, 0, None) == 1
+    assert lib.rover_lift_ppo_standardize(C.byref(h), vp, 36, vp, 1, 1, 0, vp, vp, 1 << 30, None) == 1      # train needs 2 rows
+    assert lib.rover_lift_ppo_minibatch(C.byref(dp), C.byref(dv), C.byref(h), vp, vp, vp, vp, vp, vp, vp, vp, vp, 0, 0, vp, vp, 1 << 30,
+                                        vp, vp, None, None, None) == 1
+    assert lib.rover_lift_ppo_kl_schedule(C.byref(h), vp, 0, vp, None, None) == 1
