@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Minimal TRPO on the HIP-backed AAURoverEnv-v0: the reference's rover_trpo.yaml (rollouts 60, 4 value epochs of 60
+mini-batches, gamma 0.99, lambda 0.95, max KL 0.01, damping 0.1, 10 CG steps, 10 backtracking steps, value lr 1e-3,
+value grad-norm 0.5) on the actor / critic of examples/04_train_ppo.py (imported: ``Net``).  The rollout is 04's: policy mean
+and value through ``RoverNet``, env.step on the fused kernels.  The update is the torch spec
+``isaac_rover_orbit_amd.trpo.TorchTRPO`` (``--update torch``, the default) or the fused HIP update ``FusedTRPO``
+(``--update fused``: GAE, surrogate gradient, Fisher-vector products, CG, line search and the value regression as HIP kernels).
+
+    python examples/06_train_trpo.py --num_envs 4096 --iterations 60 --update fused --out trpo.jsonl
+"""
+import argparse
+import importlib.util
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from isaac_rover_orbit_amd import terrain as T  # noqa: E402
+from isaac_rover_orbit_amd.cfg import RoverEnvCfg  # noqa: E402
+from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
+from isaac_rover_orbit_amd.policy import RoverNet  # noqa: E402
+from isaac_rover_orbit_amd.trpo import FusedTRPO, TorchTRPO  # noqa: E402
+
+_spec = importlib.util.spec_from_file_location("train_ppo_example", os.path.join(ROOT, "examples", "04_train_ppo.py"))
+ppo_example = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(ppo_example)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--num_envs", type=int, default=4096)
+    ap.add_argument("--iterations", type=int, default=60)
+    ap.add_argument("--rollouts", type=int, default=60)
+    ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--out", default=None, help="write the per-iteration statistics as JSON lines")
+    ap.add_argument("--save", default=None, help="write a skrl-style checkpoint {'policy': state_dict, 'value': state_dict}")
+    ap.add_argument("--update", choices=("torch", "fused"), default="torch",
+                    help="TRPO update: the torch spec (TorchTRPO) or the fused HIP kernels (FusedTRPO)")
+    args = ap.parse_args()
+    torch.manual_seed(args.seed)
+    dev = torch.device("cuda")
+    n, Tn = args.num_envs, args.rollouts
+    terrain = T.make_procedural_terrain((2048, 2048), seed=1234)
+    terrain.make_spawns(2 * n)
+    cfg = RoverEnvCfg(); cfg.scene.num_envs = n; cfg.terrain.kind = "custom"
+    env = RoverEnv(cfg, terrain=terrain)
+    policy, value = ppo_example.Net(2, True).to(dev), ppo_example.Net(1, False).to(dev)
+    spec = fused = None
+    if args.update == "fused":
+        fused = FusedTRPO(policy.state_dict(), value.state_dict())
+    else:
+        spec = TorchTRPO(policy, value)
+    gamma, lam = ppo_example.GAMMA, ppo_example.LAM
+
+    obs_buf = torch.empty(Tn, n, 965, device=dev)
+    act_buf = torch.empty(Tn, n, 2, device=dev)
+    logp_buf, val_buf, rew_buf = (torch.empty(Tn, n, device=dev) for _ in range(3))
+    done_buf = torch.empty(Tn, n, device=dev)
+    obs, _ = env.reset()
+    o = torch.nan_to_num(obs["policy"], neginf=0.0)
+    out = open(args.out, "w") if args.out else None
+    B = Tn * n
+    for it in range(args.iterations):
+        t0 = time.perf_counter()
+        # ---- rollout on the fused kernels (examples/04_train_ppo.py)
+        if fused is None:
+            actor = RoverNet.from_state_dict(policy.state_dict(), final_act="tanh")
+            critic = RoverNet.from_state_dict(value.state_dict(), final_act="none")
+            log_std = policy.log_std_parameter.detach().clamp(-20.0, 2.0)
+        else:
+            actor, critic = fused.actor, fused.critic
+            log_std = fused.log_std.clamp(-20.0, 2.0)
+        std = log_std.exp()
+        ep_count = torch.zeros((), device=dev); ep_stats = torch.zeros(4, device=dev)
+        for t in range(Tn):
+            mean = actor(o)
+            a = mean + std * torch.randn_like(mean)
+            logp_buf[t] = (-0.5 * ((a - mean) / std) ** 2 - log_std - 0.9189385332).sum(1)
+            val_buf[t] = critic(o).squeeze(1)
+            obs_buf[t], act_buf[t] = o, a
+            obs, rew, term, trunc, info = env.step(a.clamp(-1.0, 1.0))
+            o = torch.nan_to_num(obs["policy"], neginf=0.0)
+            rew_buf[t], done_buf[t] = rew, (term | trunc).float()
+            lv = env.episode_log_vector
+            ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
+        torch.cuda.synchronize(); t_roll = time.perf_counter() - t0
+        perms = [torch.randperm(B, device=dev) for _ in range(4)]
+        with torch.no_grad():
+            last_v = critic(o).squeeze(1)
+            if fused is not None:
+                adv, ret = fused.gae(rew_buf, done_buf, val_buf, last_v)
+            else:
+                adv = torch.zeros_like(rew_buf); gae = torch.zeros(n, device=dev)
+                for t in reversed(range(Tn)):
+                    nv = last_v if t == Tn - 1 else val_buf[t + 1]
+                    nd = 1.0 - done_buf[t]
+                    delta = rew_buf[t] + gamma * nv * nd - val_buf[t]
+                    gae = delta + gamma * lam * nd * gae
+                    adv[t] = gae
+                ret = adv + val_buf
+            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+        t1 = time.perf_counter()
+        flat = [x.reshape(B, *x.shape[2:]) for x in (obs_buf, act_buf, logp_buf, ret, adv)]
+        trpo = (fused or spec).update(*flat, perms=perms)
+        torch.cuda.synchronize(); t_upd = time.perf_counter() - t1
+        st = {"iteration": it, "mean_step_reward": rew_buf.mean().item(), "episodes": ep_count.item(),
+              "time_out": ep_stats[0].item(), "success": ep_stats[1].item(), "far": ep_stats[2].item(),
+              "collision": ep_stats[3].item(), **trpo, "rollout_s": t_roll, "rollout_env_steps_per_s": Tn * n / t_roll,
+              "update_s": t_upd, "iteration_s": time.perf_counter() - t0}
+        print(json.dumps(st), flush=True)
+        if out:
+            out.write(json.dumps(st) + "\n"); out.flush()
+    if args.save:
+        torch.save(fused.state_dict() if fused is not None else {"policy": policy.state_dict(), "value": value.state_dict()}, args.save)
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

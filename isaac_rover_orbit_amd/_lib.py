@@ -42,6 +42,9 @@ EXPORTS = [
     "rover_lift_ppo_default_hparams", "rover_lift_ppo_hparams_bytes", "rover_lift_ppo_state_bytes",  # rover_lift_train.h
     "rover_lift_ppo_param_floats", "rover_lift_ppo_workspace_bytes", "rover_lift_ppo_scaler_doubles", "rover_lift_ppo_standardize",
     "rover_lift_ppo_minibatch", "rover_lift_ppo_apply", "rover_lift_ppo_kl_schedule",
+    "rover_trpo_default_hparams", "rover_trpo_hparams_bytes", "rover_trpo_state_bytes", "rover_trpo_param_floats",  # rover_trpo.h
+    "rover_trpo_workspace_bytes", "rover_trpo_policy_grad", "rover_trpo_fvp", "rover_trpo_policy_step", "rover_trpo_value_minibatch",
+    "rover_trpo_value_apply",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -88,6 +91,24 @@ class LiftPpoState(C.Structure):
     _fields_ = [("lr", C.c_double), ("step", C.c_int32), ("grad_norm", C.c_float), ("clip_coef", C.c_float),
                 ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("stop", C.c_int32), ("recorded", C.c_int32),
                 ("epochs", C.c_int32), ("stopped_epochs", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TrpoHparams(C.Structure):
+    """Mirror of ``struct rover_trpo_hparams`` (include/rover_trpo.h)."""
+    _fields_ = [("gamma", C.c_float), ("lam", C.c_float), ("value_loss_scale", C.c_float), ("log_std_min", C.c_float),
+                ("log_std_max", C.c_float), ("max_grad_norm", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("value_lr", C.c_float), ("damping", C.c_float), ("max_kl", C.c_float), ("cg_tol", C.c_float),
+                ("accept_ratio", C.c_float), ("step_fraction", C.c_float), ("cg_steps", C.c_int32), ("max_backtrack", C.c_int32)]
+
+
+class TrpoState(C.Structure):
+    """Mirror of ``struct rover_trpo_state`` (include/rover_trpo.h; it lives in device memory)."""
+    _fields_ = [("cg_done", C.c_int32), ("ls_done", C.c_int32), ("accepted", C.c_int32), ("cg_iters", C.c_int32),
+                ("trials", C.c_int32), ("value_step", C.c_int32), ("value_batches", C.c_int32), ("reserved0", C.c_int32),
+                ("loss_old", C.c_float), ("loss_new", C.c_float), ("rr_old", C.c_float), ("rr", C.c_float), ("cg_alpha", C.c_float),
+                ("cg_beta", C.c_float), ("xhx", C.c_float), ("step", C.c_float), ("expected", C.c_float), ("kl", C.c_float),
+                ("value_loss_sum", C.c_float), ("grad_norm", C.c_float), ("clip_coef", C.c_float), ("step_size", C.c_float),
+                ("bc2_sqrt", C.c_float), ("reserved1", C.c_float)]
 
 
 class RoverHipError(RuntimeError):
@@ -285,6 +306,19 @@ def load():
     lib.rover_lift_ppo_apply.argtypes = [C.POINTER(PolicyDesc), C.POINTER(PolicyDesc), C.POINTER(LiftPpoHparams), vp, vp, vp, vp, vp,
                                          vp, vp, i32, vp, C.c_size_t, vp]
     lib.rover_lift_ppo_kl_schedule.argtypes = [C.POINTER(LiftPpoHparams), vp, i32, vp, vp, vp]
+    lib.rover_trpo_default_hparams.argtypes = [C.POINTER(TrpoHparams)]
+    lib.rover_trpo_hparams_bytes.restype = C.c_size_t
+    lib.rover_trpo_state_bytes.restype = C.c_size_t
+    lib.rover_trpo_param_floats.argtypes = [C.POINTER(PolicyDesc), C.POINTER(PolicyDesc)]
+    lib.rover_trpo_param_floats.restype = C.c_size_t
+    lib.rover_trpo_workspace_bytes.argtypes = [i32, i32]
+    lib.rover_trpo_workspace_bytes.restype = C.c_size_t
+    pd, th = C.POINTER(PolicyDesc), C.POINTER(TrpoHparams)
+    lib.rover_trpo_policy_grad.argtypes = [pd, pd, th, vp, vp, vp, vp, vp, i32, vp, C.c_size_t, vp, vp, vp]
+    lib.rover_trpo_fvp.argtypes = [pd, pd, th, vp, vp, i32, vp, C.c_size_t, vp, vp, vp]
+    lib.rover_trpo_policy_step.argtypes = [pd, pd, th, vp, vp, vp, vp, vp, i32, vp, C.c_size_t, vp, vp, i32, vp, vp, vp]
+    lib.rover_trpo_value_minibatch.argtypes = [pd, pd, th, vp, vp, vp, vp, i32, i32, vp, C.c_size_t, vp, vp, vp]
+    lib.rover_trpo_value_apply.argtypes = [pd, pd, th, vp, vp, vp, vp, vp, vp, i32, vp, C.c_size_t, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -304,6 +338,8 @@ def load():
         raise RoverHipError("struct rover_ppo_hparams / rover_ppo_state of librover_hip.so does not match the Python mirror")
     if lib.rover_lift_ppo_hparams_bytes() != C.sizeof(LiftPpoHparams) or lib.rover_lift_ppo_state_bytes() != C.sizeof(LiftPpoState):
         raise RoverHipError("struct rover_lift_ppo_hparams / rover_lift_ppo_state of librover_hip.so does not match the Python mirror")
+    if lib.rover_trpo_hparams_bytes() != C.sizeof(TrpoHparams) or lib.rover_trpo_state_bytes() != C.sizeof(TrpoState):
+        raise RoverHipError("struct rover_trpo_hparams / rover_trpo_state of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib
