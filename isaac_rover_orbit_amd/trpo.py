@@ -88,8 +88,9 @@ def gauss_newton_fvp(policy, states, vector, damping=0.1):
     return torch.cat(out) + damping * vector
 
 
-def conjugate_gradient(fvp, b, num_iterations=10, residual_tolerance=1e-10):
-    """skrl TRPO._update.conjugate_gradient; returns (x, iterations run, final r.r)."""
+def conjugate_gradient(fvp, b, num_iterations=10, residual_tolerance=1e-10, trace: list | None = None):
+    """skrl TRPO._update.conjugate_gradient; returns (x, iterations run, final r.r).  ``trace`` (a list) receives r.r after
+    each iteration."""
     x = torch.zeros_like(b)
     r = b.clone()
     p = b.clone()
@@ -101,6 +102,8 @@ def conjugate_gradient(fvp, b, num_iterations=10, residual_tolerance=1e-10):
         x += alpha * p
         r -= alpha * hv
         rr_new = torch.dot(r, r)
+        if trace is not None:
+            trace.append(float(rr_new))
         if rr_new < residual_tolerance:
             break
         p = r + rr_new / rr_old * p
@@ -290,10 +293,15 @@ class FusedTRPO:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _ensure_ws(self, rows: int, mb: int = 1):
+        """Grow the workspace to (rows, mb).  The old bytes are carried over (on the stream of the kernels): the policy region
+        sits at a fixed offset and its layout depends on the caller's B only, so the theta_old cache ``fvp`` reads survives a
+        growth by ``value_minibatch`` between ``policy_grad`` and ``fvp``."""
         rows, mb = max(rows, self._ws_shape[0]), max(mb, self._ws_shape[1])
         if (rows, mb) != self._ws_shape:
             need = int(self._lib.rover_trpo_workspace_bytes(rows, mb))
-            self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws[:self.ws.numel()].copy_(self.ws)
+            self.ws = ws
             self._ws_shape = (rows, mb)
 
     @staticmethod

@@ -126,21 +126,32 @@ def _grads_of(tr):
 
 @pytest.mark.parametrize("log_std", [[-0.5, 0.2, 0.0, -1.0, 0.4, -0.2, 0.1, 2.5]])
 def test_gradients_match_float64_autograd(log_std):
+    _gradient_case(4096, log_std)
+
+
+@pytest.mark.parametrize("n", [1, 17, 4099])
+def test_gradients_match_float64_autograd_at_ragged_rows(n):
+    """The same bound at minibatches that end in a ragged 16-row workgroup; the clamped log_std's gradient stays exactly 0."""
+    _gradient_case(n, [-0.5, 0.2, 0.0, -1.0, 0.4, -0.2, 0.1, 2.5])
+
+
+def _gradient_case(n, log_std):
     from isaac_rover_orbit_amd import lift_ppo as LP
     pol, val = _nets(2, log_std=log_std)                              # log_std[7] = 2.5: clamped, no gradient
-    B, n = 8192, 4096
+    B = 8192
     obs, act, logp, oldv, ret, adv = _rollout(pol, val, B, seed=3)
     tr = _trainer(pol, val)
     idx = torch.randperm(B, device=DEV)[:n].contiguous()
     tr.minibatch(obs, act, logp, oldv, ret, adv, idx)
     s = tr.standardize(obs[idx].contiguous(), "state")
-    with torch.no_grad():                                             # every clip branch is crossed
-        lp = LP.gaussian_logp(pol(s), pol.log_std_parameter, act[idx])
-        r = (lp - logp[idx]).exp()
-        dv = val(s)[:, 0] - oldv[idx]
-    for side in (r < 0.8, r > 1.2):
-        assert int((side & (adv[idx] > 0)).sum()) > 10 and int((side & (adv[idx] < 0)).sum()) > 10
-    assert int((dv > 0.2).sum()) > 10 and int((dv < -0.2).sum()) > 10
+    if n == 4096:
+        with torch.no_grad():                                         # every clip branch is crossed
+            lp = LP.gaussian_logp(pol(s), pol.log_std_parameter, act[idx])
+            r = (lp - logp[idx]).exp()
+            dv = val(s)[:, 0] - oldv[idx]
+        for side in (r < 0.8, r > 1.2):
+            assert int((side & (adv[idx] > 0)).sum()) > 10 and int((side & (adv[idx] < 0)).sum()) > 10
+        assert int((dv > 0.2).sum()) > 10 and int((dv < -0.2).sum()) > 10
     args = (s, act[idx], logp[idx], oldv[idx], ret[idx], adv[idx])
     _, _, ref = loss_and_grads(pol.state_dict(), val.state_dict(), *args)
     _, _, t32 = loss_and_grads(pol.state_dict(), val.state_dict(), *args, dtype=torch.float32)
@@ -151,7 +162,9 @@ def test_gradients_match_float64_autograd(log_std):
             e_f = float((fused[role][k].double() - g64).norm())
             e_t = float((t32[role][k].double().cpu() - g64).norm())
             assert e_f <= 4 * e_t + 1e-6 * float(g64.norm()), (role, k, e_f, e_t, float(g64.norm()))
-    assert fused["policy"]["log_std_parameter"][7] == 0.0 and fused["policy"]["log_std_parameter"][0] != 0.0
+    assert fused["policy"]["log_std_parameter"][7] == 0.0
+    if n == 4096:
+        assert fused["policy"]["log_std_parameter"][0] != 0.0
 
 
 def test_kl_early_stop_skips_the_rest_of_the_epoch():

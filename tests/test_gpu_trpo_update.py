@@ -4,62 +4,9 @@ inputs; the step and the accepted trial equal the spec's; runs are bit-reproduci
 import pytest
 import torch
 
-from ppo_reference import load_example
+from trpo_helpers import DEV, _check, _copy, _err, _flat_to_sd, _nets, _rollout, _spec_step, _trainer
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-
-
-def _nets(seed=0, log_std=(-0.4, 0.3)):
-    ex = load_example()
-    torch.manual_seed(seed)
-    pol, val = ex.Net(2, True), ex.Net(1, False)
-    with torch.no_grad():
-        pol.log_std_parameter.copy_(torch.tensor(log_std))
-    return pol.to(DEV), val.to(DEV)
-
-
-def _rollout(pol, B, seed=1):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    obs = torch.randn(B, 965, device=DEV, generator=g) * 0.5
-    with torch.no_grad():
-        mean = torch.cat([pol(obs[i:i + 8192]) for i in range(0, B, 8192)])
-        ls = pol.log_std_parameter.clamp(-20.0, 2.0)
-        act = mean + ls.exp() * torch.randn(B, 2, device=DEV, generator=g)
-        lp = (-0.5 * ((act - mean) / ls.exp()) ** 2 - ls - 0.9189385332).sum(1)
-    logp = (lp + 0.05 * torch.randn(B, device=DEV, generator=g)).contiguous()
-    adv = torch.randn(B, device=DEV, generator=g)
-    adv = ((adv - adv.mean()) / (adv.std() + 1e-8)).contiguous()
-    ret = torch.randn(B, device=DEV, generator=g)
-    return obs, act.contiguous(), logp, ret, adv
-
-
-def _copy(net, dtype):
-    import copy
-    return copy.deepcopy(net).to(dtype)
-
-
-def _flat_to_sd(net, flat):
-    out, i = {}, 0
-    for k, p in net.named_parameters():
-        out[k] = flat[i:i + p.numel()].view_as(p)
-        i += p.numel()
-    return out
-
-
-def _err(a, ref):
-    return float((a.double().cpu() - ref.double().cpu()).norm())
-
-
-def _check(fused_sd, sd64, sd32, factor=4.0, floor=1e-5):
-    for k, ref in sd64.items():
-        e_f, e_t = _err(fused_sd[k], ref), _err(sd32[k], ref)
-        assert e_f <= factor * e_t + floor * float(ref.double().norm()) + 1e-30, (k, e_f, e_t, float(ref.norm()))
-
-
-def _trainer(pol, val, **kw):
-    from isaac_rover_orbit_amd.trpo import FusedTRPO
-    return FusedTRPO(pol.state_dict(), val.state_dict(), **kw)
 
 
 @pytest.mark.parametrize("log_std", [(-0.4, 0.3), (2.5, -0.3)])
@@ -97,13 +44,6 @@ def test_fvp_matches_float64(log_std):
             v = torch.cat([vsd[k].reshape(-1) for k, _ in p.named_parameters()]).to(DEV, dt)
             ref[dt] = _flat_to_sd(p, fisher_vector_product(p, obs.to(dt), v, 0.1).detach())
         _check(out, ref[torch.float64], ref[torch.float32])
-
-
-def _spec_step(pol, val, obs, act, logp, adv, dtype, **hp):
-    from isaac_rover_orbit_amd.trpo import TorchTRPO
-    p, v = _copy(pol, dtype), _copy(val, dtype)
-    st = TorchTRPO(p, v, **hp).policy_step(obs.to(dtype), act.to(dtype), logp.to(dtype), adv.to(dtype))
-    return p, st
 
 
 def test_policy_step_matches_spec():
