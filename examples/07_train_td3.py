@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""Minimal TD3 on the HIP-backed AAURoverEnv-v0: the reference's learning/train/td3.py with rover_td3.yaml (batch 4096, actor
+and critic lr 1e-4, RandomMemory of 2 x batch slots, one gradient step per env step, policy delay 2, polyak 0.005) on the actor
+of examples/04_train_ppo.py (``Net(2, False)``, imported) and two Q(s, a) critics (``isaac_rover_orbit_amd.td3.Critic``).
+Transitions live in ``td3.ReplayMemory``, one observation ring.  The update is the torch spec ``TorchTD3``
+(``--update torch``, the default) or the fused HIP update ``FusedTD3`` (``--update fused``).
+
+Every env step: the actor forward (``FusedTD3.actor`` on the fused kernels, or the torch actor), optional exploration noise,
+env.step with those actions, memory.add of the same actions, then one gradient step on a batch drawn from the memory.
+
+    python examples/07_train_td3.py --num_envs 4096 --timesteps 2000 --update fused --out td3.jsonl
+"""
+import argparse
+import importlib.util
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from isaac_rover_orbit_amd import terrain as T  # noqa: E402
+from isaac_rover_orbit_amd.cfg import RoverEnvCfg  # noqa: E402
+from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
+from isaac_rover_orbit_amd.td3 import (HPARAMS, Critic, FusedTD3, ReplayMemory, TorchTD3, exploration_scale,  # noqa: E402
+                                       explore)
+
+_spec = importlib.util.spec_from_file_location("train_ppo_example", os.path.join(ROOT, "examples", "04_train_ppo.py"))
+ppo_example = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(ppo_example)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--num_envs", type=int, default=4096)
+    ap.add_argument("--timesteps", type=int, default=1000)
+    ap.add_argument("--batch_size", type=int, default=HPARAMS["batch_size"])
+    ap.add_argument("--memory_size", type=int, default=None, help="memory slots (default 2 x batch_size, as the reference)")
+    ap.add_argument("--exploration_noise", type=float, default=0.0,
+                    help="std of Gaussian exploration noise with skrl's linear scale schedule (default 0: none, as rover_td3.yaml)")
+    ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--log_every", type=int, default=50, help="env steps per logged line (the fused path syncs only then)")
+    ap.add_argument("--out", default=None, help="write the logged statistics as JSON lines")
+    ap.add_argument("--save", default=None, help="write a skrl-style TD3 checkpoint (policy, target_policy, critic_1, ...)")
+    ap.add_argument("--update", choices=("torch", "fused"), default="torch",
+                    help="TD3 update: the torch spec (TorchTD3) or the fused HIP kernels (FusedTD3)")
+    args = ap.parse_args()
+    torch.manual_seed(args.seed)
+    dev = torch.device("cuda")
+    n, M = args.num_envs, args.memory_size or 2 * args.batch_size
+    print(json.dumps({"memory_slots": M, "num_envs": n, "memory_gb": ReplayMemory.nbytes(M, n) / 1e9,
+                      "two_buffer_memory_gb": ReplayMemory.two_buffer_nbytes(M, n) / 1e9}), flush=True)
+    terrain = T.make_procedural_terrain((2048, 2048), seed=1234)
+    terrain.make_spawns(2 * n)
+    cfg = RoverEnvCfg(); cfg.scene.num_envs = n; cfg.terrain.kind = "custom"
+    env = RoverEnv(cfg, terrain=terrain)
+    policy, critic_1, critic_2 = ppo_example.Net(2, False).to(dev), Critic().to(dev), Critic().to(dev)
+    memory = ReplayMemory(M, n, device=dev)
+    fused = spec = None
+    if args.update == "fused":
+        fused = FusedTD3(policy.state_dict(), critic_1.state_dict(), critic_2.state_dict())
+    else:
+        spec = TorchTD3(policy, critic_1, critic_2)
+    gen = torch.Generator(device=dev).manual_seed(args.seed)
+    obs, _ = env.reset()
+    o = torch.nan_to_num(obs["policy"], neginf=0.0)
+    out = open(args.out, "w") if args.out else None
+    t_log, steps_log, last = time.perf_counter(), 0, {}
+    ep_count = torch.zeros((), device=dev); ep_stats = torch.zeros(4, device=dev)
+    for step in range(args.timesteps):
+        with torch.no_grad():
+            a = fused.actor(o) if fused is not None else spec.act(o)
+        if args.exploration_noise > 0:
+            scale = exploration_scale(step, args.timesteps, HPARAMS["exploration_initial_scale"], HPARAMS["exploration_final_scale"])
+            a = explore(a, args.exploration_noise * torch.randn(a.shape, device=dev, generator=gen), scale)
+        obs, rew, term, trunc, info = env.step(a)
+        o_next = torch.nan_to_num(obs["policy"], neginf=0.0)
+        memory.add(o, a, rew, o_next, term)
+        o = o_next
+        lv = env.episode_log_vector
+        ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
+        idx = memory.sample_indices(args.batch_size, gen)
+        if fused is not None:
+            fused.update(memory, idx)
+        else:
+            last = spec.update(memory, idx)
+        steps_log += 1
+        if (step + 1) % args.log_every == 0 or step + 1 == args.timesteps:
+            if fused is not None:
+                s = fused.stats()
+                last = {k: s[k] for k in ("critic_loss", "q1_mean", "q2_mean", "y_mean", "policy_loss", "critic_step", "actor_step")}
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t_log
+            st = {"timestep": step + 1, "memory_rows": len(memory), **{k: v for k, v in last.items() if k != "actor_stepped"},
+                  "episodes": ep_count.item(), "time_out": ep_stats[0].item(), "success": ep_stats[1].item(),
+                  "far": ep_stats[2].item(), "collision": ep_stats[3].item(), "env_steps_per_s": steps_log * n / dt}
+            print(json.dumps(st), flush=True)
+            if out:
+                out.write(json.dumps(st) + "\n"); out.flush()
+            t_log, steps_log = time.perf_counter(), 0
+    if args.save:
+        torch.save(fused.state_dict() if fused is not None else spec.checkpoint(), args.save)
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

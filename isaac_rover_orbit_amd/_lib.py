@@ -45,6 +45,9 @@ EXPORTS = [
     "rover_trpo_default_hparams", "rover_trpo_hparams_bytes", "rover_trpo_state_bytes", "rover_trpo_param_floats",  # rover_trpo.h
     "rover_trpo_workspace_bytes", "rover_trpo_policy_grad", "rover_trpo_fvp", "rover_trpo_policy_step", "rover_trpo_value_minibatch",
     "rover_trpo_value_apply",
+    "rover_td3_default_hparams", "rover_td3_hparams_bytes", "rover_td3_state_bytes", "rover_td3_critic_desc",  # rover_td3.h
+    "rover_td3_critic_pack", "rover_td3_param_floats", "rover_td3_workspace_bytes", "rover_td3_critic_step", "rover_td3_actor_step",
+    "rover_td3_polyak",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -109,6 +112,20 @@ class TrpoState(C.Structure):
                 ("cg_beta", C.c_float), ("xhx", C.c_float), ("step", C.c_float), ("expected", C.c_float), ("kl", C.c_float),
                 ("value_loss_sum", C.c_float), ("grad_norm", C.c_float), ("clip_coef", C.c_float), ("step_size", C.c_float),
                 ("bc2_sqrt", C.c_float), ("reserved1", C.c_float)]
+
+
+class Td3Hparams(C.Structure):
+    """Mirror of ``struct rover_td3_hparams`` (include/rover_td3.h)."""
+    _fields_ = [("gamma", C.c_float), ("polyak", C.c_float), ("actor_lr", C.c_float), ("critic_lr", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float), ("noise_clip", C.c_float), ("act_min", C.c_float), ("act_max", C.c_float)]
+
+
+class Td3State(C.Structure):
+    """Mirror of ``struct rover_td3_state`` (include/rover_td3.h; it lives in device memory)."""
+    _fields_ = [("critic_step", C.c_int32), ("actor_step", C.c_int32), ("critic_updates", C.c_int32), ("bad_index", C.c_int32),
+                ("critic_loss", C.c_float), ("policy_loss", C.c_float), ("q1_mean", C.c_float), ("q2_mean", C.c_float),
+                ("y_mean", C.c_float), ("critic_step_size", C.c_float), ("critic_bc2_sqrt", C.c_float), ("actor_step_size", C.c_float),
+                ("actor_bc2_sqrt", C.c_float), ("reserved", C.c_float * 3)]
 
 
 class RoverHipError(RuntimeError):
@@ -319,6 +336,21 @@ def load():
     lib.rover_trpo_policy_step.argtypes = [pd, pd, th, vp, vp, vp, vp, vp, i32, vp, C.c_size_t, vp, vp, i32, vp, vp, vp]
     lib.rover_trpo_value_minibatch.argtypes = [pd, pd, th, vp, vp, vp, vp, i32, i32, vp, C.c_size_t, vp, vp, vp]
     lib.rover_trpo_value_apply.argtypes = [pd, pd, th, vp, vp, vp, vp, vp, vp, i32, vp, C.c_size_t, vp]
+    tdh = C.POINTER(Td3Hparams)
+    lib.rover_td3_default_hparams.argtypes = [tdh]
+    lib.rover_td3_hparams_bytes.restype = C.c_size_t
+    lib.rover_td3_state_bytes.restype = C.c_size_t
+    lib.rover_td3_critic_desc.argtypes = [pd]
+    lib.rover_td3_critic_pack.argtypes = [pd, C.POINTER(vp), C.POINTER(vp), vp]
+    lib.rover_td3_param_floats.argtypes = [pd, pd]
+    lib.rover_td3_param_floats.restype = C.c_size_t
+    lib.rover_td3_workspace_bytes.argtypes = [i32]
+    lib.rover_td3_workspace_bytes.restype = C.c_size_t
+    lib.rover_td3_critic_step.argtypes = [pd, pd, tdh, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, C.c_int64, vp, vp,
+                                          C.c_size_t, vp, vp, vp]
+    lib.rover_td3_actor_step.argtypes = [pd, pd, tdh, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, C.c_int64, vp, C.c_size_t, vp, vp, i32,
+                                         vp, vp]
+    lib.rover_td3_polyak.argtypes = [tdh, vp, vp, C.c_size_t, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -340,6 +372,8 @@ def load():
         raise RoverHipError("struct rover_lift_ppo_hparams / rover_lift_ppo_state of librover_hip.so does not match the Python mirror")
     if lib.rover_trpo_hparams_bytes() != C.sizeof(TrpoHparams) or lib.rover_trpo_state_bytes() != C.sizeof(TrpoState):
         raise RoverHipError("struct rover_trpo_hparams / rover_trpo_state of librover_hip.so does not match the Python mirror")
+    if lib.rover_td3_hparams_bytes() != C.sizeof(Td3Hparams) or lib.rover_td3_state_bytes() != C.sizeof(Td3State):
+        raise RoverHipError("struct rover_td3_hparams / rover_td3_state of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib
