@@ -18,7 +18,8 @@
  *           y = r + (gamma * !terminated) * min(tq1(s', a'), tq2(s', a')), critic_loss = (mse(q1(s, a), y) + mse(q2(s, a), y)) / 2,
  *           one Adam step (critic_lr) over both critics;
  *   actor:  policy_loss = -mean q1(s, pi(s)) with the critic_1 just updated, one Adam step (actor_lr) on the actor;
- *   polyak: target = target * (1 - polyak) + polyak * params over the whole vector (skrl: t.mul_(1 - tau); t.add_(tau * p)).
+ *   polyak: target = target * (1 - polyak) + polyak * params over the whole vector (skrl: t.mul_(1 - tau); t.add_(tau * p)),
+ *           with tau the float the struct holds, widened to double: see rover_td3_polyak for when that is skrl's result.
  *
  * Parameters live in ONE flat device vector: [actor packed | critic_1 packed | critic_2 packed | zero padding],
  * rover_td3_param_floats() floats.  The target vector, the gradient and both Adam moments have the same layout.
@@ -33,7 +34,7 @@
  * no host synchronisation, no atomics, -ffp-contract=off.
  *
  * Numerics and reduction order (bit-reproducible from run to run; results are fp32 and agree with float64, not bit for bit
- * with torch -- except rover_td3_polyak, which is bit-identical to torch's fp32 mul_ / add_):
+ * with torch -- except rover_td3_polyak, which is bit-identical to torch's fp32 mul_ / add_ for tau = (double)h->polyak):
  *   - dense layers (forward Z = A W^T + b; reverse dA = dZ W) on v_mfma_f32_16x16x4_f32, the reduction over k in ascending
  *     groups of 4 (one MFMA per group); LeakyReLU' from the sign of the stored activation;
  *   - weight / bias gradients dW = sum_rows dZ^T A: rows cut into fixed chunks of 512, one MFMA chain per (tile, chunk) over the
@@ -117,7 +118,15 @@ int rover_td3_actor_step(const rover_policy_desc *actor, const rover_policy_desc
                          void *ws, size_t ws_bytes, void *state, float *replicas_actor, int32_t n_copies, float *dact_out,
                          void *stream);
 
-/* target[e] = target[e] * (float)(1 - polyak) then + polyak * params[e], for e < count (elementwise, two roundings each). */
+/* target[e] = target[e] * keep then + h->polyak * params[e], for e < count (elementwise: two products and one sum, each
+ * rounded to fp32), with keep = (float)(1.0 - (double)h->polyak).  That is bit for bit torch's fp32
+ * `t.mul_(1 - tau); t.add_(tau * p)` for the Python float tau = (double)h->polyak, the float32 the struct holds.  skrl forms
+ * 1 - tau from the double it was configured with, so its result is the same exactly when
+ * (float)(1 - tau_double) == (float)(1 - (double)(float)tau_double): true at the default 0.005, at 0.05 and at 0.25; false at 0.9
+ * (0.1 against 0.100000024), 0.99, 0.995, 0.999 and about 40 % of the four-decimal taus in (0, 1), where `keep` is off by up to
+ * 2^-25 (half a float32 ulp of tau: several ulps of a small 1 - tau).  polyak = 1 gives keep = 0 and, for finite targets, a
+ * copy of params (skrl: t.copy_(p)).  `count`
+ * needs no alignment or padding; elements at and past `count` are not touched. */
 int rover_td3_polyak(const rover_td3_hparams *h, float *target, const float *params, size_t count, void *stream);
 
 #ifdef __cplusplus

@@ -299,6 +299,11 @@ class FusedTD3:
 
     ``update`` runs one gradient step without a host synchronisation; ``stats`` reads the state (one synchronisation).  The
     host counts the critic steps and runs the actor step and Polyak on every ``policy_delay``-th one.
+
+    Hyper-parameters are float32 in the C struct.  ``polyak`` is bit-identical to torch's fp32 ``t.mul_(1 - tau); t.add_(tau * p)``
+    for ``tau = float(numpy.float32(polyak))``; that is skrl's result with the double ``polyak`` whenever
+    ``float32(1 - polyak) == float32(1 - float32(polyak))`` (0.005, 0.05, 0.25: yes; 0.9, 0.99, 0.995, 0.999: no, see
+    ``rover_td3_polyak`` in rover_td3.h).  ``polyak = 1`` copies the parameters.
     """
 
     def __init__(self, policy_sd: Mapping[str, torch.Tensor], critic_1_sd: Mapping[str, torch.Tensor],

@@ -1,6 +1,6 @@
-"""Shared helpers of the TD3 tests (test_td3.py, test_gpu_td3_update.py, test_gpu_td3_edges.py): the example's actor, the
-Q(s, a) critic, a filled replay memory, float64 / float32 copies of the networks and the "fused error <= 4x torch fp32 error
-against float64, plus a floor" check of trpo_helpers."""
+"""Shared helpers of the TD3 tests (test_td3.py, test_gpu_td3_*.py): the example's actor, the Q(s, a) critic, a filled replay
+memory, float64 / float32 copies of the networks, the "fused error <= 4x torch fp32 error against float64, plus a floor" check
+of trpo_helpers, one hyper-parameter dict for both paths and bit comparisons of two trainers."""
 import copy
 
 import torch
@@ -56,3 +56,67 @@ def check(fused, ref64, ref32, factor=4.0, floor=1e-5, what=""):
         return
     e_f, e_t = err(fused, ref64), err(ref32, ref64)
     assert e_f <= factor * e_t + floor * float(ref64.double().norm()) + 1e-30, (what, e_f, e_t, float(ref64.norm()))
+
+
+# ---- hyper-parameters: one dict in rover_td3_hparams' field names for both paths
+TORCH_NAMES = dict(gamma="discount_factor", polyak="polyak", actor_lr="actor_learning_rate", critic_lr="critic_learning_rate",
+                   noise_clip="smooth_regularization_clip", act_min="clip_actions_min", act_max="clip_actions_max")
+ADAM_NAMES = ("beta1", "beta2", "eps")
+
+
+def hparams(**hp):
+    """(FusedTD3 keywords, TorchTD3 keywords, Adam settings) of one dict in the C field names.  Every value goes through
+    numpy.float32 and back to a Python float first, so both paths hold the number the C struct holds."""
+    import numpy as np
+    unknown = set(hp) - set(TORCH_NAMES) - set(ADAM_NAMES)
+    assert not unknown, unknown
+    f = {k: float(np.float32(v)) for k, v in hp.items()}
+    return f, {TORCH_NAMES[k]: v for k, v in f.items() if k in TORCH_NAMES}, {k: v for k, v in f.items() if k in ADAM_NAMES}
+
+
+def set_adam(spec, adam):
+    """Adam's betas and eps are not TorchTD3 hyper-parameters: set them on both of the spec's optimizers."""
+    for opt in (spec.policy_optimizer, spec.critic_optimizer):
+        for g in opt.param_groups:
+            g["betas"] = (adam.get("beta1", g["betas"][0]), adam.get("beta2", g["betas"][1]))
+            g["eps"] = adam.get("eps", g["eps"])
+
+
+def trainers(mods, policy_delay=2, **hp):
+    """(FusedTD3, {float64: TorchTD3, float32: TorchTD3}) from (actor, critic_1, critic_2) with the same hyper-parameters."""
+    from isaac_rover_orbit_amd.td3 import FusedTD3, TorchTD3
+    fused_kw, torch_kw, adam = hparams(**hp)
+    fused = FusedTD3(*(m.state_dict() for m in mods), policy_delay=policy_delay, **fused_kw)
+    specs = {}
+    for dt in (torch.float64, torch.float32):
+        specs[dt] = TorchTD3(*copies(mods, dt), policy_delay=policy_delay, **torch_kw)
+        set_adam(specs[dt], adam)
+    return fused, specs
+
+
+def poison_ws(fused, rows):
+    """Grows the trainer's workspace to ``rows`` rows and fills it with 0xFF bytes: every float in it is a NaN."""
+    fused._ensure_ws(rows)
+    fused.ws.fill_(0xFF)
+
+
+TRAINER_VECTORS = ("params", "target", "grad", "adam_m", "adam_v", "state", "rep_a")
+
+
+def clone_trainer(src, dst):
+    """Copies src's device vectors and step count into dst (a FusedTD3 of the same hyper-parameters)."""
+    for name in TRAINER_VECTORS:
+        getattr(dst, name).copy_(getattr(src, name))
+    dst.critic_updates = src.critic_updates
+
+
+def assert_same_trainer(a, b, skip_state_words=()):
+    """Every device vector of two trainers bit for bit (state words in skip_state_words left out)."""
+    for name in TRAINER_VECTORS:
+        x, y = getattr(a, name), getattr(b, name)
+        if name == "state" and skip_state_words:
+            keep = [i for i in range(x.numel()) if i not in skip_state_words]
+            x, y = x[keep], y[keep]
+        # equal as numbers (a NaN on either side fails) and as bit patterns (-0 is not +0)
+        assert torch.equal(x, y) and torch.equal(x.view(torch.int32), y.view(torch.int32)), name
+    assert a.critic_updates == b.critic_updates
