@@ -76,6 +76,9 @@ def main():
     ap.add_argument("--save", default=None, help="write a skrl-style checkpoint {'policy': state_dict, 'value': state_dict}")
     ap.add_argument("--update", choices=("torch", "fused"), default="torch",
                     help="PPO update: torch autograd + torch.optim.Adam, or the fused HIP kernels (isaac_rover_orbit_amd.ppo)")
+    ap.add_argument("--rollout", choices=("torch", "fused"), default="torch",
+                    help="rollout glue around env.step: torch ops with torch.randn noise, or isaac_rover_orbit_amd.rollout.RolloutCollector "
+                         "(one HIP launch per step: sanitise, both networks, counter-based Gaussian actions, log-prob)")
     args = ap.parse_args()
     torch.manual_seed(42)
     dev = torch.device("cuda")
@@ -96,8 +99,19 @@ def main():
     act_buf = torch.empty(Tn, n, 2, device=dev)
     logp_buf, val_buf, rew_buf = (torch.empty(Tn, n, device=dev) for _ in range(3))
     done_buf = torch.empty(Tn, n, device=dev)
+    collector = None
+    if args.rollout == "fused":
+        from isaac_rover_orbit_amd.rollout import RolloutCollector
+        if fused is not None:                   # the trainer's networks and log-std by reference: always the current parameters
+            collector = RolloutCollector(fused.actor, fused.critic, fused.log_std, n, Tn, seed=42)
+        else:                                   # re-packed networks are handed over at the top of every iteration
+            collector = RolloutCollector(RoverNet.from_state_dict(policy.state_dict(), final_act="tanh"),
+                                         RoverNet.from_state_dict(value.state_dict(), final_act="none"),
+                                         policy.log_std_parameter.detach(), n, Tn, seed=42)
+        obs_buf, act_buf, logp_buf, val_buf = collector.obs, collector.actions, collector.logp, collector.val
+        rew_buf, done_buf = collector.rew, collector.done
     obs, _ = env.reset()
-    o = torch.nan_to_num(obs["policy"], neginf=0.0)
+    o = obs["policy"] if collector is not None else torch.nan_to_num(obs["policy"], neginf=0.0)
     out = open(args.out, "w") if args.out else None
     for it in range(args.iterations):
         t0 = time.perf_counter()
@@ -111,7 +125,16 @@ def main():
             log_std = fused.log_std.clamp(-20.0, 2.0)
         std = log_std.exp()
         ep_count = torch.zeros((), device=dev); ep_stats = torch.zeros(4, device=dev)
+        if collector is not None:
+            collector.actor, collector.critic = actor, critic
         for t in range(Tn):
+            if collector is not None:           # the raw rows go in; slot t of every buffer comes out
+                obs, rew, term, trunc, info = env.step(collector.act(t, o))
+                o = obs["policy"]
+                collector.record(t, rew, term, trunc)
+                lv = env.episode_log_vector
+                ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
+                continue
             mean = actor(o)
             a = mean + std * torch.randn_like(mean)
             logp_buf[t] = (-0.5 * ((a - mean) / std) ** 2 - log_std - 0.9189385332).sum(1)
@@ -126,7 +149,7 @@ def main():
         if fused is not None:
             # ---- GAE and the PPO update on the fused HIP kernels (isaac_rover_orbit_amd.ppo)
             with torch.no_grad():
-                last_v = critic(o).squeeze(1)
+                last_v = collector.last_value(o) if collector is not None else critic(o).squeeze(1)
                 adv, ret = fused.gae(rew_buf, done_buf, val_buf, last_v)
                 adv = (adv - adv.mean()) / (adv.std() + 1e-8)
             kls, _ = fused.update(obs_buf, act_buf, logp_buf, val_buf, ret, adv)
@@ -134,7 +157,7 @@ def main():
         else:
             # ---- GAE (skrl PPO: bootstraps through time-outs like the reference's config)
             with torch.no_grad():
-                last_v = critic(o).squeeze(1)
+                last_v = collector.last_value(o) if collector is not None else critic(o).squeeze(1)
                 adv = torch.zeros_like(rew_buf); gae = torch.zeros(n, device=dev)
                 for t in reversed(range(Tn)):
                     nv = last_v if t == Tn - 1 else val_buf[t + 1]

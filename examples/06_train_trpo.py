@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--save", default=None, help="write a skrl-style checkpoint {'policy': state_dict, 'value': state_dict}")
     ap.add_argument("--update", choices=("torch", "fused"), default="torch",
                     help="TRPO update: the torch spec (TorchTRPO) or the fused HIP kernels (FusedTRPO)")
+    ap.add_argument("--rollout", choices=("torch", "fused"), default="torch",
+                    help="rollout glue around env.step: torch ops with torch.randn noise, or isaac_rover_orbit_amd.rollout.RolloutCollector "
+                         "(one HIP launch per step: sanitise, both networks, counter-based Gaussian actions, log-prob)")
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
@@ -60,8 +63,19 @@ def main():
     act_buf = torch.empty(Tn, n, 2, device=dev)
     logp_buf, val_buf, rew_buf = (torch.empty(Tn, n, device=dev) for _ in range(3))
     done_buf = torch.empty(Tn, n, device=dev)
+    collector = None
+    if args.rollout == "fused":
+        from isaac_rover_orbit_amd.rollout import RolloutCollector
+        if fused is not None:                   # the trainer's networks and log-std by reference: always the current parameters
+            collector = RolloutCollector(fused.actor, fused.critic, fused.log_std, n, Tn, seed=args.seed)
+        else:                                   # re-packed networks are handed over at the top of every iteration
+            collector = RolloutCollector(RoverNet.from_state_dict(policy.state_dict(), final_act="tanh"),
+                                         RoverNet.from_state_dict(value.state_dict(), final_act="none"),
+                                         policy.log_std_parameter.detach(), n, Tn, seed=args.seed)
+        obs_buf, act_buf, logp_buf, val_buf = collector.obs, collector.actions, collector.logp, collector.val
+        rew_buf, done_buf = collector.rew, collector.done
     obs, _ = env.reset()
-    o = torch.nan_to_num(obs["policy"], neginf=0.0)
+    o = obs["policy"] if collector is not None else torch.nan_to_num(obs["policy"], neginf=0.0)
     out = open(args.out, "w") if args.out else None
     B = Tn * n
     for it in range(args.iterations):
@@ -76,7 +90,16 @@ def main():
             log_std = fused.log_std.clamp(-20.0, 2.0)
         std = log_std.exp()
         ep_count = torch.zeros((), device=dev); ep_stats = torch.zeros(4, device=dev)
+        if collector is not None:
+            collector.actor, collector.critic = actor, critic
         for t in range(Tn):
+            if collector is not None:           # the raw rows go in; slot t of every buffer comes out
+                obs, rew, term, trunc, info = env.step(collector.act(t, o))
+                o = obs["policy"]
+                collector.record(t, rew, term, trunc)
+                lv = env.episode_log_vector
+                ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
+                continue
             mean = actor(o)
             a = mean + std * torch.randn_like(mean)
             logp_buf[t] = (-0.5 * ((a - mean) / std) ** 2 - log_std - 0.9189385332).sum(1)
@@ -90,7 +113,7 @@ def main():
         torch.cuda.synchronize(); t_roll = time.perf_counter() - t0
         perms = [torch.randperm(B, device=dev) for _ in range(4)]
         with torch.no_grad():
-            last_v = critic(o).squeeze(1)
+            last_v = collector.last_value(o) if collector is not None else critic(o).squeeze(1)
             if fused is not None:
                 adv, ret = fused.gae(rew_buf, done_buf, val_buf, last_v)
             else:

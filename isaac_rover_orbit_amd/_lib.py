@@ -48,6 +48,7 @@ EXPORTS = [
     "rover_td3_default_hparams", "rover_td3_hparams_bytes", "rover_td3_state_bytes", "rover_td3_critic_desc",  # rover_td3.h
     "rover_td3_critic_pack", "rover_td3_param_floats", "rover_td3_workspace_bytes", "rover_td3_critic_step", "rover_td3_actor_step",
     "rover_td3_polyak",
+    "rover_rollout_default_hparams", "rover_rollout_hparams_bytes", "rover_rollout_act", "rover_rollout_record",  # rover_rollout.h
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -126,6 +127,12 @@ class Td3State(C.Structure):
                 ("critic_loss", C.c_float), ("policy_loss", C.c_float), ("q1_mean", C.c_float), ("q2_mean", C.c_float),
                 ("y_mean", C.c_float), ("critic_step_size", C.c_float), ("critic_bc2_sqrt", C.c_float), ("actor_step_size", C.c_float),
                 ("actor_bc2_sqrt", C.c_float), ("reserved", C.c_float * 3)]
+
+
+class RolloutHparams(C.Structure):
+    """Mirror of ``struct rover_rollout_hparams`` (include/rover_rollout.h)."""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("clip_actions", C.c_int32),
+                ("action_low", C.c_float), ("action_high", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float)]
 
 
 class RoverHipError(RuntimeError):
@@ -351,6 +358,11 @@ def load():
     lib.rover_td3_actor_step.argtypes = [pd, pd, tdh, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, C.c_int64, vp, C.c_size_t, vp, vp, i32,
                                          vp, vp]
     lib.rover_td3_polyak.argtypes = [tdh, vp, vp, C.c_size_t, vp]
+    lib.rover_rollout_default_hparams.argtypes = [C.POINTER(RolloutHparams)]
+    lib.rover_rollout_hparams_bytes.restype = C.c_size_t
+    lib.rover_rollout_act.argtypes = [pd, vp, pd, vp, i32, C.POINTER(RolloutHparams), C.c_uint64, vp, i32, vp, vp, vp, vp, vp, vp, vp,
+                                      vp, vp]
+    lib.rover_rollout_record.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -374,6 +386,8 @@ def load():
         raise RoverHipError("struct rover_trpo_hparams / rover_trpo_state of librover_hip.so does not match the Python mirror")
     if lib.rover_td3_hparams_bytes() != C.sizeof(Td3Hparams) or lib.rover_td3_state_bytes() != C.sizeof(Td3State):
         raise RoverHipError("struct rover_td3_hparams / rover_td3_state of librover_hip.so does not match the Python mirror")
+    if lib.rover_rollout_hparams_bytes() != C.sizeof(RolloutHparams):
+        raise RoverHipError("struct rover_rollout_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib
