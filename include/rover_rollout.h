@@ -42,7 +42,7 @@ typedef struct rover_rollout_hparams {
     uint32_t seed_lo, seed_hi;        /* Philox key */
     int32_t  env_id_offset;           /* global id of row 0 (RoverEnvCfg.env_id_offset) */
     int32_t  clip_actions;            /* 1: env_act = clamp(act, action_low, action_high)  (models.py:66) */
-    float    action_low, action_high; /* -1, 1 */
+    float    action_low, action_high; /* -1, 1; action_low > action_high is only refused when clip_actions is set */
     float    log_std_min, log_std_max;/* -20, 2 (models.py:66) */
 } rover_rollout_hparams;
 

@@ -19,6 +19,7 @@ import torch
 
 from helpers import random_policy_weights, small_procedural
 from ppo_reference import load_example
+from rollout_helpers import _biteq, _inject, _run
 
 pytestmark = pytest.mark.gpu
 
@@ -59,46 +60,6 @@ def env_rows():
     rows = obs["policy"].clone()
     env.close()
     return rows
-
-
-def _inject(rows, n):
-    """Rows [0, n) with non-finite values on rows 0, 15, 16 and n - 1 (those that exist): -inf and NaN alternate over the first and
-    the last encoder column (3, 963), column 0 and a mid-row column; +inf sits in column 964.  That column is in the row but read by
-    neither network (models.py:95 drops the last ray), so the FLT_MAX it becomes is checked in obs_out without saturating the
-    networks to inf - inf = NaN, for which no bound on act or logp could be stated."""
-    raw = rows[:n].clone()
-    vals = [float("-inf"), float("nan")]
-    for i, r in enumerate(sorted({0, 15, 16, n - 1})):
-        if r >= n:
-            continue
-        for j, c in enumerate((3, 963, 0, 500 + r % 7)):
-            raw[r, c] = vals[(i + j) % 2]
-        raw[r, 964] = float("inf")
-    return raw
-
-
-def _biteq(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def _hp(**kw):
-    from isaac_rover_orbit_amd import rollout as R
-    hp = R.default_hparams()
-    for k, v in kw.items():
-        setattr(hp, k, v)
-    return hp
-
-
-def _run(nets, raw, log_std, counter=0, outs=("obs", "act", "env_act", "logp", "eps"), **hp):
-    from isaac_rover_orbit_amd import rollout as R
-    n, A = raw.shape[0], nets[0].out_dim
-    f = dict(dtype=torch.float32, device="cuda")
-    shapes = {"obs": (n, 965), "act": (n, A), "env_act": (n, A), "logp": (n,), "eps": (n, A)}
-    o = {k: torch.full(shapes[k], 777.0, **f) for k in outs}
-    mean, val = R.rollout_act(nets[0], nets[1], log_std, raw, counter, _hp(**hp), **{k + "_out": v for k, v in o.items()})
-    o["mean"], o["val"] = mean, val
-    torch.cuda.synchronize()
-    return o
 
 
 @pytest.mark.parametrize("n", SIZES)
