@@ -123,7 +123,8 @@ int rover_lift_ppo_minibatch(const rover_policy_desc *policy, const rover_policy
                              float *mean_out, float *value_out, void *stream);
 
 /* Unless state->stop is set: clip_grad_norm_ + one Adam step in torch's order (as rover_ppo_apply), then the new packed
- * parameters of each network n_copies times back to back into replicas_policy / replicas_value (either may be NULL). */
+ * parameters of each network n_copies times back to back into replicas_policy / replicas_value (either may be NULL).  `grad` is
+ * overwritten: after a step that ran it holds the clipped gradient, grad * state->clip_coef (fp32 products). */
 int rover_lift_ppo_apply(const rover_policy_desc *policy, const rover_policy_desc *value, const rover_lift_ppo_hparams *h,
                          float *params, float *grad, float *adam_m, float *adam_v, void *state, float *replicas_policy,
                          float *replicas_value, int32_t n_copies, void *ws, size_t ws_bytes, void *stream);

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from lift_ppo_reference import NumpyScaler, loss_and_grads
+from lift_ppo_reference import NumpyScaler, clip_and_adam, loss_and_grads, loss_terms_and_grads
 
 
 def _nets(seed=0):
@@ -48,6 +48,64 @@ def test_float64_reference_matches_the_torch_spec_loss():
         assert torch.allclose(p.grad, grads["policy"][name], rtol=1e-10, atol=1e-12), name
     for name, p in val64.named_parameters():
         assert torch.allclose(p.grad, grads["value"][name], rtol=1e-10, atol=1e-12), name
+
+
+@pytest.mark.parametrize("moved", [{}, {"clip": 0.05, "vclip": 1.0, "vscale": 7.0}])
+def test_float64_reference_terms_match_the_torch_spec_loss(moved):
+    """loss_terms_and_grads (the log_std bounds at their defaults) = lift_ppo_loss + autograd: both loss terms, KL, gradients."""
+    from isaac_rover_orbit_amd import lift_ppo as LP
+    pol, val = _nets(7)
+    g = torch.Generator().manual_seed(8)
+    n = 300
+    s = torch.randn(n, 36, generator=g)
+    with torch.no_grad():
+        mean = pol(s)
+        a = mean + torch.randn(n, 8, generator=g) * 0.7
+        lp = LP.gaussian_logp(mean, pol.log_std_parameter, a) + 0.3 * torch.randn(n, generator=g)
+        oldv = val(s)[:, 0] + 0.4 * torch.randn(n, generator=g)
+    ret, adv = oldv + torch.randn(n, generator=g), torch.randn(n, generator=g)
+    pol64, val64 = pol.double(), val.double()
+    args64 = [x.double() for x in (s, a, lp, oldv, ret, adv)]
+    loss, kl, pl, vl = LP.lift_ppo_loss(pol64, val64, *args64, **moved)
+    loss.backward()
+    r_loss, r_kl, r_pl, r_vl, grads = loss_terms_and_grads(pol.state_dict(), val.state_dict(), *args64, **moved)
+    for a_, b_ in ((loss.detach(), r_loss), (kl, r_kl), (pl, r_pl), (vl, r_vl)):
+        assert torch.allclose(a_, b_, rtol=1e-12, atol=1e-12)
+    assert torch.allclose(r_pl + r_vl, r_loss, rtol=1e-14, atol=0)
+    for name, p in pol64.named_parameters():
+        assert torch.allclose(p.grad, grads["policy"][name], rtol=1e-10, atol=1e-12), name
+    for name, p in val64.named_parameters():
+        assert torch.allclose(p.grad, grads["value"][name], rtol=1e-10, atol=1e-12), name
+    l3, k3, g3 = loss_and_grads(pol.state_dict(), val.state_dict(), *args64, **moved)      # the three-value form is the same call
+    assert torch.equal(l3, r_loss) and torch.equal(k3, r_kl)
+    assert all(torch.equal(g3[r][k], grads[r][k]) for r in grads for k in grads[r])
+
+
+@pytest.mark.parametrize("scale,max_norm,kw", [(1.0, 1.0, {}), (0.001, 1.0, {}),
+                                               (1.0, 0.25, {"lr": 3e-3, "betas": (0.8, 0.99), "eps": 1e-5})])
+def test_clip_and_adam_matches_torch_adam_in_float64(scale, max_norm, kw):
+    """clip_and_adam at float64 = clip_grad_norm_ + torch.optim.Adam on float64 tensors over 3 steps, clipped and un-clipped."""
+    g = torch.Generator().manual_seed(11)
+    shapes = [(7, 5), (5,), (3, 4), (8,)]
+    p0 = [torch.randn(*s, generator=g, dtype=torch.float64) for s in shapes]
+    ref = [p.clone().requires_grad_(True) for p in p0]
+    opt = torch.optim.Adam(ref, **{"lr": 1e-4, **kw})
+    lr, (b1, b2), eps = opt.defaults["lr"], opt.defaults["betas"], opt.defaults["eps"]
+    params, m, v = p0, [torch.zeros_like(p) for p in p0], [torch.zeros_like(p) for p in p0]
+    for step in (1, 2, 3):
+        grads = [torch.randn(*s, generator=g, dtype=torch.float64) * scale for s in shapes]
+        for p, gr in zip(ref, grads):
+            p.grad = gr.clone()
+        norm_t = float(torch.nn.utils.clip_grad_norm_(ref, max_norm))
+        opt.step()
+        params, m, v, clipped, norm, coef = clip_and_adam(params, grads, m, v, step, lr, max_norm, b1, b2, eps, torch.float64)
+        assert norm == pytest.approx(norm_t, rel=1e-12)
+        assert coef == pytest.approx(min(1.0, max_norm / (norm_t + 1e-6)), rel=1e-12)
+        assert (coef == 1.0) == (scale < 1.0)
+        for a_, b_, c_, d_ in zip(params, ref, clipped, grads):
+            assert torch.allclose(a_, b_.detach(), rtol=1e-12, atol=0)
+            assert torch.allclose(c_, b_.grad, rtol=1e-12, atol=0) and torch.allclose(c_, d_ * coef, rtol=1e-15, atol=0)
+    assert all(not torch.equal(a_, b_) for a_, b_ in zip(params, p0))
 
 
 def test_torch_scaler_matches_numpy_float64():
