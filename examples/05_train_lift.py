@@ -4,10 +4,13 @@ skrl_ppo_cfg.yaml): ELU networks 36 -> 256 -> 128 -> 64 -> {8, 1}, RunningStanda
 24 rollouts, 8 epochs, 24 minibatches, lr 1e-4 with KLAdaptiveRL, KL early stop 0.008, value-loss scale 2, grad-norm clip 1.0.
 Rollouts run on the fused kernels (env.step = HIP, policy mean and value = one HIP forward each); the update is either the
 torch spec (``--update torch``: isaac_rover_orbit_amd.lift_ppo.TorchLiftPPO, plain autograd + torch.optim.Adam) or the fused HIP
-update (``--update fused``: FusedLiftPPO; the rollout reads the trainer's parameters and scalers directly).  A stand-in for the
-reference's skrl trainer, which needs packages that are not part of this repository.
+update (``--update fused``: FusedLiftPPO; the rollout reads the trainer's parameters and scalers directly).  ``--rollout fused``
+(with ``--update fused``) replaces the per-step torch glue around ``env.step`` with isaac_rover_orbit_amd.lift_rollout's
+LiftRolloutCollector: one launch for scale + act + sample + log-prob, one for the reward / done record and the episode tally; its
+action noise is counter-based (Philox), so the curve follows ``--rollout torch`` statistically, not bit for bit.  A stand-in for
+the reference's skrl trainer, which needs packages that are not part of this repository.
 
-    python examples/05_train_lift.py --update fused --num_envs 4096 --iterations 100 --out curve.jsonl
+    python examples/05_train_lift.py --update fused --rollout fused --num_envs 4096 --iterations 100 --out curve.jsonl
 """
 import argparse
 import json
@@ -34,7 +37,11 @@ def main():
     ap.add_argument("--save", default=None, help="write a skrl-style checkpoint (policy, value, both preprocessors)")
     ap.add_argument("--update", choices=("torch", "fused"), default="torch",
                     help="PPO update: the torch spec (autograd + torch.optim.Adam) or the fused HIP kernels")
+    ap.add_argument("--rollout", choices=("torch", "fused"), default="torch",
+                    help="per-step rollout glue: torch ops, or the fused HIP collector (needs --update fused)")
     args = ap.parse_args()
+    if args.rollout == "fused" and args.update != "fused":
+        ap.error("--rollout fused requires --update fused")
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
     n, Tn = args.num_envs, args.rollouts
@@ -52,6 +59,11 @@ def main():
     obs_buf = torch.empty(Tn, n, LP.OBS_DIM, device=dev)
     act_buf = torch.empty(Tn, n, LP.ACT_DIM, device=dev)
     logp_buf, val_buf, rew_buf, done_buf = (torch.empty(Tn, n, device=dev) for _ in range(4))
+    col = None
+    if args.rollout == "fused":                 # the collector's own (T, n, ...) buffers go straight into gae / update
+        from isaac_rover_orbit_amd.lift_rollout import LiftRolloutCollector
+        col = LiftRolloutCollector(fused, n, Tn, seed=args.seed)
+        obs_buf, act_buf, logp_buf, val_buf, rew_buf, done_buf = col.obs, col.actions, col.logp, col.val, col.rew, col.done
     obs, _ = env.reset()
     o = obs["policy"].clone()
     out = open(args.out, "w") if args.out else None
@@ -71,8 +83,11 @@ def main():
         ls = log_std.clamp(-20.0, 2.0)
         std = ls.exp()
         ep_sum = torch.zeros(8, device=dev); ep_count = torch.zeros((), device=dev)
+        if col is not None:
+            col.reset_tally()
+            ep_sum, ep_count = col.ep_sum, col.ep_count
         with torch.no_grad():
-            for t in range(Tn):
+            for t in range(Tn if col is None else 0):
                 s = state_pre(o)
                 mean = actor(s)
                 a = mean + std * torch.randn_like(mean)                   # clip_actions: False
@@ -86,8 +101,12 @@ def main():
                 k = log[8]                                                # envs reset in this step; log[0:8] are their means
                 ep_sum += torch.where(k > 0, log[0:8] * torch.where(torch.arange(8, device=dev) < 6, k, 1.0), 0.0)
                 ep_count += k
+            for t in range(Tn if col is not None else 0):                 # the same steps, two launches around env.step
+                obs, rew, term, trunc, _ = env.step(col.act(t, o))
+                o = obs["policy"]
+                col.record(t, rew, term, trunc, log)
             torch.cuda.synchronize(); t_roll = time.perf_counter() - t0
-            last_v = value_inv(critic(state_pre(o))).squeeze(1)
+            last_v = col.last_value(o) if col is not None else value_inv(critic(state_pre(o))).squeeze(1)
             if fused is not None:
                 adv, ret = fused.gae(rew_buf, done_buf, val_buf, last_v)
             else:

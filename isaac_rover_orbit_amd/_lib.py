@@ -49,6 +49,8 @@ EXPORTS = [
     "rover_td3_critic_pack", "rover_td3_param_floats", "rover_td3_workspace_bytes", "rover_td3_critic_step", "rover_td3_actor_step",
     "rover_td3_polyak",
     "rover_rollout_default_hparams", "rover_rollout_hparams_bytes", "rover_rollout_act", "rover_rollout_record",  # rover_rollout.h
+    "rover_lift_rollout_default_hparams", "rover_lift_rollout_hparams_bytes", "rover_lift_rollout_act",  # rover_lift_rollout.h
+    "rover_lift_rollout_record",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -133,6 +135,13 @@ class RolloutHparams(C.Structure):
     """Mirror of ``struct rover_rollout_hparams`` (include/rover_rollout.h)."""
     _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("clip_actions", C.c_int32),
                 ("action_low", C.c_float), ("action_high", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float)]
+
+
+class LiftRolloutHparams(C.Structure):
+    """Mirror of ``struct rover_lift_rollout_hparams`` (include/rover_lift_rollout.h)."""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("clip_actions", C.c_int32),
+                ("action_low", C.c_float), ("action_high", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
+                ("scaler_eps", C.c_float), ("scaler_clip", C.c_float), ("reward_scale", C.c_float)]
 
 
 class RoverHipError(RuntimeError):
@@ -363,6 +372,11 @@ def load():
     lib.rover_rollout_act.argtypes = [pd, vp, pd, vp, i32, C.POINTER(RolloutHparams), C.c_uint64, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                       vp, vp]
     lib.rover_rollout_record.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    lib.rover_lift_rollout_default_hparams.argtypes = [C.POINTER(LiftRolloutHparams)]
+    lib.rover_lift_rollout_hparams_bytes.restype = C.c_size_t
+    lib.rover_lift_rollout_act.argtypes = [pd, vp, pd, vp, i32, C.POINTER(LiftRolloutHparams), C.c_uint64, vp, i32, vp, vp, vp, vp, vp,
+                                           vp, vp, vp, vp, vp, vp]
+    lib.rover_lift_rollout_record.argtypes = [vp, vp, vp, i32, f32, vp, vp, vp, vp, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -388,6 +402,8 @@ def load():
         raise RoverHipError("struct rover_td3_hparams / rover_td3_state of librover_hip.so does not match the Python mirror")
     if lib.rover_rollout_hparams_bytes() != C.sizeof(RolloutHparams):
         raise RoverHipError("struct rover_rollout_hparams of librover_hip.so does not match the Python mirror")
+    if lib.rover_lift_rollout_hparams_bytes() != C.sizeof(LiftRolloutHparams):
+        raise RoverHipError("struct rover_lift_rollout_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib

@@ -43,10 +43,11 @@ def philox4x32(c0, c1, c2, c3, k0, k1):
     return c0, c1, c2, c3
 
 
-def rollout_counter(env_ids, counter: int, pair):
-    """The Philox input (c0, c1, c2, c3) of global env id(s) ``env_ids``, step ``counter`` and action pair(s) ``pair``."""
+def rollout_counter(env_ids, counter: int, pair, tag: int = ROLLOUT_TAG):
+    """The Philox input (c0, c1, c2, c3) of global env id(s) ``env_ids``, step ``counter`` and action pair(s) ``pair``; ``tag`` is
+    the stream's word 3 (the lift collector draws under a tag of its own)."""
     return (np.asarray(env_ids, dtype=np.uint64) & np.uint64(_MASK), np.uint64(int(counter) & _MASK),
-            np.uint64((int(counter) >> 32) & _MASK), np.uint64(ROLLOUT_TAG) | np.asarray(pair, dtype=np.uint64))
+            np.uint64((int(counter) >> 32) & _MASK), np.uint64(int(tag) & _MASK) | np.asarray(pair, dtype=np.uint64))
 
 
 def unit_uniform(w):
@@ -54,11 +55,11 @@ def unit_uniform(w):
     return ((np.asarray(w, dtype=np.uint64) >> np.uint64(9)).astype(np.float64) + 0.5) * 2.0 ** -23
 
 
-def standard_normals(seed: int, env_ids, counter: int, width: int) -> np.ndarray:
+def standard_normals(seed: int, env_ids, counter: int, width: int, tag: int = ROLLOUT_TAG) -> np.ndarray:
     """eps (len(env_ids), width) in float64: Box-Muller on the exact uniforms, columns 2p / 2p + 1 = cosine / sine branch of pair p."""
     ids = np.asarray(env_ids, dtype=np.int64).reshape(-1, 1)
     pairs = np.arange((width + 1) // 2, dtype=np.int64).reshape(1, -1)
-    w0, w1, _, _ = philox4x32(*rollout_counter(ids, counter, pairs), int(seed) & _MASK, (int(seed) >> 32) & _MASK)
+    w0, w1, _, _ = philox4x32(*rollout_counter(ids, counter, pairs, tag), int(seed) & _MASK, (int(seed) >> 32) & _MASK)
     u1, u2 = unit_uniform(w0), unit_uniform(w1)
     rho = np.sqrt(-2.0 * np.log(u1))
     eps = np.stack([rho * np.cos(2.0 * np.pi * u2), rho * np.sin(2.0 * np.pi * u2)], axis=-1).reshape(ids.shape[0], -1)
