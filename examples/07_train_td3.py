@@ -7,8 +7,11 @@ Transitions live in ``td3.ReplayMemory``, one observation ring.  The update is t
 
 Every env step: the actor forward (``FusedTD3.actor`` on the fused kernels, or the torch actor), optional exploration noise,
 env.step with those actions, memory.add of the same actions, then one gradient step on a batch drawn from the memory.
+``--rollout fused`` (with ``--update fused``) hands all of that but env.step and the update to ``td3_collect.TD3Collector``: two
+HIP launches per env step, counter-based noise and batch indices.
 
     python examples/07_train_td3.py --num_envs 4096 --timesteps 2000 --update fused --out td3.jsonl
+    python examples/07_train_td3.py --num_envs 4096 --timesteps 2000 --update fused --rollout fused --out td3.jsonl
 """
 import argparse
 import importlib.util
@@ -26,6 +29,7 @@ from isaac_rover_orbit_amd.cfg import RoverEnvCfg  # noqa: E402
 from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
 from isaac_rover_orbit_amd.td3 import (HPARAMS, Critic, FusedTD3, ReplayMemory, TorchTD3, exploration_scale,  # noqa: E402
                                        explore)
+from isaac_rover_orbit_amd.td3_collect import TD3Collector  # noqa: E402
 
 _spec = importlib.util.spec_from_file_location("train_ppo_example", os.path.join(ROOT, "examples", "04_train_ppo.py"))
 ppo_example = importlib.util.module_from_spec(_spec)
@@ -46,7 +50,11 @@ def main():
     ap.add_argument("--save", default=None, help="write a skrl-style TD3 checkpoint (policy, target_policy, critic_1, ...)")
     ap.add_argument("--update", choices=("torch", "fused"), default="torch",
                     help="TD3 update: the torch spec (TorchTD3) or the fused HIP kernels (FusedTD3)")
+    ap.add_argument("--rollout", choices=("torch", "fused"), default="torch",
+                    help="the glue around env.step: torch ops and ReplayMemory.add, or the fused collector (needs --update fused)")
     args = ap.parse_args()
+    if args.rollout == "fused" and args.update != "fused":
+        ap.error("--rollout fused needs --update fused (the collector runs FusedTD3's actor)")
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
     n, M = args.num_envs, args.memory_size or 2 * args.batch_size
@@ -65,23 +73,34 @@ def main():
         spec = TorchTD3(policy, critic_1, critic_2)
     gen = torch.Generator(device=dev).manual_seed(args.seed)
     obs, _ = env.reset()
-    o = torch.nan_to_num(obs["policy"], neginf=0.0)
+    collector = None
+    if args.rollout == "fused":
+        collector = TD3Collector(fused.actor, memory, seed=args.seed, env_id_offset=cfg.env_id_offset, noise_std=args.exploration_noise)
+        collector.begin(obs)
+    else:
+        o = torch.nan_to_num(obs["policy"], neginf=0.0)
     out = open(args.out, "w") if args.out else None
     t_log, steps_log, last = time.perf_counter(), 0, {}
     ep_count = torch.zeros((), device=dev); ep_stats = torch.zeros(4, device=dev)
     for step in range(args.timesteps):
-        with torch.no_grad():
-            a = fused.actor(o) if fused is not None else spec.act(o)
+        scale = None
         if args.exploration_noise > 0:
             scale = exploration_scale(step, args.timesteps, HPARAMS["exploration_initial_scale"], HPARAMS["exploration_final_scale"])
-            a = explore(a, args.exploration_noise * torch.randn(a.shape, device=dev, generator=gen), scale)
-        obs, rew, term, trunc, info = env.step(a)
-        o_next = torch.nan_to_num(obs["policy"], neginf=0.0)
-        memory.add(o, a, rew, o_next, term)
-        o = o_next
+        if collector is not None:
+            obs, rew, term, trunc, info = env.step(collector.act(scale))
+            idx = collector.record(obs, rew, term, args.batch_size)
+        else:
+            with torch.no_grad():
+                a = fused.actor(o) if fused is not None else spec.act(o)
+            if args.exploration_noise > 0:
+                a = explore(a, args.exploration_noise * torch.randn(a.shape, device=dev, generator=gen), scale)
+            obs, rew, term, trunc, info = env.step(a)
+            o_next = torch.nan_to_num(obs["policy"], neginf=0.0)
+            memory.add(o, a, rew, o_next, term)
+            o = o_next
+            idx = memory.sample_indices(args.batch_size, gen)
         lv = env.episode_log_vector
         ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
-        idx = memory.sample_indices(args.batch_size, gen)
         if fused is not None:
             fused.update(memory, idx)
         else:

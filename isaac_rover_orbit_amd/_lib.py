@@ -51,6 +51,8 @@ EXPORTS = [
     "rover_rollout_default_hparams", "rover_rollout_hparams_bytes", "rover_rollout_act", "rover_rollout_record",  # rover_rollout.h
     "rover_lift_rollout_default_hparams", "rover_lift_rollout_hparams_bytes", "rover_lift_rollout_act",  # rover_lift_rollout.h
     "rover_lift_rollout_record",
+    "rover_td3_collect_default_hparams", "rover_td3_collect_hparams_bytes", "rover_td3_collect_act",  # rover_td3_collect.h
+    "rover_td3_collect_record",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -142,6 +144,12 @@ class LiftRolloutHparams(C.Structure):
     _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("clip_actions", C.c_int32),
                 ("action_low", C.c_float), ("action_high", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
                 ("scaler_eps", C.c_float), ("scaler_clip", C.c_float), ("reward_scale", C.c_float)]
+
+
+class Td3CollectHparams(C.Structure):
+    """Mirror of ``struct rover_td3_collect_hparams`` (include/rover_td3_collect.h)."""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("explore", C.c_int32),
+                ("noise_std", C.c_float), ("noise_scale", C.c_float), ("action_low", C.c_float), ("action_high", C.c_float)]
 
 
 class RoverHipError(RuntimeError):
@@ -377,6 +385,11 @@ def load():
     lib.rover_lift_rollout_act.argtypes = [pd, vp, pd, vp, i32, C.POINTER(LiftRolloutHparams), C.c_uint64, vp, i32, vp, vp, vp, vp, vp,
                                            vp, vp, vp, vp, vp, vp]
     lib.rover_lift_rollout_record.argtypes = [vp, vp, vp, i32, f32, vp, vp, vp, vp, vp, vp]
+    tch = C.POINTER(Td3CollectHparams)
+    lib.rover_td3_collect_default_hparams.argtypes = [tch]
+    lib.rover_td3_collect_hparams_bytes.restype = C.c_size_t
+    lib.rover_td3_collect_act.argtypes = [pd, vp, i32, tch, C.c_uint64, vp, i32, vp, vp, vp, vp, vp]
+    lib.rover_td3_collect_record.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.c_int64, tch, C.c_uint64, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -404,6 +417,8 @@ def load():
         raise RoverHipError("struct rover_rollout_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_lift_rollout_hparams_bytes() != C.sizeof(LiftRolloutHparams):
         raise RoverHipError("struct rover_lift_rollout_hparams of librover_hip.so does not match the Python mirror")
+    if lib.rover_td3_collect_hparams_bytes() != C.sizeof(Td3CollectHparams):
+        raise RoverHipError("struct rover_td3_collect_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib

@@ -1,0 +1,283 @@
+"""The TD3 collector's specification (isaac_rover_orbit_amd.td3_collect.TorchTD3Collector) and the error behaviour of its C ABI
+(include/rover_td3_collect.h), on a host without a GPU.
+
+  * driven over the wrap, the spec leaves a memory bit-equal to nan_to_num + ReplayMemory.add, and every gather agrees
+  * the draws do not depend on how the envs are split, and the checkpoint is the counter
+  * the batch indices lie in [0, mem_rows), equal a big-integer evaluation of the formula and reach every row
+  * exploration is td3.explore on noise_std * eps; without it the actor's output passes unclamped
+  * the streams (noise, indices) are disjoint from each other, from the rollout collectors' and from the env's
+  * rover_td3_collect_act / rover_td3_collect_record return codes for bad arguments, nothing is launched
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from isaac_rover_orbit_amd import rollout as R
+from isaac_rover_orbit_amd import td3_collect as TC
+from isaac_rover_orbit_amd.td3 import ReplayMemory, explore
+
+F = 0xFFFFFFFF
+
+
+def _biteq(a, b):
+    if a.dtype == torch.bool or b.dtype == torch.bool:
+        return a.dtype == b.dtype and torch.equal(a, b)
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def _rows(n, step, seed=0):
+    """(n, 965) rows with -inf (ray misses), NaN, +inf and -0.0 at places that move with the step."""
+    g = torch.Generator().manual_seed(1000 * seed + step)
+    raw = torch.randn(n, 965, generator=g)
+    raw[torch.rand(n, 965, generator=g) < 1.0 / 16.0] = float("-inf")
+    raw[step % n, 5 + step] = float("nan")
+    raw[(step + 1) % n, 964] = float("inf")
+    raw[0, 0] = -0.0
+    return raw
+
+
+def _actor(o):
+    """A stand-in actor whose outputs leave [-1, 1] on some rows."""
+    return torch.stack([o[:, 4:100].sum(1) * 0.3, o[:, 0] - o[:, 200:260].sum(1) * 0.2], 1)
+
+
+def _transition(n, step):
+    g = torch.Generator().manual_seed(77 + step)
+    rew = torch.randn(n, generator=g)
+    rew[step % n] = float("nan") if step % 2 else float("-inf")
+    return rew, torch.rand(n, generator=g) < 0.4
+
+
+def _drive(col, n, steps, batch=None):
+    """begin + ``steps`` env steps; returns the per-step (actions, idx)."""
+    col.begin(_rows(n, 0))
+    out = []
+    for t in range(steps):
+        a = col.act(None).clone()
+        rew, term = _transition(n, t)
+        idx = col.record(_rows(n, t + 1), rew, term, batch)
+        out.append((a, None if idx is None else idx.clone()))
+    return out
+
+
+@pytest.mark.parametrize("M", [1, 3])
+def test_memory_equals_nan_to_num_and_add(M):
+    n, steps = 5, 2 * M + 3
+    mem, ref = ReplayMemory(M, n, device="cpu"), ReplayMemory(M, n, device="cpu")
+    col = TC.TorchTD3Collector(_actor, mem)
+    got = _drive(col, n, steps, batch=7)
+    o = torch.nan_to_num(_rows(n, 0), neginf=0.0)
+    for t in range(steps):                                         # the loop of examples/07_train_td3.py
+        a = _actor(o)
+        rew, term = _transition(n, t)
+        o_next = torch.nan_to_num(_rows(n, t + 1), neginf=0.0)
+        ref.add(o, a, rew, o_next, term)
+        o = o_next
+        assert _biteq(got[t][0], a)
+        assert got[t][1].dtype == torch.int64 and got[t][1].shape == (7,)
+        assert int(got[t][1].min()) >= 0 and int(got[t][1].max()) < min(t + 1, M) * n
+    assert not torch.isfinite(_rows(n, 1)).all() and torch.isfinite(mem.obs).all()
+    for name in ("obs", "actions", "rewards", "terminated", "ring_pos"):
+        assert _biteq(getattr(mem, name), getattr(ref, name)), name
+    assert len(mem) == len(ref) == M * n and (mem.memory_index, mem.filled, mem.cursor) == (ref.memory_index, ref.filled, ref.cursor)
+    every = torch.arange(len(mem))
+    for x, y in zip(mem.gather(every), ref.gather(every)):
+        assert _biteq(x, y)
+    # the collector cleared the skip record: a plain add after it writes its states slot again
+    assert mem._last_next is None
+    rew, term = _transition(n, 99)
+    mem.add(o + 1.0, _actor(o), rew, o, term)
+    assert torch.equal(mem.obs[(mem.cursor - 1) % mem.slots], o + 1.0)
+
+
+def test_draws_do_not_depend_on_the_split():
+    n, M = 8, 4
+    actor = lambda o: torch.stack([o[:, 0] * 0.5 + o[:, 5], o[:, 7] - o[:, 9] * 2.0], 1)   # noqa: E731  elementwise: a shard's rows are the whole's
+    whole = TC.TorchTD3Collector(actor, ReplayMemory(M, n, device="cpu"), seed=(9 << 32) | 5, noise_std=0.3)
+    parts = [TC.TorchTD3Collector(actor, ReplayMemory(M, 4, device="cpu"), seed=(9 << 32) | 5, env_id_offset=off, noise_std=0.3)
+             for off in (0, 4)]
+    raw = _rows(n, 0)
+    whole.begin(raw)
+    for p, sl in zip(parts, (slice(0, 4), slice(4, 8))):
+        p.begin(raw[sl])
+    for t in range(3):
+        a = whole.act(0.7)
+        b = torch.cat([p.act(0.7) for p in parts])
+        assert _biteq(a, b) and not _biteq(a, actor(whole.memory.obs[whole.memory.cursor]))
+        assert np.array_equal(whole.draws(t * 2), np.concatenate([p.draws(t * 2) for p in parts]))
+        rew, term = _transition(n, t)
+        raw = _rows(n, t + 1)
+        whole.record(raw, rew, term)
+        for p, sl in zip(parts, (slice(0, 4), slice(4, 8))):
+            p.record(raw[sl], rew[sl].contiguous(), term[sl].contiguous())
+    assert _biteq(whole.memory.actions, torch.cat([p.memory.actions for p in parts], 1))
+
+
+def test_checkpoint_is_the_counter():
+    n, M = 6, 5
+    col = TC.TorchTD3Collector(_actor, ReplayMemory(M, n, device="cpu"), seed=11, env_id_offset=32, noise_std=0.2)
+    _drive(col, n, 2, batch=9)
+    sd = col.state_dict()
+    assert sd == {"seed": 11, "counter": 4, "env_id_offset": 32}
+    fresh = TC.TorchTD3Collector(_actor, ReplayMemory(M, n, device="cpu"))
+    fresh.noise_std = 0.2
+    fresh.load_state_dict(sd)
+    fresh.memory.obs.copy_(col.memory.obs)
+    fresh.memory.cursor, fresh.memory.memory_index = col.memory.cursor, col.memory.memory_index
+    a, b = col.act(0.5), fresh.act(0.5)
+    assert _biteq(a, b) and not _biteq(a, _actor(col.memory.obs[col.memory.cursor]).clamp(-1, 1))
+    rew, term = _transition(n, 2)
+    i, j = col.record(_rows(n, 3), rew, term, 33), fresh.record(_rows(n, 3), rew, term, 33)
+    assert torch.equal(i, j) and col.state_dict() == fresh.state_dict() and col.counter == 6
+    other = TC.sample_indices(11, 4, 33, len(col.memory))          # another counter: other rows
+    assert not np.array_equal(other, i.numpy())
+
+
+def _philox_int(c, k):
+    """Philox4x32-10 in Python integers (Random123), independent of the numpy text under test."""
+    c, k = list(c), list(k)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k[0], p1 & F, (p0 >> 32) ^ c[3] ^ k[1], p0 & F]
+        k = [(k[0] + 0x9E3779B9) & F, (k[1] + 0xBB67AE85) & F]
+    return c
+
+
+@pytest.mark.parametrize("mem_rows", [1, 2, 3, 2 ** 25 + 1])
+def test_indices_against_big_integers(mem_rows):
+    B, seed, counter = 257, (3 << 32) | 42, (1 << 32) | 7
+    idx = TC.sample_indices(seed, counter, B, mem_rows)
+    assert idx.dtype == np.int64 and idx.shape == (B,) and idx.min() >= 0 and idx.max() < mem_rows
+    want = [(_philox_int((i >> 2, counter & F, counter >> 32, 0x54335300), (seed & F, seed >> 32))[i & 3] * mem_rows) >> 32 for i in range(B)]
+    assert idx.tolist() == want
+    if mem_rows > 3:
+        assert len(set(want)) > B // 2 and max(want) > mem_rows // 2
+
+
+def test_indices_reach_every_row_and_edges():
+    idx = TC.sample_indices(42, 0, 4096, 3)
+    assert sorted(set(idx.tolist())) == [0, 1, 2]
+    assert np.bincount(idx).min() > 4096 // 3 - 5 * 31          # 5 sigma of a binomial(4096, 1/3): sigma = 30.2
+    top = TC.sample_indices(42, 0, 64, 2 ** 32)                  # the largest mem_rows the product admits: the word itself
+    assert top.max() < 2 ** 32 and top.min() >= 0 and len(set(top.tolist())) == 64
+    for bad in (0, -1, 2 ** 32 + 1):
+        with pytest.raises(ValueError):
+            TC.sample_indices(42, 0, 4, bad)
+
+
+def test_exploration_is_td3_explore():
+    n, M = 33, 2
+    for kw, scale in ((dict(noise_std=0.4), None), (dict(noise_std=0.0), 0.9)):      # no exploration: the output, NOT clamped
+        col = TC.TorchTD3Collector(_actor, ReplayMemory(M, n, device="cpu"), **kw)
+        col.begin(_rows(n, 0))
+        a = col.act(scale)
+        mean = _actor(col.memory.obs[col.memory.cursor])
+        assert _biteq(a, mean) and (a.abs() > 1).any() and col.counter == 1 and _biteq(col.memory.actions[0], mean)
+    for clip in ((-1.0, 1.0), (-0.25, 0.5)):
+        col = TC.TorchTD3Collector(_actor, ReplayMemory(M, n, device="cpu"), seed=5, env_id_offset=3, noise_std=0.4, clip=clip)
+        col.begin(_rows(n, 0))
+        col.counter = 9
+        eps64 = R.standard_normals(5, 3 + np.arange(n), 9, 2, tag=TC.NOISE_TAG)
+        assert np.array_equal(col.draws(), eps64) and not np.array_equal(eps64, R.standard_normals(5, 3 + np.arange(n), 9, 2))
+        a = col.act(0.37)
+        mean = _actor(col.memory.obs[col.memory.cursor])
+        want = explore(mean, 0.4 * torch.from_numpy(eps64.astype(np.float32)), 0.37, *clip)
+        assert _biteq(a, want) and float(a.min()) >= clip[0] and float(a.max()) <= clip[1]
+        assert (a == clip[0]).any() and (a == clip[1]).any() and ((a > clip[0]) & (a < clip[1])).any()
+        assert col.counter == 10
+
+
+def test_stream_separation():
+    """Word 3 of every stream under one seed: the env's 0, 1, 2 (rover_hip.h), the rollout collectors' tags | pair, the noise tag |
+    pair and the index tag are pairwise distinct for every pair an action width <= 16 has."""
+    from isaac_rover_orbit_amd import lift_rollout as LR
+    words = [0, 1, 2, TC.INDEX_TAG]
+    for tag in (R.ROLLOUT_TAG, LR.LIFT_ROLLOUT_TAG, TC.NOISE_TAG):
+        words += [tag | p for p in range(8)]
+    assert len(set(words)) == len(words) == 28
+    assert TC.NOISE_TAG == 0x54443300 and TC.INDEX_TAG == 0x54335300
+
+
+def test_arguments_are_validated():
+    n, M = 4, 2
+    col = TC.TorchTD3Collector(_actor, ReplayMemory(M, n, device="cpu"))
+    rew, term = _transition(n, 0)
+    for bad in (_rows(n + 1, 0), _rows(n, 0).double(), _rows(n, 0)[:, :964]):
+        with pytest.raises(ValueError):
+            col.begin(bad)
+        with pytest.raises(ValueError):
+            col.record(bad, rew, term)
+    for r, t in ((rew.double(), term), (rew, term.float()), (rew[:3], term), (rew, term[:3])):
+        with pytest.raises(ValueError):
+            col.record(_rows(n, 1), r, t)
+    col.begin({"policy": _rows(n, 0)})                               # the env's dict is accepted
+    col.act()
+    assert col.record(_rows(n, 1), rew, term.to(torch.uint8) * 255) is None and col.memory.terminated[0].tolist() == term.tolist()
+    with pytest.raises(ValueError):
+        TC.TorchTD3Collector(_actor, ReplayMemory(M, n, device="cpu"), noise_std=-1.0)
+    with pytest.raises(ValueError):
+        TC.TorchTD3Collector(_actor, ReplayMemory(M, n, device="cpu"), clip=(1.0, -1.0))
+    with pytest.raises(ValueError):
+        TC.TorchTD3Collector(_actor, ReplayMemory(M, n, device="cpu", obs_dim=36))
+
+
+def test_abi_errors_are_codes():
+    """NULL, aliasing, mem_rows = 0 and every other invalid argument return ROVER_ERR_INVALID (1); an actor that is not the reference
+    architecture without a final activation returns ROVER_ERR_UNSUPPORTED (4).  Nothing reaches the GPU: the checks come before any
+    HIP call."""
+    from isaac_rover_orbit_amd import _lib
+    lib = _lib.load()
+    assert lib.rover_td3_collect_hparams_bytes() == C.sizeof(_lib.Td3CollectHparams) == 32
+    assert lib.rover_td3_collect_default_hparams(None) == 1
+    hp = _lib.Td3CollectHparams()
+    assert lib.rover_td3_collect_default_hparams(C.byref(hp)) == 0
+    assert (hp.seed_lo, hp.seed_hi, hp.env_id_offset, hp.explore) == (42, 0, 0, 0)
+    assert (hp.noise_std, hp.noise_scale, hp.action_low, hp.action_high) == (0.0, 1.0, -1.0, 1.0)
+    da, tanh = _lib.PolicyDesc(), _lib.PolicyDesc()
+    assert lib.rover_policy_default_desc(C.byref(da), 2, 0) == 0 and lib.rover_policy_default_desc(C.byref(tanh), 2, 1) == 0
+    # never dereferenced: every call below is refused before a launch
+    P, OBS, OUT, RING = 0x10000, 0x20000, 0x30000, 0x4000000
+    good = dict(actor=C.byref(da), p=P, copies=1, hp=C.byref(hp), counter=0, obs=OBS, n=16, mean=None, act=OUT, env_act=OUT, eps=None)
+
+    def act(**kw):
+        a = dict(good, **kw)
+        return lib.rover_td3_collect_act(a["actor"], a["p"], a["copies"], a["hp"], C.c_uint64(a["counter"]), a["obs"], a["n"], a["mean"],
+                                         a["act"], a["env_act"], a["eps"], None)
+
+    assert lib.rover_td3_collect_act(None, None, 0, None, C.c_uint64(0), None, 0, None, None, None, None, None) == 1
+    assert len(lib.rover_last_error()) > 0
+    for bad in (dict(actor=None), dict(hp=None), dict(p=None), dict(obs=None), dict(act=None), dict(env_act=None), dict(n=0), dict(n=-3),
+                dict(copies=0), dict(p=P + 4)):
+        assert act(**bad) == 1, bad
+    bad_hp = _lib.Td3CollectHparams.from_buffer_copy(hp)
+    bad_hp.explore, bad_hp.action_low, bad_hp.action_high = 1, 1.0, -1.0
+    assert act(hp=C.byref(bad_hp)) == 1 and b"action_low" in lib.rover_last_error()
+    bad_hp.explore = 2
+    assert act(hp=C.byref(bad_hp)) == 1
+    lift = _lib.PolicyDesc()
+    assert lib.rover_lift_policy_desc(C.byref(lift), 8) == 0
+    assert act(actor=C.byref(lift)) == 4 and act(actor=C.byref(tanh)) == 4
+    wide = _lib.PolicyDesc.from_buffer_copy(da)
+    wide.layers[5].N = 17
+    assert act(actor=C.byref(wide)) == 4
+
+    rgood = dict(raw=OBS, n=16, ring=RING, rew=OUT, term=OUT, rew_out=OUT, term_out=OUT, pos=OUT, pos_value=0, idx=OUT, batch=8, rows=16,
+                 hp=C.byref(hp))
+
+    def rec(**kw):
+        a = dict(rgood, **kw)
+        return lib.rover_td3_collect_record(a["raw"], a["n"], a["ring"], a["rew"], a["term"], a["rew_out"], a["term_out"], a["pos"],
+                                            a["pos_value"], a["idx"], a["batch"], a["rows"], a["hp"], C.c_uint64(0), None)
+
+    assert lib.rover_td3_collect_record(None, 1, None, None, None, None, None, None, 0, None, 0, 0, None, C.c_uint64(0), None) == 1
+    for bad in (dict(raw=None), dict(ring=None), dict(n=0), dict(n=-1), dict(ring=OBS), dict(ring=OBS + 4), dict(ring=OBS + 16 * 965 * 4 - 4),
+                dict(raw=RING + 4), dict(rows=0), dict(rows=-5), dict(rows=2 ** 32 + 1), dict(batch=0), dict(hp=None), dict(rew=None),
+                dict(term=None), dict(rew_out=None), dict(term_out=None), dict(rew=None, rew_out=None)):
+        assert rec(**bad) == 1, bad
+    assert rec(ring=OBS) == 1 and b"alias" in lib.rover_last_error()
+    assert rec(rows=0) == 1 and b"mem_rows" in lib.rover_last_error()
+    if not torch.cuda.is_available():
+        with pytest.raises(_lib.RoverHipError):
+            TC.TD3Collector(None, ReplayMemory(2, 4, device="cpu"))        # the product path fails loudly, no CPU fallback
