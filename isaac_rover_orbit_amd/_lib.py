@@ -53,6 +53,8 @@ EXPORTS = [
     "rover_lift_rollout_record",
     "rover_td3_collect_default_hparams", "rover_td3_collect_hparams_bytes", "rover_td3_collect_act",  # rover_td3_collect.h
     "rover_td3_collect_record",
+    "rover_trace_stream_bytes", "rover_trace_stage_pitch", "rover_trace_stage_bytes", "rover_trace_state_bytes",  # rover_trace.h
+    "rover_trace_init", "rover_trace_append", "rover_trace_commit_all", "rover_trace_gather", "rover_trace_drained",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -150,6 +152,12 @@ class Td3CollectHparams(C.Structure):
     """Mirror of ``struct rover_td3_collect_hparams`` (include/rover_td3_collect.h)."""
     _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("explore", C.c_int32),
                 ("noise_std", C.c_float), ("noise_scale", C.c_float), ("action_low", C.c_float), ("action_high", C.c_float)]
+
+
+class TraceStream(C.Structure):
+    """Mirror of ``struct rover_trace_stream`` (include/rover_trace.h)."""
+    _fields_ = [("src", C.c_void_p), ("src_pitch", C.c_int64), ("stage", C.c_void_p), ("stage_pitch", C.c_int64),
+                ("out", C.c_void_p), ("out_pitch", C.c_int64), ("row_bytes", C.c_int32), ("flags", C.c_int32)]
 
 
 class RoverHipError(RuntimeError):
@@ -390,6 +398,17 @@ def load():
     lib.rover_td3_collect_hparams_bytes.restype = C.c_size_t
     lib.rover_td3_collect_act.argtypes = [pd, vp, i32, tch, C.c_uint64, vp, i32, vp, vp, vp, vp, vp]
     lib.rover_td3_collect_record.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.c_int64, tch, C.c_uint64, vp]
+    trs = C.POINTER(TraceStream)
+    for name in ("rover_trace_stream_bytes", "rover_trace_stage_pitch", "rover_trace_stage_bytes", "rover_trace_state_bytes"):
+        getattr(lib, name).restype = C.c_size_t
+    lib.rover_trace_stage_pitch.argtypes = [i32]
+    lib.rover_trace_stage_bytes.argtypes = [i32, i32, i32]
+    lib.rover_trace_state_bytes.argtypes = [i32, i32]
+    lib.rover_trace_init.argtypes = [vp, i32, i32, vp]
+    lib.rover_trace_append.argtypes = [trs, i32, vp, i32, i32, i32, i32, vp, vp]
+    lib.rover_trace_commit_all.argtypes = [vp, i32, i32, i32, vp]
+    lib.rover_trace_gather.argtypes = [trs, i32, vp, i32, i32, i32, i32, i32, vp]
+    lib.rover_trace_drained.argtypes = [vp, i32, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -419,6 +438,8 @@ def load():
         raise RoverHipError("struct rover_lift_rollout_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_td3_collect_hparams_bytes() != C.sizeof(Td3CollectHparams):
         raise RoverHipError("struct rover_td3_collect_hparams of librover_hip.so does not match the Python mirror")
+    if lib.rover_trace_stream_bytes() != C.sizeof(TraceStream):
+        raise RoverHipError("struct rover_trace_stream of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib
