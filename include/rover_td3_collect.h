@@ -8,6 +8,7 @@
  *     mean     = actor(ring[cursor])                                       (exactly rover_policy_forward)
  *     eps      = N(0, 1) from Philox4x32-10, keyed by (seed, global env id, counter, action pair)
  *     act      = explore ? clamp(mean + (noise_std * eps) * noise_scale, low, high) : mean
+ *                (clamp as torch.clamp: a NaN sum stays NaN, it does not become `low`; +inf / -inf clamp to high / low)
  *     env.step(act)
  *     ring[cursor + 1] = nan_to_num(raw_obs, nan=0, posinf=FLT_MAX, neginf=0);  rewards[k], terminated[k], ring_pos[k]
  *     idx[i]   = uniform row index in [0, mem_rows) from Philox4x32-10, keyed by (seed, counter, i)

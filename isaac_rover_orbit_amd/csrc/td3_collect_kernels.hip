@@ -348,11 +348,12 @@ __global__ __launch_bounds__(TDC_THREADS) void rover_td3_collect_act_kernel(rove
     const size_t o = (size_t)(row0 + r) * N + c;
     if (live && L.mean_out) L.mean_out[o] = y;
 
-    // ---- exploration epilogue (td3.explore): noise_std * eps, * scale, + mean as three separate operations, then the clamp
+    // ---- exploration epilogue (td3.explore): noise_std * eps, * scale, + mean as three separate operations, then the clamp (a NaN
+    // sum stays NaN, as under torch.clamp)
     float a = y;
     if (L.hp.explore) {
         uint32_t w4[4];
-        philox4x32((uint32_t)(L.hp.env_id_offset + row0 + r), L.ctr_lo, L.ctr_hi, NOISE_TAG | (uint32_t)(c >> 1), L.hp.seed_lo, L.hp.seed_hi, w4);
+        philox4x32((uint32_t)L.hp.env_id_offset + (uint32_t)(row0 + r), L.ctr_lo, L.ctr_hi, NOISE_TAG | (uint32_t)(c >> 1), L.hp.seed_lo, L.hp.seed_hi, w4);
         const float u1 = ((float)(w4[0] >> 9) + 0.5f) * 0x1p-23f, u2 = ((float)(w4[1] >> 9) + 0.5f) * 0x1p-23f;   // exact, inside (0, 1)
         const float rho = sqrtf(-2.0f * logf(u1));
         float sn, cs;
@@ -361,7 +362,8 @@ __global__ __launch_bounds__(TDC_THREADS) void rover_td3_collect_act_kernel(rove
         float noise = L.hp.noise_std * eps;
         noise = noise * L.hp.noise_scale;
         a = y + noise;
-        a = fminf(fmaxf(a, L.hp.action_low), L.hp.action_high);
+        const float cl = fminf(fmaxf(a, L.hp.action_low), L.hp.action_high);
+        a = a != a ? a : cl;                        // torch.clamp keeps a NaN; fmaxf alone would turn it into action_low
         if (live && L.eps_out) L.eps_out[o] = eps;
     }
     if (live) {

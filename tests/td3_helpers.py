@@ -120,3 +120,70 @@ def assert_same_trainer(a, b, skip_state_words=()):
         # equal as numbers (a NaN on either side fails) and as bit patterns (-0 is not +0)
         assert torch.equal(x, y) and torch.equal(x.view(torch.int32), y.view(torch.int32)), name
     assert a.critic_updates == b.critic_updates
+
+
+# ---- the collector's edge cases (test_td3_collect.py on the spec, test_gpu_td3_collect_edges.py on the kernels)
+INF = float("inf")
+# exploration hyper-parameters under explore = 1: name -> (noise_std, noise_scale, low, high).  1e30 * |eps| * 1e30 overflows fp32
+# for every |eps| > 3.5e-22, i.e. for every draw: the second product is +/-inf and the clamp returns a bound.
+EXPLORE_CASES = {"low_equals_high": (0.3, 0.7, 0.25, 0.25),
+                 "unbounded": (0.3, 0.7, -INF, INF),
+                 "zero_scale": (0.3, 0.0, -1.0, 1.0),
+                 "negative_scale": (0.3, -0.7, -1.0, 1.0),
+                 "overflowing_noise": (1e30, 1e30, -0.5, 0.75)}
+
+# the top of the draws' ranges: the last of 33 ids is 2**31 - 2, every key bit set, counters around 2**32 and at 2**64 - 1
+TOP_OFFSET, TOP_SEED, TOP_COUNTERS = 2 ** 31 - 34, 2 ** 64 - 1, (2 ** 32 - 1, 2 ** 32, 2 ** 64 - 1)
+
+# index draws: the top of mem_rows with batches that end one and three positions into a Philox block, and one below / above 1024
+INDEX_MEM_ROWS, INDEX_BATCHES = (2 ** 31, 2 ** 32 - 1, 2 ** 32), (3, 5, 1023, 1025)
+
+
+def check_explore_case(name, act, mean, eps):
+    """``act`` bit for bit against td3.explore in fp32 torch on ``mean`` and ``eps``, and what the case is there to show."""
+    from isaac_rover_orbit_amd.td3 import explore
+    std, scale, low, high = EXPLORE_CASES[name]
+    want = explore(mean, std * eps, scale, low, high)
+    assert same_bits_nan_aware(act, want), name
+    if name == "low_equals_high":
+        assert bool((act == low).all())
+    elif name == "unbounded":
+        assert same_bits_nan_aware(act, mean + (std * eps) * scale) and not same_bits_nan_aware(act, (mean + (std * eps) * scale).clamp(-1, 1))
+    elif name == "zero_scale":
+        assert same_bits_nan_aware(act, (mean + (std * eps) * 0.0).clamp(low, high))
+    elif name == "negative_scale":
+        plus = explore(mean, std * eps, -scale, low, high)
+        assert not same_bits_nan_aware(act, plus)
+    elif name == "overflowing_noise":
+        assert bool(((act == low) | (act == high)).all()) and bool((act == low).any()) and bool((act == high).any())
+        assert bool(torch.isinf((std * eps) * scale).all())
+
+
+def same_bits_nan_aware(a, b):
+    """NaN at the same places (whatever its payload) and every other element equal on the bits."""
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    na, nb = torch.isnan(a), torch.isnan(b)
+    x, y = a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)
+    return bool(torch.equal(na, nb)) and bool(torch.equal(x[~na], y[~nb]))
+
+
+def eps_float64_by_hand(seed, ids, counter, width, tag):
+    """The exploration draws in Python integers and math.* (Random123's Philox4x32-10, the uniforms and Box-Muller of
+    include/rover_td3_collect.h), independent of the numpy text of rollout.standard_normals."""
+    import math
+    F = 0xFFFFFFFF
+    out = []
+    for g in ids:
+        row = []
+        for p in range((width + 1) // 2):
+            c, k = [int(g) & F, counter & F, (counter >> 32) & F, tag | p], [seed & F, (seed >> 32) & F]
+            for _ in range(10):
+                p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+                c = [(p1 >> 32) ^ c[1] ^ k[0], p1 & F, (p0 >> 32) ^ c[3] ^ k[1], p0 & F]
+                k = [(k[0] + 0x9E3779B9) & F, (k[1] + 0xBB67AE85) & F]
+            u1, u2 = ((c[0] >> 9) + 0.5) * 2.0 ** -23, ((c[1] >> 9) + 0.5) * 2.0 ** -23
+            rho = math.sqrt(-2.0 * math.log(u1))
+            row += [rho * math.cos(2.0 * math.pi * u2), rho * math.sin(2.0 * math.pi * u2)]
+        out.append(row[:width])
+    return out

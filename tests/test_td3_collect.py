@@ -7,6 +7,9 @@
   * exploration is td3.explore on noise_std * eps; without it the actor's output passes unclamped
   * the streams (noise, indices) are disjoint from each other, from the rollout collectors' and from the env's
   * rover_td3_collect_act / rover_td3_collect_record return codes for bad arguments, nothing is launched
+  * the edge cases of tests/test_gpu_td3_collect_edges.py (tests/td3_helpers.py) on the spec: degenerate and infinite bounds, zero,
+    negative and overflowing noise, a non-finite actor output, the top of the id / seed / counter ranges against a by-hand
+    evaluation, indices at mem_rows up to 2**32 with batches that end inside a Philox block
 """
 import ctypes as C
 
@@ -17,6 +20,8 @@ import torch
 from isaac_rover_orbit_amd import rollout as R
 from isaac_rover_orbit_amd import td3_collect as TC
 from isaac_rover_orbit_amd.td3 import ReplayMemory, explore
+from td3_helpers import (EXPLORE_CASES, INDEX_BATCHES, INDEX_MEM_ROWS, TOP_COUNTERS, TOP_OFFSET, TOP_SEED, check_explore_case,
+                         eps_float64_by_hand, same_bits_nan_aware)
 
 F = 0xFFFFFFFF
 
@@ -281,3 +286,63 @@ def test_abi_errors_are_codes():
     if not torch.cuda.is_available():
         with pytest.raises(_lib.RoverHipError):
             TC.TD3Collector(None, ReplayMemory(2, 4, device="cpu"))        # the product path fails loudly, no CPU fallback
+
+
+# ------------------------------------------------------------------------------- the edge cases the GPU runs, on the spec
+@pytest.mark.parametrize("name", sorted(EXPLORE_CASES))
+def test_exploration_hyper_parameters(name):
+    n, (std, scale, low, high) = 33, EXPLORE_CASES[name]
+    col = TC.TorchTD3Collector(_actor, ReplayMemory(2, n, device="cpu"), seed=5, env_id_offset=3, noise_std=std, clip=(low, high))
+    col.begin(_rows(n, 0))
+    eps = torch.from_numpy(col.draws().astype(np.float32))
+    a = col.act(scale)
+    check_explore_case(name, a, _actor(col.memory.obs[col.memory.cursor]), eps)
+
+
+def test_a_non_finite_actor_output():
+    """NaN in column 0 and +inf in column 1: both pass through without exploration; with it NaN stays NaN (torch.clamp) and +inf
+    becomes the upper bound."""
+    n = 5
+
+    def actor(o):
+        a = torch.stack([o[:, 0], o[:, 1], o[:, 2]], 1)
+        a[:, 0], a[:, 1] = float("nan"), float("inf")
+        return a
+    for scale in (None, 0.7):
+        col = TC.TorchTD3Collector(actor, ReplayMemory(2, n, device="cpu", act_dim=3), noise_std=0.3, clip=(-0.5, 0.75))
+        col.begin(_rows(n, 0))
+        eps = torch.from_numpy(col.draws().astype(np.float32))
+        a = col.act(scale)
+        assert torch.isnan(a[:, 0]).all() and same_bits_nan_aware(col.memory.actions[0], a)
+        if scale is None:
+            assert (a[:, 1] == float("inf")).all() and _biteq(a[:, 2], col.memory.obs[col.memory.cursor][:, 2])
+        else:
+            assert (a[:, 1] == 0.75).all() and torch.isfinite(a[:, 2]).all()
+            assert same_bits_nan_aware(a, explore(actor(col.memory.obs[col.memory.cursor]), 0.3 * eps, scale, -0.5, 0.75))
+
+
+@pytest.mark.parametrize("counter", TOP_COUNTERS)
+def test_draws_at_the_top_of_the_ranges(counter):
+    n, A = 33, 3
+    col = TC.TorchTD3Collector(_actor, ReplayMemory(2, n, device="cpu"), seed=TOP_SEED, env_id_offset=TOP_OFFSET, noise_std=0.3)
+    col.A, col.counter = A, counter
+    ids = TOP_OFFSET + np.arange(n)
+    assert ids[-1] == 2 ** 31 - 2
+    got = col.draws()
+    want = np.array(eps_float64_by_hand(TOP_SEED, ids, counter, A, TC.NOISE_TAG))
+    assert got.shape == want.shape == (n, A) and np.abs(got - want).max() <= 1e-12      # two float64 evaluations of one formula
+    assert not np.array_equal(got, R.standard_normals(TOP_SEED, ids, (counter + 1) % 2 ** 64, A, tag=TC.NOISE_TAG))
+    lo, hi = R.standard_normals(TOP_SEED, ids[:16], counter, A, tag=TC.NOISE_TAG), R.standard_normals(TOP_SEED, ids[16:], counter, A, tag=TC.NOISE_TAG)
+    assert np.array_equal(got, np.concatenate([lo, hi]))                               # the split, at that offset
+
+
+@pytest.mark.parametrize("mem_rows", INDEX_MEM_ROWS)
+def test_indices_at_the_top_of_mem_rows(mem_rows):
+    seed, counter = TOP_SEED, 2 ** 32 - 1
+    for B in INDEX_BATCHES:
+        idx = TC.sample_indices(seed, counter, B, mem_rows)
+        assert idx.dtype == np.int64 and idx.shape == (B,) and idx.min() >= 0 and idx.max() < mem_rows
+        want = [(_philox_int((i >> 2, counter & F, counter >> 32, 0x54335300), (seed & F, seed >> 32))[i & 3] * mem_rows) >> 32 for i in range(B)]
+        assert idx.tolist() == want
+        if B > 1000:
+            assert idx.max() >= 2 ** 31 or mem_rows == 2 ** 31                          # the top half is reached: no int32 wrap

@@ -8,6 +8,9 @@
   * EpisodeRecorder's ValueErrors hold
   * every invalid argument of the C ABI returns ROVER_ERR_INVALID (1) and nothing is launched
   * device_bytes is the sum of what the class allocates
+  * the edge cases of tests/test_gpu_trace_collect_edges.py (tests/trace_cases.py) on the model: row widths around 16 and 4096 bytes in
+    every dtype, sixteen streams, pitched sources, uint8 flags of 2 and 255, ring and descriptor overrun with the drain held off,
+    the smallest ring, the commit's carry over three chunks, the close paths and pieces around a wave of rows
 """
 import ctypes as C
 
@@ -15,7 +18,8 @@ import numpy as np
 import pytest
 import torch
 
-from trace_cases import EXTRAS, assert_same_files, drive
+from trace_cases import (CARRY_KW, CARRY_PATTERNS, EXTRAS, OVERRUN, OVERRUN_KW, WIDTH_CASES, WIDTH_STEPS, Paired, assert_same_files,
+                         assert_same_state, drive, drive_overrun, model_base, pitched_sources, uint8_done)
 
 from isaac_rover_orbit_amd import trace_collect as TC
 from isaac_rover_orbit_amd.trace import load_trace
@@ -221,3 +225,127 @@ def test_device_bytes_is_what_is_allocated(tmp_path, extras, piece):
     # sizing a run: 750-row episodes at 4096 envs take 3.9 KB per env step without extras, 61.5 KB with the depth image
     per_row = TC.TraceCollector.device_bytes(4096, 965, 2, None, 750, 64) / (4096 * 814)
     assert 3884 <= per_row < 3950
+
+
+# ------------------------------------------------------------------------------- the edge cases the GPU runs, on the model
+@pytest.mark.parametrize("n", [5, 67])
+@pytest.mark.parametrize("case", sorted(WIDTH_CASES))
+def test_row_widths_and_dtypes(tmp_path, case, n):
+    """Rows of 16, 17, 18, 20, 24 and 8 bytes, of 4096, 4097, 4098 and 4100 bytes, in uint8, int16, float16, float32, float64 and
+    int64; twelve extras are sixteen streams.  A second model runs behind ``Paired``: the state comparison itself is rehearsed."""
+    ex, max_rows, steps = WIDTH_CASES[case], 40 if n == 5 else 1000, WIDTH_STEPS[n]
+
+    def make(base):
+        return Paired(_make(n, max_rows, ex)(base), _make(n, max_rows, ex)(model_base(base)))
+    ref, col, fr, fg = drive(make, str(tmp_path), n, steps, 0.15, 6, extras=ex, max_rows=max_rows)
+    assert sum(assert_same_files(fr, fg)) == steps * n and col.checks >= steps // 3
+    assert_same_files(fr, col.model_files)
+    d = load_trace(fg[0])
+    for k, p in ex.items():
+        assert d[k].dtype == np.dtype(p["dtype"]) and d[k].shape[1:] == tuple(p["shape"])
+
+
+def test_a_thirteenth_extra_is_refused(tmp_path):
+    ex = dict(WIDTH_CASES["sixteen_streams"], one_more={"shape": (1,), "dtype": np.float32})
+    with pytest.raises(ValueError, match="at most 16"):
+        TC.TorchTraceCollector(str(tmp_path / "run"), 2, 7, 2, ex, **KW)
+
+
+@pytest.mark.parametrize("obs_dim", [7, 965])
+def test_sources_with_a_pitch(tmp_path, obs_dim):
+    n = 5
+    ref, col, fr, fg = drive(_make(n, obs_dim=obs_dim), str(tmp_path), n, 20, 0.15, 6, obs_dim=obs_dim, to_device=pitched_sources(n, obs_dim))
+    assert sum(assert_same_files(fr, fg)) == 20 * n
+
+
+def test_uint8_done_flags(tmp_path):
+    n = 5
+    ref, col, fr, fg = drive(_make(n), str(tmp_path), n, 20, 0.3, 6, to_device=uint8_done())
+    assert sum(assert_same_files(fr, fg)) == 20 * n
+    flags = np.concatenate([load_trace(f)["terminated"].view(np.uint8).ravel() for f in fg])
+    assert set(flags.tolist()) == {0, 1}
+
+
+@pytest.mark.parametrize("kind", sorted(OVERRUN))
+def test_overrun_with_the_drain_held_off(tmp_path, kind):
+    """The status bit appears at the step worked out in trace_cases.py and not before, nothing is written past desc_cap, a refused
+    row does not overwrite a staged one, and the drain names what was overrun."""
+    n = 5
+    col = TC.TorchTraceCollector(str(tmp_path / "run"), n, 7, 2, EXTRAS, **OVERRUN_KW)
+    snap = {}
+
+    def after(t, want):
+        assert int(col.state[TC.W_STATUS]) == want, (t, int(col.state[TC.W_STATUS]), want)
+        assert col.guards_intact()
+        if t == OVERRUN[kind]["first"] - 1:
+            snap["stage"] = [s.clone() for s in col.stage]
+    drive_overrun([col], kind, n, after)
+    if kind == "ring":
+        assert all(torch.equal(a, b) for a, b in zip(snap["stage"], col.stage))        # the refused rows changed nothing
+        assert int(col.state[TC.W_COUNT]) == 3 * n and int(col.state[TC.W_ROWS]) == 9 * n
+    else:
+        assert int(col.state[TC.W_COUNT]) == 8 * n and int(col.state[TC.W_ROWS]) == 8 * n
+    with pytest.raises(TC.TraceOverflowError, match=OVERRUN[kind]["match"]):
+        col.drain()
+    col.close()
+
+
+@pytest.mark.parametrize("n", [1, 257])
+def test_smallest_geometry(tmp_path, n):
+    """max_episode_rows = 1, drain_interval = 1: rings of two rows, every env done at every step, pieces of one row."""
+    kw = dict(max_episode_rows=1, drain_interval=1, piece_rows=1)
+    ref, col, fr, fg = drive(_make(n, 1000, None, **kw), str(tmp_path), n, 6, 1.0, 1, extras=None, max_rows=1000)
+    assert col.R == 2 and sum(assert_same_files(fr, fg)) == 6 * n
+
+
+@pytest.mark.parametrize("n", [513, 600])
+@pytest.mark.parametrize("pattern", sorted(CARRY_PATTERNS))
+def test_commit_carry_over_chunks(tmp_path, pattern, n):
+    ref, col, fr, fg = drive(_make(n, 10_000, None, **CARRY_KW), str(tmp_path), n, 8, 0.0, 8, extras=None, max_rows=10_000,
+                             done_fn=CARRY_PATTERNS[pattern], force=False)
+    assert sum(assert_same_files(fr, fg)) == 8 * n
+
+
+def test_close_paths(tmp_path):
+    n = 5
+    # every env holds an open episode, two rows of it staged since the last drain
+    ref, col, fr, fg = drive(_make(n), str(tmp_path / "a"), n, 5, 0.0, 6, force=False)
+    assert assert_same_files(fr, fg) == [25]
+    # every env done at step 2, where a drain runs: close() has nothing to commit
+    ref, col, fr, fg = drive(_make(n), str(tmp_path / "b"), n, 3, 0.0, 6, done_fn=lambda t, n_: torch.full((n_,), t == 2), force=False)
+    assert assert_same_files(fr, fg) == [15] and int(col.state[TC.W_COUNT]) == 0
+    assert col.close() == fg                                                           # a second close changes nothing
+    assert assert_same_files(fr, fg) == [15]
+
+
+@pytest.mark.parametrize("piece", [63, 64, 65])
+def test_piece_sizes_around_a_wave_of_rows(tmp_path, piece):
+    n = 67
+    ref, col, fr, fg = drive(_make(n, 1000, guard_bytes=64, piece_rows=piece), str(tmp_path), n, 20, 0.15, 6, max_rows=1000,
+                             hook=lambda c, t: c.guards_intact() or pytest.fail("a canary changed"))
+    assert sum(assert_same_files(fr, fg)) == 20 * n
+
+
+def test_assert_same_state_sees_a_difference(tmp_path):
+    """The helper the GPU tests lean on: equal for two models driven alike, and it fails on one changed word of each kind."""
+    n = 5
+    cols = [TC.TorchTraceCollector(str(tmp_path / f"run{i}"), n, 7, 2, EXTRAS, **OVERRUN_KW) for i in range(2)]
+    g = torch.Generator().manual_seed(0)
+    from trace_cases import step_tensors
+    for t in range(2):
+        obs, act, rew, info = step_tensors(g, n, 7, 2, EXTRAS)
+        for c in cols:
+            c.append(obs, act, rew, torch.arange(n) % 2 == t, info)
+    assert_same_state(*cols)
+    H, d0 = TC.HEADER_WORDS, TC.desc_word(n)
+    assert int(cols[0].state[TC.W_COUNT]) == 5
+    for word in (TC.W_COUNT, TC.W_STATUS, TC.W_ROWS, H + 1, H + n + 1, H + 2 * n + 1, d0 + 4 * 4 + 3):
+        cols[1].state[word] += 1
+        with pytest.raises(AssertionError):
+            assert_same_state(*cols)
+        cols[1].state[word] -= 1
+    assert_same_state(*cols)
+    cols[1].state[d0 + 4 * 5] += 1                                                     # behind the last descriptor: not compared
+    assert_same_state(*cols)
+    for c in cols:
+        c.close()
