@@ -14,6 +14,7 @@
  *     eps      = N(0, 1) from Philox4x32-10, keyed by (seed, global env id, step counter, action pair)
  *     act      = mean + expf(clamp(log_std)) * eps     (a separate multiply and add)
  *     env_act  = clip_actions ? clamp(act, low, high) : act
+ *                (clamp as torch.clamp: a NaN stays NaN; +inf / -inf clamp to high / low)
  *     logp     = sum_c (-0.5 x_c^2 - ls_c - 0.9189385332),  x_c = (act_c - mean_c) / std_c
  *                                                     (the expression rover_lift_ppo_minibatch evaluates for the new policy,
  *                                                      operation for operation: the sum starts at 0 and runs in column order)

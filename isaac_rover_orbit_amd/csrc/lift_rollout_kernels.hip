@@ -191,7 +191,7 @@ __global__ __launch_bounds__(RT) void lift_rollout_act_kernel(LroArgs A, const f
     for (int j = 0; j < 4; ++j) {
         const int r = 4 * akq + j;
         uint32_t w4[4];
-        philox4x32((uint32_t)(A.hp.env_id_offset + row0 + r), A.ctr_lo, A.ctr_hi, LRO_TAG | (uint32_t)(c >> 1), A.hp.seed_lo, A.hp.seed_hi, w4);
+        philox4x32((uint32_t)A.hp.env_id_offset + (uint32_t)(row0 + r), A.ctr_lo, A.ctr_hi, LRO_TAG | (uint32_t)(c >> 1), A.hp.seed_lo, A.hp.seed_hi, w4);
         const float u1 = ((float)(w4[0] >> 9) + 0.5f) * 0x1p-23f, u2 = ((float)(w4[1] >> 9) + 0.5f) * 0x1p-23f;   // exact, inside (0, 1)
         const float rho = sqrtf(-2.0f * logf(u1));
         float sn, cs;
@@ -199,7 +199,8 @@ __global__ __launch_bounds__(RT) void lift_rollout_act_kernel(LroArgs A, const f
         const float eps = (c & 1) ? rho * sn : rho * cs;
         const float noise = sd * eps;
         const float a = y[j] + noise;           // a separate multiply and add
-        const float ea = A.hp.clip_actions ? fminf(fmaxf(a, A.hp.action_low), A.hp.action_high) : a;
+        const float cl = fminf(fmaxf(a, A.hp.action_low), A.hp.action_high);
+        const float ea = (A.hp.clip_actions && a == a) ? cl : a;   // torch.clamp keeps a NaN; fmaxf alone would turn it into action_low
         const float x = (a - y[j]) / sd;        // lift_rows_kernel forms x, the term and the row sum below the same way
         const float term = -0.5f * x * x - ls - 0.9189385332f;
         float lp = 0.0f;                        // column 0 first, then the others in order (all 64 lanes take part)

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .lift_ppo import OBS_DIM, gaussian_logp
+from .lift_ppo import OBS_DIM
 from .rollout import _MASK, standard_normals
 
 LIFT_ROLLOUT_TAG = 0x4C524F00     # "LRO\0": word 3 of the Philox counter, | action pair (the lift env's draws have word 3 in {0, 1})
@@ -78,10 +78,12 @@ class TorchLiftRollout(_LiftRolloutBase):
     output -> value (``None``: the raw critic output)."""
 
     def __init__(self, actor, critic, log_std, state_pre, value_inv, num_envs: int, horizon: int, seed: int = 42,
-                 env_id_offset: int = 0, clip_actions: bool = False, reward_scale: float = 0.01, device="cpu"):
+                 env_id_offset: int = 0, clip_actions: bool = False, reward_scale: float = 0.01, device="cpu",
+                 log_std_min: float = LOG_STD_MIN, log_std_max: float = LOG_STD_MAX):
         super().__init__(log_std, num_envs, horizon, seed, env_id_offset, clip_actions, device)
         self.actor, self.critic, self.state_pre, self.value_inv = actor, critic, state_pre, value_inv
         self.reward_scale = float(np.float32(reward_scale))
+        self.log_std_min, self.log_std_max = float(log_std_min), float(log_std_max)
 
     def draws(self, counter: int | None = None) -> np.ndarray:
         """float64 eps (n, A) of step ``counter`` (default: the next one)."""
@@ -101,10 +103,10 @@ class TorchLiftRollout(_LiftRolloutBase):
         mean = self.actor(s)
         if eps is None:
             eps = torch.from_numpy(self.draws().astype(np.float32)).to(self.device)
-        log_std = self.log_std.detach().to(self.device)
-        std = log_std.clamp(LOG_STD_MIN, LOG_STD_MAX).exp()
+        ls = self.log_std.detach().to(self.device).clamp(self.log_std_min, self.log_std_max)
+        std = ls.exp()
         a = mean + std * eps
-        self.logp[t] = gaussian_logp(mean, log_std, a)
+        self.logp[t] = (-0.5 * ((a - mean) / std) ** 2 - ls - 0.9189385332).sum(-1)      # lift_ppo.gaussian_logp under the window
         self.val[t] = self._value(s)
         self.obs[t], self.mean[t], self.actions[t] = o, mean, a
         self.counter += 1
@@ -116,8 +118,9 @@ class TorchLiftRollout(_LiftRolloutBase):
         self.done[t] = (terminated.bool() | truncated.bool()).float()
         if log is not None:
             k = log[8]                                                # envs reset in this step; log[0:8] are their means
-            self.ep_sum += torch.where(k > 0, log[0:8] * torch.where(torch.arange(8, device=self.device) < 6, k, 1.0), 0.0)
-            self.ep_count += k
+            add = log[0:8] * torch.where(torch.arange(8, device=self.device) < 6, k, 1.0)
+            self.ep_sum.copy_(torch.where(k > 0, self.ep_sum + add, self.ep_sum))      # the header's "if k > 0": a zero, negative
+            self.ep_count.copy_(torch.where(k > 0, self.ep_count + k, self.ep_count))  # or NaN k moves no bit of the tally
 
     @torch.no_grad()
     def last_value(self, obs) -> torch.Tensor:

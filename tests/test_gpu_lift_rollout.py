@@ -21,40 +21,13 @@ import numpy as np
 import pytest
 import torch
 
+from lift_rollout_helpers import EPS_TOL, FILL, GUARD, LS_CLAMPED, ULP, _biteq, _errors, _make_trainer, _run
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ULP = 2.0 ** -23
-EPS_TOL = 2.05e-06
-TAG = 0x4C524F00
 A = 8
 LOGP_TOL = (8 + (A - 2) / 2) * ULP
-LOG_STD = (0.0, -0.7, 0.3, 2.5, -21.0, 1.0, -3.0, 0.1)          # inside, above (2.5) and below (-21) the clamps [-20, 2]
-LS_CLAMPED = np.clip(np.array(LOG_STD, dtype=np.float32).astype(np.float64), -20.0, 2.0)
-GUARD, FILL = 16, 777.0
-OUT_KEYS = ("obs", "mean", "val", "act", "env_act", "logp", "eps")
-
-
-def _biteq(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def _make_trainer(seed=3, **kw):
-    from isaac_rover_orbit_amd import lift_ppo as LP
-    torch.manual_seed(seed)
-    policy, value = LP.LiftMLP(LP.ACT_DIM, log_std=True), LP.LiftMLP(1)
-    with torch.no_grad():
-        policy.log_std_parameter.copy_(torch.tensor(LOG_STD))
-    tr = LP.FusedLiftPPO(policy.state_dict(), value.state_dict(), lr=1e-3, **kw)
-    rng = np.random.RandomState(seed)
-    mean = rng.uniform(-1.0, 1.0, 36)
-    mean[::5] = 3.0
-    mean[2::5] = -3.0
-    var = rng.uniform(0.25, 4.0, 36)
-    var[7] = 0.0                                                  # (o - mean) / (0 + 1e-8): +-5 after the clamp, 0 when o == mean
-    tr.state_scaler.copy_(torch.from_numpy(np.concatenate([mean, var, [100.0]])))
-    tr.value_scaler.copy_(torch.tensor([-1.5, 4.0, 50.0], dtype=torch.float64))
-    return tr
 
 
 @pytest.fixture(scope="module")
@@ -68,46 +41,10 @@ def _rows(n, seed=0):
     return o.cuda()
 
 
-def _shapes(n):
-    return {"obs": (n, 36), "mean": (n, A), "val": (n, 1), "act": (n, A), "env_act": (n, A), "logp": (n,), "eps": (n, A)}
-
-
-def _run(tr, o, counter=0, outs=OUT_KEYS, value_scaler=True, log_std=None, **hp):
-    """One launch; every output is the middle of a buffer with GUARD sentinel rows on both sides, which must come back untouched."""
-    from isaac_rover_orbit_amd import lift_rollout as LR
-    n = o.shape[0]
-    h = LR.default_hparams()
-    for k, v in hp.items():
-        setattr(h, k, v)
-    full = {k: torch.full((s[0] + 2 * GUARD,) + s[1:], FILL, device="cuda") for k, s in _shapes(n).items() if k in outs or k in ("mean", "val")}
-    view = {k: v[GUARD:GUARD + n] for k, v in full.items()}
-    LR.lift_rollout_act(tr.actor, tr.critic, tr.log_std if log_std is None else log_std, o, counter, h, tr.state_scaler,
-                        tr.value_scaler if value_scaler else None, **{k + "_out": view.get(k) for k in OUT_KEYS})
-    torch.cuda.synchronize()
-    for k, v in full.items():
-        assert (v[:GUARD] == FILL).all() and (v[GUARD + n:] == FILL).all(), f"{k}: a guard row was written"
-    return {k: v.clone() for k, v in view.items()}
-
-
 def _reference(tr, o):
     s = tr.standardize(o)
     v = tr.critic(s)
     return s, tr.actor(s), v, tr.standardize(v, "value", inverse=True)
-
-
-def _errors(o, n, counter=0, seed=42, offset=0):
-    """(|eps - float64 spec|, act error / max(|mean|, |std eps|), logp error / sum_c (0.5 x_c**2 + |ls_c| + 0.919)) maxima."""
-    from isaac_rover_orbit_amd import rollout as R
-    eps64 = R.standard_normals(seed, offset + np.arange(n), counter, A, tag=TAG)
-    eps, m, a = (o[k].cpu().numpy().astype(np.float64) for k in ("eps", "mean", "act"))
-    noise = np.exp(LS_CLAMPED) * eps
-    d_act = np.abs(a - (m + noise)) / np.maximum(np.abs(m), np.abs(noise))
-    x = (a - m) / np.exp(LS_CLAMPED)
-    want = (-0.5 * x * x - LS_CLAMPED - 0.9189385332).sum(1)
-    scale = (0.5 * x * x + np.abs(LS_CLAMPED) + 0.919).sum(1)
-    assert np.isfinite(want).all()
-    d_lp = np.abs(o["logp"].cpu().numpy().astype(np.float64) - want) / scale
-    return float(np.abs(eps - eps64).max()), float(d_act.max()), float(d_lp.max())
 
 
 @pytest.mark.parametrize("n", [1, 15, 16, 17, 33, 257])

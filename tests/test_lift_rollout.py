@@ -7,6 +7,8 @@ C ABI (include/rover_lift_rollout.h), on a host without a GPU.
   * two shards of 8 + 9 envs equal one 17-env call bit for bit; the checkpoint resumes the stream
   * ``record`` matches the example's reward / done / episode-tally lines over log vectors with k = 0, 1 and 3
   * rover_lift_rollout_act / rover_lift_rollout_record return codes for bad arguments, nothing is launched
+  * the case lists of tests/test_gpu_lift_rollout_edges.py (tests/lift_rollout_helpers.py) on the spec: every action width, the moved
+    log-std window, NaN rows under ``clip_actions=True`` (NaN kept), ids that wrap past 2**31 and 2**32, the record kernel's inputs
 """
 import ctypes as C
 
@@ -17,12 +19,8 @@ import torch
 from isaac_rover_orbit_amd import lift_ppo as LP
 from isaac_rover_orbit_amd import lift_rollout as LR
 from isaac_rover_orbit_amd import rollout as R
-
-TAG = 0x4C524F00
-
-
-def _biteq(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+import lift_rollout_helpers as H
+from lift_rollout_helpers import TAG, _biteq
 
 
 @pytest.fixture(scope="module")
@@ -207,3 +205,144 @@ def test_abi_defaults_and_error_codes():
     if not torch.cuda.is_available():
         with pytest.raises(_lib.RoverHipError):
             LR.LiftRolloutCollector(None, 4, 2)                                            # no CPU fallback
+
+
+# ------------------------------------------------- the edge cases of tests/test_gpu_lift_rollout_edges.py, on the specification
+def _width_spec(A, n, **kw):
+    """TorchLiftRollout on the fp32 torch networks of ``width_state_dicts(A)`` and a RunningStandardScaler holding the hand-written
+    blocks of ``scaler_blocks``."""
+    sd_p, sd_v = H.width_state_dicts(A)
+    policy, value = LP.LiftMLP(A), LP.LiftMLP(1)
+    policy.load_state_dict(sd_p); value.load_state_dict(sd_v)
+    state, vblk = H.scaler_blocks()
+    sp, vp = LP.RunningStandardScaler(LP.OBS_DIM, device="cpu"), LP.RunningStandardScaler(1, device="cpu")
+    sp.running_mean, sp.running_variance = torch.from_numpy(state[:36]), torch.from_numpy(state[36:72])
+    vp.running_mean, vp.running_variance = torch.from_numpy(vblk[:1]), torch.from_numpy(vblk[1:2])
+    col = LR.TorchLiftRollout(policy, value, torch.from_numpy(H.log_std_of(A)), lambda x: sp(x), lambda v: vp(v, inverse=True), n, 1, **kw)
+    return col, (sd_p, sd_v, torch.from_numpy(state), torch.from_numpy(vblk))
+
+
+def _outputs(col, t=0):
+    eps = (col.actions[t] - col.mean[t]).double()      # not the draws: the measures take eps from the caller
+    return {"mean": col.mean[t], "act": col.actions[t], "logp": col.logp[t], "eps": eps}
+
+
+@pytest.mark.parametrize("A", H.WIDTHS)
+def test_action_widths_on_the_spec(A):
+    """Every width of the GPU file: shapes, the three sampling bounds on the spec's own fp32 arithmetic, the odd last column as the
+    cosine draw of its pair, nesting of the draws, and mean / val within the float64 bound on inputs that respect its cap."""
+    worst = 0.0
+    for n in H.WIDTH_ROWS:
+        o = H.lift_rows(n, seed=n)
+        col, (sd_p, sd_v, state, vblk) = _width_spec(A, n, seed=9, env_id_offset=11)
+        col.counter = 5
+        eps64 = col.draws()
+        col.act(0, o)
+        assert col.mean[0].shape == col.actions[0].shape == (n, A) and col.logp[0].shape == (n,)
+        ls = np.clip(H.log_std_of(A).astype(np.float64), -20.0, 2.0)
+        assert (H.log_std_of(A) > 2.0).any() and (A == 1 or (H.log_std_of(A) < -20.0).any())
+        out = {"mean": col.mean[0], "act": col.actions[0], "logp": col.logp[0], "eps": torch.from_numpy(eps64.astype(np.float32))}
+        H.check_sampling(out, n, ls, f"spec A={A} n={n}", counter=5, seed=9, offset=11)
+        wide = R.standard_normals(9, 11 + np.arange(n), 5, A + 1, tag=TAG)
+        assert np.array_equal(wide[:, :A], eps64)                                          # column c depends on c, not on A
+        if A % 2:
+            pair = R.standard_normals(9, 11 + np.arange(n), 5, 2, tag=TAG | ((A - 1) // 2))[:, 0]
+            assert np.array_equal(eps64[:, A - 1], pair)                                   # the cosine draw of pair (A - 1) / 2
+        ref = H.float64_forward(sd_p, sd_v, o, state, vblk, 1e-8, 5.0)
+        worst = max(worst, float(ref[2].double().mean()))
+        assert not ref[3].any()
+        if n == 33:
+            H.check_float64({"mean": col.mean[0], "val": col.val[0].reshape(n, 1)}, ref, f"spec A={A} n={n}")
+            assert 0.2 <= float(ref[0].abs().mean()) <= 5.0                                # the means are O(1)
+    assert worst <= H.MAX_EXCLUDED
+
+
+@pytest.mark.parametrize("window", H.WINDOWS)
+def test_moved_log_std_window_on_the_spec(window):
+    A, n = 8, 33
+    ls_raw = torch.tensor(H.LOG_STD)
+    col = LR.TorchLiftRollout(lambda s: s[:, :A] * 0.5, lambda s: s[:, :1], ls_raw, lambda x: x, None, n, 1, log_std_min=window[0],
+                              log_std_max=window[1])
+    eps64 = col.draws()
+    col.act(0, H.lift_rows(n, seed=1))
+    ls = np.clip(np.array(H.LOG_STD, dtype=np.float32).astype(np.float64), *window)
+    out = {"mean": col.mean[0], "act": col.actions[0], "logp": col.logp[0], "eps": torch.from_numpy(eps64.astype(np.float32))}
+    H.check_sampling(out, n, ls, f"spec window {window}")
+    base = LR.TorchLiftRollout(lambda s: s[:, :A] * 0.5, lambda s: s[:, :1], ls_raw, lambda x: x, None, n, 1)
+    base.act(0, H.lift_rows(n, seed=1))
+    assert not torch.equal(base.actions[0], col.actions[0]) and _biteq(base.mean[0], col.mean[0])
+    assert _biteq(base.logp[0], LP.gaussian_logp(base.mean[0], ls_raw, base.actions[0]))   # the default window is gaussian_logp
+
+
+@pytest.mark.parametrize("n", H.POISON_ROWS)
+def test_nan_rows_stay_nan_under_clip_actions(setup, n):
+    """torch.clamp keeps a NaN: the env action of a poisoned row is NaN, not -1; rows with infinities only stay finite."""
+    policy, value, sp, vp = setup
+    rowwise = lambda net: (lambda x: torch.cat([net(x[i:i + 1]) for i in range(x.shape[0])]))      # noqa: E731
+    make = lambda: LR.TorchLiftRollout(rowwise(policy), rowwise(value), policy.log_std_parameter, lambda x: sp(x),      # noqa: E731
+                                       lambda v: vp(v, inverse=True), n, 1, seed=7, env_id_offset=3, clip_actions=True)
+    o = H.lift_rows(n, seed=2)
+    raw, nan_rows, inf_rows = H.poison(o)
+    a, b = make(), make()
+    eps64 = a.draws()
+    env_act, env_clean = a.act(0, raw), b.act(0, o)
+    f32 = lambda x: torch.from_numpy(x.astype(np.float32))      # noqa: E731
+    out = {"obs": a.obs[0], "mean": a.mean[0], "val": a.val[0], "act": a.actions[0], "env_act": env_act, "logp": a.logp[0], "eps": f32(eps64)}
+    clean = {"obs": b.obs[0], "mean": b.mean[0], "val": b.val[0], "act": b.actions[0], "env_act": env_clean, "logp": b.logp[0], "eps": f32(eps64)}
+    bad = nan_rows + inf_rows
+    clean["obs"] = clean["obs"].clone(); clean["obs"][bad] = raw[bad]
+    H.check_poisoned(out, clean, raw, nan_rows, inf_rows, eps64)
+    assert ((env_act[inf_rows] >= -1.0) & (env_act[inf_rows] <= 1.0)).all()
+    with torch.no_grad():
+        assert _biteq(sp(raw)[inf_rows].abs().max(1).values, torch.full((len(inf_rows),), 5.0))      # +-inf standardises to +-clip
+
+
+def test_ids_wrap_mod_2_32():
+    """standard_normals takes ids mod 2**32 (the kernel's word 0 is a uint32 sum): ids past 2**31 and past 2**32, negative ids, the
+    by-hand evaluation at the top of every range, and two shards across 2**31 equal to the whole."""
+    from td3_helpers import eps_float64_by_hand
+    n, A = 33, 3
+    for off in H.WRAP_OFFSETS:
+        ids = off + np.arange(n, dtype=np.int64)
+        assert ids[0] < 2 ** 31 <= ids[-1]
+        for counter in H.TOP_COUNTERS:
+            got = R.standard_normals(H.TOP_SEED, ids, counter, A, tag=TAG)
+            assert np.abs(got - np.array(eps_float64_by_hand(H.TOP_SEED, ids, counter, A, TAG))).max() <= 1e-12
+            assert np.array_equal(got, R.standard_normals(H.TOP_SEED, ids + 2 ** 32, counter, A, tag=TAG))
+            assert np.array_equal(got, R.standard_normals(H.TOP_SEED, ids - 2 ** 32, counter, A, tag=TAG))
+            assert np.array_equal(got, R.standard_normals(H.TOP_SEED, ids.astype(np.uint32).astype(np.int32), counter, A, tag=TAG))
+            col = LR.TorchLiftRollout(lambda s: s[:, :A] * 0.5, lambda s: s[:, :1], torch.zeros(A), lambda x: x, None, n, 1, seed=H.TOP_SEED,
+                                      env_id_offset=off)
+            col.counter = counter
+            assert np.array_equal(col.draws(), got)
+            lo = LR.TorchLiftRollout(col.actor, col.critic, torch.zeros(A), lambda x: x, None, 16, 1, seed=H.TOP_SEED, env_id_offset=off)
+            hi = LR.TorchLiftRollout(col.actor, col.critic, torch.zeros(A), lambda x: x, None, 17, 1, seed=H.TOP_SEED, env_id_offset=off + 16)
+            lo.counter = hi.counter = counter
+            o = H.lift_rows(n, seed=3)
+            whole = col.act(0, o)
+            assert _biteq(whole, torch.cat([lo.act(0, o[:16]), hi.act(0, o[16:])])) and _biteq(col.logp[0], torch.cat([lo.logp[0], hi.logp[0]]))
+
+
+@pytest.mark.parametrize("n", H.RECORD_NS)
+def test_record_edge_inputs_on_the_spec(n):
+    for seed, scale in enumerate(H.RECORD_SCALES + (1.0,)):
+        rew, term, trunc = H.record_inputs(n, seed)
+        want_r, want_d = H.expected_record(rew, term, trunc, scale)
+        for flags in ((term, trunc), (term != 0, trunc != 0)):
+            col = LR.TorchLiftRollout(None, None, torch.zeros(8), None, None, n, 1, reward_scale=scale)
+            col.record(0, rew, flags[0], flags[1])
+            assert H.same_bits_nan_aware(col.rew[0], want_r) and _biteq(col.done[0], want_d), (scale, flags[0].dtype)
+        assert set(term.tolist()) <= set(H.FLAG_VALUES) and (n < 255 or set(term.tolist()) == set(H.FLAG_VALUES))
+        assert torch.isnan(rew).any() or n == 1
+    col = LR.TorchLiftRollout(None, None, torch.zeros(8), None, None, n, 1)
+    col.record(0, rew, term, trunc, H.record_log(2.0, 1))
+    for k in H.STILL_KS:
+        s0, c0 = col.ep_sum.clone(), col.ep_count.clone()
+        assert (s0 != 0).all() and float(c0) == 2.0
+        col.record(0, rew, term, trunc, H.record_log(k, 2))
+        assert _biteq(col.ep_sum, s0) and _biteq(col.ep_count, c0), k                      # nothing moves, not even a sign of zero
+    log = H.record_log(3.0, 3, nan_at=2)
+    want_s, want_c = H.expected_tally(col.ep_sum, col.ep_count, log)
+    col.record(0, rew, term, trunc, log)
+    assert torch.isnan(col.ep_sum[2]) and torch.isfinite(col.ep_sum[[0, 1, 3, 4, 5, 6, 7]]).all() and float(col.ep_count) == 5.0
+    assert H.same_bits_nan_aware(col.ep_sum, want_s) and _biteq(col.ep_count, want_c)
