@@ -7,8 +7,11 @@ Transitions live in ``td3.ReplayMemory``, one observation ring.  The update is t
 
 Every env step: the actor forward (``FusedTD3.actor`` on the fused kernels, or the torch actor), optional exploration noise,
 env.step with those actions, memory.add of the same actions, then one gradient step on a batch drawn from the memory.
-``--rollout fused`` (with ``--update fused``) hands all of that but env.step and the update to ``td3_collect.TD3Collector``: two
-HIP launches per env step, counter-based noise and batch indices.
+``--rollout fused`` (with ``--update fused``) hands all of that but env.step and the update to ``td3_explore.TD3Explorer``: two
+HIP launches per env step, counter-based noise and batch indices.  That path also carries skrl's other TD3 switches: ``--noise ou``
+(Ornstein-Uhlenbeck exploration noise), ``--random_timesteps`` (uniform random actions first) and ``--smooth_noise_std`` (the target
+action's smoothing noise, drawn on the device).  ``--learning_starts`` collects without updating before that timestep, on either
+path.  At their defaults the run is what it was without them.
 
     python examples/07_train_td3.py --num_envs 4096 --timesteps 2000 --update fused --out td3.jsonl
     python examples/07_train_td3.py --num_envs 4096 --timesteps 2000 --update fused --rollout fused --out td3.jsonl
@@ -29,14 +32,14 @@ from isaac_rover_orbit_amd.cfg import RoverEnvCfg  # noqa: E402
 from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
 from isaac_rover_orbit_amd.td3 import (HPARAMS, Critic, FusedTD3, ReplayMemory, TorchTD3, exploration_scale,  # noqa: E402
                                        explore)
-from isaac_rover_orbit_amd.td3_collect import TD3Collector  # noqa: E402
+from isaac_rover_orbit_amd.td3_explore import TD3Explorer  # noqa: E402
 
 _spec = importlib.util.spec_from_file_location("train_ppo_example", os.path.join(ROOT, "examples", "04_train_ppo.py"))
 ppo_example = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(ppo_example)
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--timesteps", type=int, default=1000)
@@ -52,9 +55,26 @@ def main():
                     help="TD3 update: the torch spec (TorchTD3) or the fused HIP kernels (FusedTD3)")
     ap.add_argument("--rollout", choices=("torch", "fused"), default="torch",
                     help="the glue around env.step: torch ops and ReplayMemory.add, or the fused collector (needs --update fused)")
+    ap.add_argument("--noise", choices=("none", "gaussian", "ou"), default="none",
+                    help="exploration noise class: skrl's GaussianNoise (std --exploration_noise) or OrnsteinUhlenbeckNoise (skrl's "
+                         "defaults); none with --exploration_noise > 0 is gaussian, as before.  ou needs --rollout fused")
+    ap.add_argument("--random_timesteps", type=int, default=HPARAMS["random_timesteps"],
+                    help="env steps of uniform random actions before the actor acts (skrl random_timesteps; needs --rollout fused)")
+    ap.add_argument("--learning_starts", type=int, default=HPARAMS["learning_starts"],
+                    help="collect without an update before this timestep (skrl learning_starts)")
+    ap.add_argument("--smooth_noise_std", type=float, default=0.0,
+                    help="std of the target action's smoothing noise (skrl smooth_regularization_noise; 0: none; needs --rollout fused)")
+    return ap
+
+
+def main():
+    ap = build_parser()
     args = ap.parse_args()
     if args.rollout == "fused" and args.update != "fused":
         ap.error("--rollout fused needs --update fused (the collector runs FusedTD3's actor)")
+    if args.rollout != "fused" and (args.noise == "ou" or args.random_timesteps > 0 or args.smooth_noise_std > 0):
+        ap.error("--noise ou, --random_timesteps and --smooth_noise_std need --rollout fused (their draws are the collector's)")
+    noise = args.noise if args.noise != "none" or args.exploration_noise <= 0 else "gaussian"
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
     n, M = args.num_envs, args.memory_size or 2 * args.batch_size
@@ -75,7 +95,8 @@ def main():
     obs, _ = env.reset()
     collector = None
     if args.rollout == "fused":
-        collector = TD3Collector(fused.actor, memory, seed=args.seed, env_id_offset=cfg.env_id_offset, noise_std=args.exploration_noise)
+        collector = TD3Explorer(fused.actor, memory, seed=args.seed, env_id_offset=cfg.env_id_offset, noise=noise,
+                                noise_std=args.exploration_noise, random_timesteps=args.random_timesteps)
         collector.begin(obs)
     else:
         o = torch.nan_to_num(obs["policy"], neginf=0.0)
@@ -86,9 +107,10 @@ def main():
         scale = None
         if args.exploration_noise > 0:
             scale = exploration_scale(step, args.timesteps, HPARAMS["exploration_initial_scale"], HPARAMS["exploration_final_scale"])
+        learning = step >= args.learning_starts
         if collector is not None:
-            obs, rew, term, trunc, info = env.step(collector.act(scale))
-            idx = collector.record(obs, rew, term, args.batch_size)
+            obs, rew, term, trunc, info = env.step(collector.act(step, args.timesteps))
+            idx = collector.record(obs, rew, term, args.batch_size if learning else None)   # indices over the rows filled so far
         else:
             with torch.no_grad():
                 a = fused.actor(o) if fused is not None else spec.act(o)
@@ -98,12 +120,13 @@ def main():
             o_next = torch.nan_to_num(obs["policy"], neginf=0.0)
             memory.add(o, a, rew, o_next, term)
             o = o_next
-            idx = memory.sample_indices(args.batch_size, gen)
+            idx = memory.sample_indices(args.batch_size, gen) if learning else None
         lv = env.episode_log_vector
         ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
-        if fused is not None:
-            fused.update(memory, idx)
-        else:
+        if learning and fused is not None:
+            smooth = collector.smooth_noise(args.batch_size, args.smooth_noise_std) if args.smooth_noise_std > 0 else None
+            fused.update(memory, idx, smooth)
+        elif learning:
             last = spec.update(memory, idx)
         steps_log += 1
         if (step + 1) % args.log_every == 0 or step + 1 == args.timesteps:

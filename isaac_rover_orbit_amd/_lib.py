@@ -53,6 +53,8 @@ EXPORTS = [
     "rover_lift_rollout_record",
     "rover_td3_collect_default_hparams", "rover_td3_collect_hparams_bytes", "rover_td3_collect_act",  # rover_td3_collect.h
     "rover_td3_collect_record",
+    "rover_td3_explore_default_hparams", "rover_td3_explore_hparams_bytes", "rover_td3_explore_act",  # rover_td3_explore.h
+    "rover_td3_smooth_draw",
     "rover_trace_stream_bytes", "rover_trace_stage_pitch", "rover_trace_stage_bytes", "rover_trace_state_bytes",  # rover_trace.h
     "rover_trace_init", "rover_trace_append", "rover_trace_commit_all", "rover_trace_gather", "rover_trace_drained",
 ]
@@ -152,6 +154,16 @@ class Td3CollectHparams(C.Structure):
     """Mirror of ``struct rover_td3_collect_hparams`` (include/rover_td3_collect.h)."""
     _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("explore", C.c_int32),
                 ("noise_std", C.c_float), ("noise_scale", C.c_float), ("action_low", C.c_float), ("action_high", C.c_float)]
+
+
+TD3_EXPLORE_OFF, TD3_EXPLORE_GAUSSIAN, TD3_EXPLORE_OU, TD3_EXPLORE_RANDOM = 0, 1, 2, 3
+
+
+class Td3ExploreHparams(C.Structure):
+    """Mirror of ``struct rover_td3_explore_hparams`` (include/rover_td3_explore.h)."""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("mode", C.c_int32),
+                ("noise_std", C.c_float), ("noise_scale", C.c_float), ("ou_theta", C.c_float), ("ou_sigma", C.c_float),
+                ("ou_base_scale", C.c_float), ("action_low", C.c_float), ("action_high", C.c_float)]
 
 
 class TraceStream(C.Structure):
@@ -398,6 +410,11 @@ def load():
     lib.rover_td3_collect_hparams_bytes.restype = C.c_size_t
     lib.rover_td3_collect_act.argtypes = [pd, vp, i32, tch, C.c_uint64, vp, i32, vp, vp, vp, vp, vp]
     lib.rover_td3_collect_record.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.c_int64, tch, C.c_uint64, vp]
+    teh = C.POINTER(Td3ExploreHparams)
+    lib.rover_td3_explore_default_hparams.argtypes = [teh]
+    lib.rover_td3_explore_hparams_bytes.restype = C.c_size_t
+    lib.rover_td3_explore_act.argtypes = [pd, vp, i32, teh, C.c_uint64, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.rover_td3_smooth_draw.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, f32, vp, i32, i32, vp]
     trs = C.POINTER(TraceStream)
     for name in ("rover_trace_stream_bytes", "rover_trace_stage_pitch", "rover_trace_stage_bytes", "rover_trace_state_bytes"):
         getattr(lib, name).restype = C.c_size_t
@@ -438,6 +455,8 @@ def load():
         raise RoverHipError("struct rover_lift_rollout_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_td3_collect_hparams_bytes() != C.sizeof(Td3CollectHparams):
         raise RoverHipError("struct rover_td3_collect_hparams of librover_hip.so does not match the Python mirror")
+    if lib.rover_td3_explore_hparams_bytes() != C.sizeof(Td3ExploreHparams):
+        raise RoverHipError("struct rover_td3_explore_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_trace_stream_bytes() != C.sizeof(TraceStream):
         raise RoverHipError("struct rover_trace_stream of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
