@@ -57,6 +57,8 @@ EXPORTS = [
     "rover_td3_smooth_draw",
     "rover_trace_stream_bytes", "rover_trace_stage_pitch", "rover_trace_stage_bytes", "rover_trace_state_bytes",  # rover_trace.h
     "rover_trace_init", "rover_trace_append", "rover_trace_commit_all", "rover_trace_gather", "rover_trace_drained",
+    "rover_sac_default_hparams", "rover_sac_hparams_bytes", "rover_sac_state_bytes", "rover_sac_param_floats",  # rover_sac.h
+    "rover_sac_workspace_bytes", "rover_sac_critic_step", "rover_sac_policy_step", "rover_sac_polyak",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -170,6 +172,23 @@ class TraceStream(C.Structure):
     """Mirror of ``struct rover_trace_stream`` (include/rover_trace.h)."""
     _fields_ = [("src", C.c_void_p), ("src_pitch", C.c_int64), ("stage", C.c_void_p), ("stage_pitch", C.c_int64),
                 ("out", C.c_void_p), ("out_pitch", C.c_int64), ("row_bytes", C.c_int32), ("flags", C.c_int32)]
+
+
+class SacHparams(C.Structure):
+    """Mirror of ``struct rover_sac_hparams`` (include/rover_sac.h)."""
+    _fields_ = [("gamma", C.c_float), ("polyak", C.c_float), ("actor_lr", C.c_float), ("critic_lr", C.c_float),
+                ("entropy_lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("target_entropy", C.c_float), ("learn_entropy", C.c_int32)]
+
+
+class SacState(C.Structure):
+    """Mirror of ``struct rover_sac_state`` (include/rover_sac.h; it lives in device memory)."""
+    _fields_ = [("critic_step", C.c_int32), ("actor_step", C.c_int32), ("entropy_step", C.c_int32), ("bad_index", C.c_int32),
+                ("critic_loss", C.c_float), ("policy_loss", C.c_float), ("entropy_loss", C.c_float), ("q1_mean", C.c_float),
+                ("q2_mean", C.c_float), ("y_mean", C.c_float), ("logp_mean", C.c_float), ("alpha", C.c_float),
+                ("critic_step_size", C.c_float), ("critic_bc2_sqrt", C.c_float), ("actor_step_size", C.c_float),
+                ("actor_bc2_sqrt", C.c_float), ("entropy_step_size", C.c_float), ("entropy_bc2_sqrt", C.c_float),
+                ("reserved", C.c_float * 2)]
 
 
 class RoverHipError(RuntimeError):
@@ -426,6 +445,19 @@ def load():
     lib.rover_trace_commit_all.argtypes = [vp, i32, i32, i32, vp]
     lib.rover_trace_gather.argtypes = [trs, i32, vp, i32, i32, i32, i32, i32, vp]
     lib.rover_trace_drained.argtypes = [vp, i32, vp]
+    sah = C.POINTER(SacHparams)
+    lib.rover_sac_default_hparams.argtypes = [sah]
+    lib.rover_sac_hparams_bytes.restype = C.c_size_t
+    lib.rover_sac_state_bytes.restype = C.c_size_t
+    lib.rover_sac_param_floats.argtypes = [pd, pd]
+    lib.rover_sac_param_floats.restype = C.c_size_t
+    lib.rover_sac_workspace_bytes.argtypes = [i32]
+    lib.rover_sac_workspace_bytes.restype = C.c_size_t
+    lib.rover_sac_critic_step.argtypes = [pd, pd, sah, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, C.c_int64, vp, vp,
+                                          C.c_size_t, vp, vp, vp]
+    lib.rover_sac_policy_step.argtypes = [pd, pd, sah, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, C.c_int64, vp, vp, C.c_size_t, vp, vp,
+                                          i32, vp, vp, vp, vp]
+    lib.rover_sac_polyak.argtypes = [pd, pd, sah, vp, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -457,6 +489,8 @@ def load():
         raise RoverHipError("struct rover_td3_collect_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_td3_explore_hparams_bytes() != C.sizeof(Td3ExploreHparams):
         raise RoverHipError("struct rover_td3_explore_hparams of librover_hip.so does not match the Python mirror")
+    if lib.rover_sac_hparams_bytes() != C.sizeof(SacHparams) or lib.rover_sac_state_bytes() != C.sizeof(SacState):
+        raise RoverHipError("struct rover_sac_hparams / rover_sac_state of librover_hip.so does not match the Python mirror")
     if lib.rover_trace_stream_bytes() != C.sizeof(TraceStream):
         raise RoverHipError("struct rover_trace_stream of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:

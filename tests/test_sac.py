@@ -1,0 +1,332 @@
+"""SAC, CPU side: the closed form of the Gaussian head's backward against autograd through the torch spec's policy loss in
+float64, the spec's target, entropy step, target copies, Polyak and checkpoint, and the host-only parts of include/rover_sac.h."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from sac_helpers import draws, fill, nets, params
+
+F64 = torch.float64
+
+
+def _spec(seed=0, dtype=F64, bias=None, log_std=None, tie=False, **hp):
+    from isaac_rover_orbit_amd.sac import TorchSAC
+    pol, c1, c2 = (m.to(dtype) for m in nets(seed, bias=bias, log_std=log_std))
+    if tie:
+        c2.load_state_dict(c1.state_dict())
+    return TorchSAC(pol, c1, c2, **hp)
+
+
+def _memory(M=3, N=8, steps=5):
+    from isaac_rover_orbit_amd.td3 import ReplayMemory
+    mem = ReplayMemory(M, N, device="cpu")
+    fill(mem, steps)
+    return mem
+
+
+def _flat(m):
+    return torch.cat([p.detach().reshape(-1) for p in m.parameters()])
+
+
+def _rel(a, b):
+    return float((a - b).norm()) / max(float(b.norm()), 1e-300)
+
+
+# ---- the closed form
+def _closed_form_case(spec, B=96, seed=3):
+    """(closed form, autograd) of the policy step's head on B random rows; autograd runs through TorchSAC.policy_loss."""
+    from isaac_rover_orbit_amd.sac import gaussian_head_backward
+    g_ = torch.Generator().manual_seed(seed)
+    s = torch.randn(B, 965, generator=g_, dtype=F64) * 0.5
+    eps = torch.randn(B, 2, generator=g_, dtype=F64)
+    seen = {}
+
+    def hook(_, inp, out):
+        inp[0].retain_grad(); out.retain_grad()
+        seen["z6"], seen["mu"] = inp[0], out
+    h = spec.policy.mlp[-1].register_forward_hook(hook)
+    loss, u, logp = spec.policy_loss(s, eps)
+    h.remove()
+    spec.policy.zero_grad()
+    loss.backward()
+    entropy_loss = -(spec.log_entropy_coefficient * (logp + spec.target_entropy).detach()).mean()
+    auto = {"dmu": seen["mu"].grad, "dz6": seen["z6"].grad, "dlog_std": spec.policy.log_std_parameter.grad.clone(),
+            "dlog_alpha": torch.autograd.grad(entropy_loss, spec.log_entropy_coefficient)[0], "u": u.detach(),
+            "logp": logp.detach().reshape(-1)}
+    # g = d min(q1, q2) / du by torch.min's rule: weight 1 on the smaller critic, 0.5 each on an exact tie
+    ud = u.detach().requires_grad_(True)
+    q1, q2 = spec.critic_1(s, ud), spec.critic_2(s, ud)
+    dq1, dq2 = torch.autograd.grad(q1.sum(), ud)[0], torch.autograd.grad(q2.sum(), ud)[0]
+    w1 = torch.where(q1 < q2, 1.0, torch.where(q1 == q2, 0.5, 0.0)).to(F64).detach()
+    g = w1 * dq1 + (1 - w1) * dq2
+    mu = seen["mu"].detach()
+    closed = gaussian_head_backward(mu, spec.policy.log_std_parameter.detach(), eps, g, spec.entropy_coefficient,
+                                    target_entropy=spec.target_entropy)
+    sigma = spec.policy.log_std_parameter.detach().clamp(-20, 2).exp()
+    x = mu + sigma * eps
+    # autograd's own error on dL/dmu: it reaches mu along two paths, +alpha t / (sigma B) directly and -alpha t / (sigma B) through
+    # u = clamp(mu + sigma eps), each summed with the critics' term before they cancel, so it carries a few roundings of that
+    # magnitude (5e8 times the result at sigma = exp(-20)); the closed form never forms those terms for an unclamped row
+    auto["cancel"] = 8 * 2.0 ** -53 * float((spec.entropy_coefficient * closed["u"].sub(mu).div(sigma).abs() / sigma / B).norm())
+    return closed, auto, x, (q1.detach(), q2.detach())
+
+
+def _assert_closed_form(closed, auto):
+    for k in ("u", "logp", "dlog_alpha"):
+        assert _rel(closed[k], auto[k]) <= 1e-10, (k, _rel(closed[k], auto[k]))
+    for k in ("dmu", "dz6"):                                # 1e-10 relative, plus the reference's cancellation error (see above)
+        assert float((closed[k] - auto[k]).norm()) <= 1e-10 * float(auto[k].norm()) + auto["cancel"], k
+    if float(auto["dlog_std"].norm()) > 0:
+        assert _rel(closed["dlog_std"], auto["dlog_std"]) <= 1e-10
+    else:
+        assert torch.equal(closed["dlog_std"], auto["dlog_std"])
+
+
+def test_closed_form_with_both_clamps_hit_and_interior_rows():
+    closed, auto, x, _ = _closed_form_case(_spec(bias=(1.5, -1.5)))
+    assert bool((x > 1).any()) and bool((x < -1).any()) and bool(((x > -1) & (x < 1)).any())
+    for c in range(2):                                      # in either component some rows are clamped, some are not
+        assert bool((x[:, c].abs() > 1).any()) and bool((x[:, c].abs() < 1).any())
+    _assert_closed_form(closed, auto)
+    assert float(auto["dlog_std"].abs().min()) > 0
+
+
+def test_closed_form_log_std_outside_the_clamp_has_zero_gradient():
+    closed, auto, _, _ = _closed_form_case(_spec(bias=(1.5, -1.5), log_std=(2.5, -20.5)))
+    assert torch.equal(auto["dlog_std"], torch.zeros(2, dtype=F64))
+    assert torch.equal(closed["dlog_std"], torch.zeros(2, dtype=F64))
+    _assert_closed_form(closed, auto)
+
+
+def test_closed_form_log_std_on_the_bounds_passes_the_gradient():
+    closed, auto, _, _ = _closed_form_case(_spec(bias=(1.5, -1.5), log_std=(2.0, -20.0)))
+    assert float(auto["dlog_std"].abs().min()) > 0
+    _assert_closed_form(closed, auto)
+
+
+def test_closed_form_with_ties_everywhere():
+    closed, auto, _, (q1, q2) = _closed_form_case(_spec(bias=(1.5, -1.5), tie=True))
+    assert torch.equal(q1, q2)
+    _assert_closed_form(closed, auto)
+
+
+# ---- torch spec
+def test_target_holds_the_entropy_term_and_terminated_rows_get_the_reward():
+    from isaac_rover_orbit_amd.sac import gaussian_act
+    spec = _spec(dtype=torch.float32)
+    g = torch.Generator().manual_seed(4)
+    B = 32
+    s2 = torch.randn(B, 965, generator=g) * 0.5
+    r = torch.randn(B, 1, generator=g)
+    eps = torch.randn(B, 2, generator=g)
+    term = (torch.arange(B) % 3 == 0).unsqueeze(1)
+    y = spec.target_values(s2, r, term, eps)
+    assert torch.equal(y[term], r[term])
+    with torch.no_grad():
+        u2, logp2 = gaussian_act(spec.policy(s2), spec.policy.log_std_parameter, eps)
+        q = torch.min(spec.target_critic_1(s2, u2), spec.target_critic_2(s2, u2))
+    live = ~term
+    alpha = torch.tensor(0.2).log().exp()
+    assert torch.equal(y[live], (r + 0.99 * (q - alpha * logp2))[live])
+    assert float((y - (r + 0.99 * ~term * q)).abs()[live].min()) > 1e-3        # the term is there, and it is not small
+    assert logp2.shape == (B, 1) and bool((u2.abs() <= 1).all())
+
+
+def test_first_move_of_log_alpha_follows_the_sign_of_logp_plus_target_entropy():
+    mem = _memory()
+    g = torch.Generator().manual_seed(5)
+    idx = mem.sample_indices(16, g)
+    for log_std, want in (((-3.0, -3.0), +1), ((1.0, 1.0), -1)):    # a narrow Gaussian has a high logp, a wide one a low logp
+        spec = _spec(log_std=log_std)
+        la0 = float(spec.log_entropy_coefficient.detach())
+        assert la0 == pytest.approx(math.log(float(np.float32(0.2))), rel=1e-12)
+        st = spec.update(mem, idx, draws(16, 6))
+        d = st["logp_mean"] + spec.target_entropy
+        assert (d > 0) == (want > 0)
+        # Adam's first step moves against the gradient -(logp_mean + target_entropy) by the learning rate
+        assert float(spec.log_entropy_coefficient.detach()) - la0 == pytest.approx(want * 5e-3, rel=1e-6)
+        assert st["entropy_loss"] == pytest.approx(-la0 * d, rel=1e-9)
+
+
+def test_alpha_used_in_a_call_is_the_one_from_before_the_call():
+    mem = _memory()
+    idx = mem.sample_indices(16, torch.Generator().manual_seed(7))
+    eps = draws(16, 8)
+    spec, frozen = _spec(), _spec(learn_entropy=False)
+    a0 = float(spec.entropy_coefficient)
+    st, st_frozen = spec.update(mem, idx, eps), frozen.update(mem, idx, eps)
+    assert st["alpha"] == a0 and float(spec.entropy_coefficient) != a0
+    assert float(spec.entropy_coefficient) == float(spec.log_entropy_coefficient.detach().exp())
+    # the whole first call equals a call that never steps alpha: critic and policy step both used a0
+    for k in ("critic_loss", "policy_loss", "y_mean"):
+        assert st[k] == st_frozen[k]
+    for m in ("policy", "critic_1", "critic_2"):
+        assert torch.equal(_flat(getattr(spec, m)), _flat(getattr(frozen, m)))
+    # ... and the second call uses the stepped alpha
+    st2, st2_frozen = spec.update(mem, idx, eps), frozen.update(mem, idx, eps)
+    assert st2["alpha"] != a0 and st2_frozen["alpha"] == a0 and st2["critic_loss"] != st2_frozen["critic_loss"]
+
+
+def test_learn_entropy_off_leaves_log_alpha_untouched():
+    mem = _memory()
+    spec = _spec(learn_entropy=False)
+    la0 = spec.log_entropy_coefficient.detach().clone()
+    for i in range(3):
+        st = spec.update(mem, mem.sample_indices(16, torch.Generator().manual_seed(i)), draws(16, 10 + i))
+        assert "entropy_loss" not in st
+    assert torch.equal(spec.log_entropy_coefficient.detach(), la0) and float(spec.entropy_coefficient) == float(la0.exp())
+
+
+def test_targets_start_as_copies_and_polyak_is_skrls_formula():
+    spec = _spec(dtype=torch.float32)
+    assert not hasattr(spec, "target_policy")
+    for t, m in ((spec.target_critic_1, spec.critic_1), (spec.target_critic_2, spec.critic_2)):
+        assert t is not m and torch.equal(_flat(t), _flat(m))
+    mem = _memory()
+    idx = mem.sample_indices(16, torch.Generator().manual_seed(9))
+    s, a, r, s2, t = mem.gather(idx)
+    spec.critic_step(s, a, r, s2, t, draws(16, 1)[:, 0:2])
+    t0, p0 = _flat(spec.target_critic_1), _flat(spec.critic_1)
+    assert not torch.equal(t0, p0)
+    spec.polyak()
+    want = t0.clone()
+    want.mul_(1 - 0.005)
+    want.add_(0.005 * p0)
+    assert torch.equal(_flat(spec.target_critic_1), want)
+
+
+def test_checkpoint_round_trip():
+    from isaac_rover_orbit_amd.sac import CHECKPOINT_KEYS, TorchSAC
+    mem = _memory()
+    spec = _spec(dtype=torch.float32)
+    g = torch.Generator().manual_seed(11)
+    for i in range(2):
+        spec.update(mem, mem.sample_indices(16, g), draws(16, 20 + i))
+    ck = spec.checkpoint()
+    assert tuple(ck) == CHECKPOINT_KEYS and "log_std_parameter" in ck["policy"]
+    assert ck["log_entropy_coefficient"].shape == (1,)
+    back = TorchSAC.from_checkpoint(ck, *nets(99))
+    for k in CHECKPOINT_KEYS[:-1]:
+        a, b = getattr(spec, k).state_dict(), getattr(back, k).state_dict()
+        assert set(a) == set(b) and all(torch.equal(a[n], b[n]) for n in a), k
+    assert torch.equal(back.log_entropy_coefficient.detach(), spec.log_entropy_coefficient.detach())
+    assert float(back.entropy_coefficient) == float(spec.entropy_coefficient)
+    assert not torch.equal(_flat(back.target_critic_1), _flat(back.critic_1))
+
+
+def test_unknown_hyper_parameter_is_refused():
+    with pytest.raises(TypeError):
+        _spec(policy_delay=2)
+
+
+# ---- host-only ABI checks
+def _descs():
+    from isaac_rover_orbit_amd import td3
+    from isaac_rover_orbit_amd.ppo import pack
+    pol, c1, _ = nets(0)
+    da, _ = pack(pol.state_dict(), "tanh")
+    dc, _ = td3.pack_critic(c1.state_dict())
+    return da, dc
+
+
+def test_struct_mirrors_and_sizes():
+    from isaac_rover_orbit_amd import _lib, build
+    from isaac_rover_orbit_amd.sac import HPARAMS, default_hparams
+    build.build_extension()
+    lib = _lib.load()
+    assert lib.rover_sac_hparams_bytes() == C.sizeof(_lib.SacHparams) == 40
+    assert lib.rover_sac_state_bytes() == C.sizeof(_lib.SacState) == 80
+    h = default_hparams()
+    want = dict(gamma=HPARAMS["discount_factor"], polyak=HPARAMS["polyak"], actor_lr=HPARAMS["actor_learning_rate"],
+                critic_lr=HPARAMS["critic_learning_rate"], entropy_lr=HPARAMS["entropy_learning_rate"], beta1=0.9, beta2=0.999,
+                eps=1e-8, target_entropy=-2.0)
+    for k, v in want.items():
+        assert getattr(h, k) == pytest.approx(v, rel=1e-7), k
+    assert h.learn_entropy == 1 and HPARAMS["learn_entropy"] is True and HPARAMS["target_entropy"] is None
+    assert HPARAMS["batch_size"] == 4096 and HPARAMS["initial_entropy_value"] == 0.2 and HPARAMS["grad_norm_clip"] == 0
+    da, dc = _descs()
+    na, nc = lib.rover_policy_packed_floats(C.byref(da)), lib.rover_policy_packed_floats(C.byref(dc))
+    P = lib.rover_sac_param_floats(C.byref(da), C.byref(dc))
+    assert P == (na + 2 * nc + 8 + 63) // 64 * 64 and (na + 2 * nc) % 4 == 0
+    assert lib.rover_sac_workspace_bytes(0) == 0 and lib.rover_sac_workspace_bytes(1) > 0
+    assert lib.rover_sac_workspace_bytes(4097) > lib.rover_sac_workspace_bytes(4096)
+
+
+def test_param_floats_is_zero_for_other_descriptors():
+    from isaac_rover_orbit_amd import _lib, build
+    from isaac_rover_orbit_amd.ppo import pack
+    from isaac_rover_orbit_amd.td3 import critic_desc
+    build.build_extension()
+    lib = _lib.load()
+    da, dc = _descs()
+    assert lib.rover_sac_param_floats(C.byref(da), C.byref(dc)) > 0
+    no_tanh, _ = pack(nets(0)[0].state_dict(), "none")          # TD3's actor: no final tanh
+    assert lib.rover_sac_param_floats(C.byref(no_tanh), C.byref(dc)) == 0
+    assert lib.rover_sac_param_floats(C.byref(dc), C.byref(da)) == 0
+    assert lib.rover_sac_param_floats(C.byref(da), C.byref(critic_desc())) == 0       # the critic layout before its pack
+    assert lib.rover_sac_param_floats(None, C.byref(dc)) == 0
+
+
+def test_bad_arguments_return_error_codes():
+    from isaac_rover_orbit_amd import _lib, build
+    from isaac_rover_orbit_amd.sac import default_hparams
+    from isaac_rover_orbit_amd.td3 import critic_desc
+    build.build_extension()
+    lib = _lib.load()
+    da, dc = _descs()
+    h = default_hparams()
+    fake = C.c_void_p(1 << 20)        # aligned, never dereferenced: every check below fails before any device access
+    odd = C.c_void_p((1 << 20) + 4)
+    ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+
+    def critic_step(a=da, c=dc, hh=h, params=fake, target=fake, ws=fake, ws_bytes=1 << 40, n=16, slots=3, envs=8, valid=16, idx=fake,
+                    eps=fake, state=fake, act=fake):
+        return lib.rover_sac_critic_step(ref(a), ref(c), ref(hh), params, target, fake, fake, fake, fake, slots, envs, fake, act, fake,
+                                         fake, idx, n, valid, eps, ws, ws_bytes, state, None, None)
+
+    def policy_step(a=da, c=dc, hh=h, params=fake, ws=fake, ws_bytes=1 << 40, n=16, slots=3, envs=8, valid=16, idx=fake, eps=fake,
+                    state=fake, rep=None, copies=1):
+        return lib.rover_sac_policy_step(ref(a), ref(c), ref(hh), params, fake, fake, fake, fake, slots, envs, fake, idx, n, valid,
+                                         eps, ws, ws_bytes, state, rep, copies, None, None, None, None)
+    for step in (critic_step, policy_step):
+        assert step(a=None) == 1 and step(c=None) == 1
+        assert step(hh=None) == 1 and step(params=None) == 1 and step(idx=None) == 1 and step(eps=None) == 1
+        assert step(ws=None) == 1 and step(state=None) == 1
+        assert step(n=0) == 1 and step(slots=1) == 1 and step(envs=0) == 1 and step(valid=17) == 1 and step(valid=0) == 1
+        assert step(ws_bytes=lib.rover_sac_workspace_bytes(16) - 1) == 1 and b"workspace too small" in lib.rover_last_error()
+        assert step(params=odd) == 1 and step(ws=odd) == 1 and b"16-byte" in lib.rover_last_error()
+        assert step(state=odd) == 1 and b"8-byte" in lib.rover_last_error()
+    assert critic_step(target=None) == 1 and critic_step(act=None) == 1 and critic_step(target=odd) == 1
+    assert policy_step(rep=fake, copies=0) == 1
+    # other descriptors: the lift network, TD3's actor (no final tanh), the unpacked critic layout, swapped roles
+    lift = _lib.PolicyDesc()
+    lib.rover_lift_policy_desc(C.byref(lift), 8)
+    none = _lib.PolicyDesc.from_buffer_copy(da)
+    none.layers[5].act = _lib.ACT_NONE
+    for a, c in ((lift, dc), (none, dc), (da, critic_desc()), (dc, da), (da, lift)):
+        assert critic_step(a=a, c=c) == 4
+        assert b"SAC" in lib.rover_last_error()
+        assert policy_step(a=a, c=c) == 4
+        assert lib.rover_sac_polyak(C.byref(a), C.byref(c), C.byref(h), fake, fake, None) == 4
+    assert lib.rover_sac_polyak(None, C.byref(dc), C.byref(h), fake, fake, None) == 1
+    assert lib.rover_sac_polyak(C.byref(da), C.byref(dc), None, fake, fake, None) == 1
+    assert lib.rover_sac_polyak(C.byref(da), C.byref(dc), C.byref(h), None, fake, None) == 1
+    assert lib.rover_sac_polyak(C.byref(da), C.byref(dc), C.byref(h), fake, None, None) == 1
+    assert lib.rover_sac_default_hparams(None) == 1
+
+
+def test_example_parser_defaults():
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("train_sac_example", os.path.join(root, "examples", "09_train_sac.py"))
+    ex = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ex)
+    args = ex.build_parser().parse_args([])
+    assert (args.update, args.batch_size, args.random_timesteps, args.learning_starts) == ("torch", 4096, 0, 0)
+    assert args.memory_size is None and args.save is None
+    args = ex.build_parser().parse_args(["--update", "fused", "--memory_size", "16", "--random_timesteps", "5", "--learning_starts", "3"])
+    assert (args.update, args.memory_size, args.random_timesteps, args.learning_starts) == ("fused", 16, 5, 3)
