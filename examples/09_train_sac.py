@@ -11,7 +11,12 @@ standard normal draws from ONE ``td3_explore.smooth_draw`` launch of width 4 (co
 update's number.  ``--random_timesteps`` acts uniformly at random first, ``--learning_starts`` collects without updating before
 that timestep (skrl's switches of those names).
 
+``--rollout fused`` (with ``--update fused``) replaces everything around ``env.step`` by ``sac_collect.SACCollector``: two HIP
+launches per env step that act from the trainer's current actor and log_std, write the transition straight into the memory and
+return the batch's indices and the update's draws; every draw is counter-based (Philox keyed by ``--seed``).
+
     python examples/09_train_sac.py --num_envs 4096 --timesteps 2000 --update fused --out sac.jsonl
+    python examples/09_train_sac.py --num_envs 4096 --timesteps 2000 --update fused --rollout fused
 """
 import argparse
 import importlib.util
@@ -46,6 +51,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--save", default=None, help="write a checkpoint (policy, critic_1, ..., log_entropy_coefficient)")
     ap.add_argument("--update", choices=("torch", "fused"), default="torch",
                     help="SAC update: the torch spec (TorchSAC) or the fused HIP kernels (FusedSAC)")
+    ap.add_argument("--rollout", choices=("torch", "fused"), default="torch",
+                    help="collection around env.step: torch ops, or the fused collector (SACCollector; needs --update fused)")
     ap.add_argument("--random_timesteps", type=int, default=HPARAMS["random_timesteps"],
                     help="env steps of uniform random actions before the actor acts (skrl random_timesteps)")
     ap.add_argument("--learning_starts", type=int, default=HPARAMS["learning_starts"],
@@ -54,11 +61,14 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.rollout == "fused" and args.update != "fused":
+        ap.error("--rollout fused needs --update fused (the collector reads the fused trainer's actor and log_std)")
     from isaac_rover_orbit_amd import terrain as T
     from isaac_rover_orbit_amd.cfg import RoverEnvCfg
     from isaac_rover_orbit_amd.envs import RoverEnv
     from isaac_rover_orbit_amd.td3_explore import smooth_draw
-    args = build_parser().parse_args(argv)
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
     n, M = args.num_envs, args.memory_size or 2 * args.batch_size
@@ -77,26 +87,39 @@ def main(argv=None):
     gen = torch.Generator(device=dev).manual_seed(args.seed)
     eps = torch.empty(args.batch_size, 4, device=dev)
     obs, _ = env.reset()
-    o = torch.nan_to_num(obs["policy"], neginf=0.0)
+    col = None
+    if args.rollout == "fused":
+        from isaac_rover_orbit_amd.sac_collect import SACCollector
+        col = SACCollector(fused.actor, fused.log_std, memory, seed=args.seed, random_timesteps=args.random_timesteps)
+        col.begin(obs)
+    else:
+        o = torch.nan_to_num(obs["policy"], neginf=0.0)
     out = open(args.out, "w") if args.out else None
     t_log, steps_log, last, updates = time.perf_counter(), 0, {}, 0
     ep_count = torch.zeros((), device=dev); ep_stats = torch.zeros(4, device=dev)
     for step in range(args.timesteps):
-        with torch.no_grad():
-            if step < args.random_timesteps:
-                a = torch.rand(n, 2, device=dev, generator=gen) * 2.0 - 1.0
-            else:
-                mu = fused.actor(o) if fused is not None else policy(o)
-                log_std = fused.log_std if fused is not None else policy.log_std_parameter
-                sigma = log_std.clamp(LOG_STD_MIN, LOG_STD_MAX).exp()
-                a = (mu + sigma * torch.randn(n, 2, device=dev, generator=gen)).clamp(-1.0, 1.0)
-        obs, rew, term, trunc, info = env.step(a)
-        o_next = torch.nan_to_num(obs["policy"], neginf=0.0)
-        memory.add(o, a, rew, o_next, term)
-        o = o_next
+        if col is not None:
+            obs, rew, term, trunc, info = env.step(col.act(step))
+            batch = col.record(obs, rew, term, args.batch_size if step >= args.learning_starts else None)
+            if batch is not None:
+                fused.update(memory, *batch)
+                updates += 1
+        else:
+            with torch.no_grad():
+                if step < args.random_timesteps:
+                    a = torch.rand(n, 2, device=dev, generator=gen) * 2.0 - 1.0
+                else:
+                    mu = fused.actor(o) if fused is not None else policy(o)
+                    log_std = fused.log_std if fused is not None else policy.log_std_parameter
+                    sigma = log_std.clamp(LOG_STD_MIN, LOG_STD_MAX).exp()
+                    a = (mu + sigma * torch.randn(n, 2, device=dev, generator=gen)).clamp(-1.0, 1.0)
+            obs, rew, term, trunc, info = env.step(a)
+            o_next = torch.nan_to_num(obs["policy"], neginf=0.0)
+            memory.add(o, a, rew, o_next, term)
+            o = o_next
         lv = env.episode_log_vector
         ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
-        if step >= args.learning_starts:
+        if col is None and step >= args.learning_starts:
             idx = memory.sample_indices(args.batch_size, gen)
             smooth_draw(args.seed, updates, 1.0, eps)
             if fused is not None:

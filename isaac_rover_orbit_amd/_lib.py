@@ -59,6 +59,8 @@ EXPORTS = [
     "rover_trace_init", "rover_trace_append", "rover_trace_commit_all", "rover_trace_gather", "rover_trace_drained",
     "rover_sac_default_hparams", "rover_sac_hparams_bytes", "rover_sac_state_bytes", "rover_sac_param_floats",  # rover_sac.h
     "rover_sac_workspace_bytes", "rover_sac_critic_step", "rover_sac_policy_step", "rover_sac_polyak",
+    "rover_sac_collect_default_hparams", "rover_sac_collect_hparams_bytes", "rover_sac_collect_act",  # rover_sac_collect.h
+    "rover_sac_collect_record",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -189,6 +191,14 @@ class SacState(C.Structure):
                 ("critic_step_size", C.c_float), ("critic_bc2_sqrt", C.c_float), ("actor_step_size", C.c_float),
                 ("actor_bc2_sqrt", C.c_float), ("entropy_step_size", C.c_float), ("entropy_bc2_sqrt", C.c_float),
                 ("reserved", C.c_float * 2)]
+
+
+SAC_COLLECT_SAMPLE, SAC_COLLECT_MEAN, SAC_COLLECT_RANDOM = 0, 1, 2
+
+
+class SacCollectHparams(C.Structure):
+    """Mirror of ``struct rover_sac_collect_hparams`` (include/rover_sac_collect.h)."""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("mode", C.c_int32)]
 
 
 class RoverHipError(RuntimeError):
@@ -458,6 +468,11 @@ def load():
     lib.rover_sac_policy_step.argtypes = [pd, pd, sah, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, C.c_int64, vp, vp, C.c_size_t, vp, vp,
                                           i32, vp, vp, vp, vp]
     lib.rover_sac_polyak.argtypes = [pd, pd, sah, vp, vp, vp]
+    sch = C.POINTER(SacCollectHparams)
+    lib.rover_sac_collect_default_hparams.argtypes = [sch]
+    lib.rover_sac_collect_hparams_bytes.restype = C.c_size_t
+    lib.rover_sac_collect_act.argtypes = [pd, vp, i32, vp, sch, C.c_uint64, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.rover_sac_collect_record.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.c_int64, vp, sch, C.c_uint64, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -491,6 +506,8 @@ def load():
         raise RoverHipError("struct rover_td3_explore_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_sac_hparams_bytes() != C.sizeof(SacHparams) or lib.rover_sac_state_bytes() != C.sizeof(SacState):
         raise RoverHipError("struct rover_sac_hparams / rover_sac_state of librover_hip.so does not match the Python mirror")
+    if lib.rover_sac_collect_hparams_bytes() != C.sizeof(SacCollectHparams):
+        raise RoverHipError("struct rover_sac_collect_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_trace_stream_bytes() != C.sizeof(TraceStream):
         raise RoverHipError("struct rover_trace_stream of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:

@@ -40,8 +40,11 @@ RANDOM_TAG = 0x54335200           # "T3R\0": word 3 of the Philox counter of the
 SMOOTH_TAG = 0x54334E00           # "T3N\0": ... of the smoothing noise, | action pair
 # every word-3 tag of a Philox stream in this repository: the upper 24 bits name the stream, the low 8 carry an action pair or quad
 # (the envs' own draws: 0, 1 and 2 there, rover_hip.h)
+SAC_ACTION_TAG = 0x53414300       # "SAC\0": the SAC collector's action draws, | action pair (sac_collect.py, rover_sac_collect.h)
+SAC_RANDOM_TAG = 0x53415200       # "SAR\0": ... its random steps' uniforms, | action quad
 TAGS = {"env": 0, "rollout": ROLLOUT_TAG, "lift_rollout": LIFT_ROLLOUT_TAG, "td3_noise": NOISE_TAG,
-        "td3_index": INDEX_TAG, "td3_random": RANDOM_TAG, "td3_smooth": SMOOTH_TAG}
+        "td3_index": INDEX_TAG, "td3_random": RANDOM_TAG, "td3_smooth": SMOOTH_TAG,
+        "sac_action": SAC_ACTION_TAG, "sac_random": SAC_RANDOM_TAG}
 OFF, GAUSSIAN, OU, RANDOM = _lib.TD3_EXPLORE_OFF, _lib.TD3_EXPLORE_GAUSSIAN, _lib.TD3_EXPLORE_OU, _lib.TD3_EXPLORE_RANDOM
 NOISES = {None: OFF, "none": OFF, "gaussian": GAUSSIAN, "ou": OU}
 OU_DEFAULTS = dict(theta=0.15, sigma=0.2, base_scale=1.0)   # skrl OrnsteinUhlenbeckNoise
