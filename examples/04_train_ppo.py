@@ -8,6 +8,11 @@ the PPO update itself uses torch autograd (``--update torch``, the default) or t
 the trainer's parameters directly, no re-packing).  A stand-in for the reference's skrl trainer (examples/02_train/train.py),
 which needs packages that are not part of this repository.
 
+``--preprocess running`` turns on what the reference's agent files call ``state_preprocessor`` / ``value_preprocessor``
+(skrl's RunningStandardScaler on the 965-wide states and on the values): ``isaac_rover_orbit_amd.ppo_scaled`` for the update
+(``TorchScaledPPO`` or ``FusedScaledPPO``) and ``isaac_rover_orbit_amd.rollout_scaled.ScaledRolloutCollector`` for the fused
+rollout.  The default, ``none``, trains on the raw rows as before.
+
     python examples/04_train_ppo.py --num_envs 4096 --iterations 100
 """
 import argparse
@@ -73,12 +78,16 @@ def main():
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--rollouts", type=int, default=60)
     ap.add_argument("--out", default=None, help="write the per-iteration statistics as JSON lines")
-    ap.add_argument("--save", default=None, help="write a skrl-style checkpoint {'policy': state_dict, 'value': state_dict}")
+    ap.add_argument("--save", default=None, help="write a skrl-style checkpoint {'policy': state_dict, 'value': state_dict}; with --preprocess running "
+                                                  "also 'state_preprocessor' and 'value_preprocessor'")
     ap.add_argument("--update", choices=("torch", "fused"), default="torch",
                     help="PPO update: torch autograd + torch.optim.Adam, or the fused HIP kernels (isaac_rover_orbit_amd.ppo)")
     ap.add_argument("--rollout", choices=("torch", "fused"), default="torch",
                     help="rollout glue around env.step: torch ops with torch.randn noise, or isaac_rover_orbit_amd.rollout.RolloutCollector "
                          "(one HIP launch per step: sanitise, both networks, counter-based Gaussian actions, log-prob)")
+    ap.add_argument("--preprocess", choices=("none", "running"), default="none",
+                    help="running: skrl's RunningStandardScaler on states and values (state_preprocessor / value_preprocessor of "
+                         "rover_ppo.yaml), as HIP kernels wherever --update / --rollout is fused")
     args = ap.parse_args()
     torch.manual_seed(42)
     dev = torch.device("cuda")
@@ -91,23 +100,48 @@ def main():
     opt = torch.optim.Adam(list(policy.parameters()) + list(value.parameters()), lr=1e-4)
     gamma, lam, clip, vclip, kl_thr = GAMMA, LAM, CLIP, VCLIP, KL_THR
     fused = None
+    scaled = args.preprocess == "running"
+    tscaled = None                              # the torch update behind the scalers
     if args.update == "fused":
         from isaac_rover_orbit_amd.ppo import FusedPPO
-        fused = FusedPPO(policy.state_dict(), value.state_dict(), lr=1e-4)
+        from isaac_rover_orbit_amd.ppo_scaled import FusedScaledPPO
+        fused = (FusedScaledPPO if scaled else FusedPPO)(policy.state_dict(), value.state_dict(), lr=1e-4)
+    elif scaled:
+        from isaac_rover_orbit_amd.ppo_scaled import TorchScaledPPO
+        tscaled = TorchScaledPPO(policy, value, lr=1e-4, device=dev)
+    # what the networks read and what the buffer stores of the critic, for the torch rollout glue
+    if not scaled:
+        standardise, unscale = (lambda x: x), (lambda v: v)
+    elif fused is not None:
+        standardise, unscale = fused.state_scaler.forward, (lambda v: fused.value_scaler.inverse(v.contiguous()))
+    else:
+        standardise = tscaled.state_preprocessor
+        unscale = lambda v: tscaled.value_preprocessor(v, inverse=True)  # noqa: E731
 
     obs_buf = torch.empty(Tn, n, 965, device=dev)
     act_buf = torch.empty(Tn, n, 2, device=dev)
     logp_buf, val_buf, rew_buf = (torch.empty(Tn, n, device=dev) for _ in range(3))
     done_buf = torch.empty(Tn, n, device=dev)
     collector = None
+    dev_scalers = None                          # device copies of the torch update's scalers, for the fused rollout
     if args.rollout == "fused":
         from isaac_rover_orbit_amd.rollout import RolloutCollector
+        from isaac_rover_orbit_amd.rollout_scaled import ScaledRolloutCollector
         if fused is not None:                   # the trainer's networks and log-std by reference: always the current parameters
-            collector = RolloutCollector(fused.actor, fused.critic, fused.log_std, n, Tn, seed=42)
+            if scaled:                          # ... and its two scaler blocks
+                collector = ScaledRolloutCollector(fused.actor, fused.critic, fused.log_std, fused.state_scaler, fused.value_scaler,
+                                                   n, Tn, seed=42)
+            else:
+                collector = RolloutCollector(fused.actor, fused.critic, fused.log_std, n, Tn, seed=42)
         else:                                   # re-packed networks are handed over at the top of every iteration
-            collector = RolloutCollector(RoverNet.from_state_dict(policy.state_dict(), final_act="tanh"),
-                                         RoverNet.from_state_dict(value.state_dict(), final_act="none"),
-                                         policy.log_std_parameter.detach(), n, Tn, seed=42)
+            nets = (RoverNet.from_state_dict(policy.state_dict(), final_act="tanh"),
+                    RoverNet.from_state_dict(value.state_dict(), final_act="none"))
+            if scaled:
+                from isaac_rover_orbit_amd.scaler import DeviceScaler
+                dev_scalers = (DeviceScaler(965, dev), DeviceScaler(1, dev))
+                collector = ScaledRolloutCollector(*nets, policy.log_std_parameter.detach(), *dev_scalers, n, Tn, seed=42)
+            else:
+                collector = RolloutCollector(*nets, policy.log_std_parameter.detach(), n, Tn, seed=42)
         obs_buf, act_buf, logp_buf, val_buf = collector.obs, collector.actions, collector.logp, collector.val
         rew_buf, done_buf = collector.rew, collector.done
     obs, _ = env.reset()
@@ -127,6 +161,9 @@ def main():
         ep_count = torch.zeros((), device=dev); ep_stats = torch.zeros(4, device=dev)
         if collector is not None:
             collector.actor, collector.critic = actor, critic
+            if dev_scalers is not None:         # the torch scalers' statistics after the last update
+                dev_scalers[0].load_state_dict(tscaled.state_preprocessor.state_dict())
+                dev_scalers[1].load_state_dict(tscaled.value_preprocessor.state_dict())
         for t in range(Tn):
             if collector is not None:           # the raw rows go in; slot t of every buffer comes out
                 obs, rew, term, trunc, info = env.step(collector.act(t, o))
@@ -135,10 +172,11 @@ def main():
                 lv = env.episode_log_vector
                 ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
                 continue
-            mean = actor(o)
+            s = standardise(o)                  # the buffer keeps the raw rows; the networks read the standardised ones
+            mean = actor(s)
             a = mean + std * torch.randn_like(mean)
             logp_buf[t] = (-0.5 * ((a - mean) / std) ** 2 - log_std - 0.9189385332).sum(1)
-            val_buf[t] = critic(o).squeeze(1)
+            val_buf[t] = unscale(critic(s)).squeeze(1)
             obs_buf[t], act_buf[t] = o, a
             obs, rew, term, trunc, info = env.step(a.clamp(-1.0, 1.0))      # clip_actions (models.py:66)
             o = torch.nan_to_num(obs["policy"], neginf=0.0)
@@ -149,15 +187,19 @@ def main():
         if fused is not None:
             # ---- GAE and the PPO update on the fused HIP kernels (isaac_rover_orbit_amd.ppo)
             with torch.no_grad():
-                last_v = collector.last_value(o) if collector is not None else critic(o).squeeze(1)
+                last_v = collector.last_value(o) if collector is not None else unscale(critic(standardise(o))).squeeze(1)
                 adv, ret = fused.gae(rew_buf, done_buf, val_buf, last_v)
                 adv = (adv - adv.mean()) / (adv.std() + 1e-8)
-            kls, _ = fused.update(obs_buf, act_buf, logp_buf, val_buf, ret, adv)
+            if scaled:                          # skrl PPO._update: the value scaler trains on the values, then on the returns
+                val_s, ret_s = fused.standardize_values(val_buf, ret)
+                kls, _ = fused.update(obs_buf, act_buf, logp_buf, val_s, ret_s, adv)
+            else:
+                kls, _ = fused.update(obs_buf, act_buf, logp_buf, val_buf, ret, adv)
             kl_mean = kls[-1]
         else:
             # ---- GAE (skrl PPO: bootstraps through time-outs like the reference's config)
             with torch.no_grad():
-                last_v = collector.last_value(o) if collector is not None else critic(o).squeeze(1)
+                last_v = collector.last_value(o) if collector is not None else unscale(critic(standardise(o))).squeeze(1)
                 adv = torch.zeros_like(rew_buf); gae = torch.zeros(n, device=dev)
                 for t in reversed(range(Tn)):
                     nv = last_v if t == Tn - 1 else val_buf[t + 1]
@@ -171,7 +213,10 @@ def main():
             B = Tn * n
             fo, fa, flp, fv, fr, fadv = (x.reshape(B, *x.shape[2:]) for x in (obs_buf, act_buf, logp_buf, val_buf, ret, adv))
             kl_mean = 0.0
-            for epoch in range(4):
+            if scaled:                          # the same update behind the two scalers (ppo_scaled.TorchScaledPPO)
+                val_s, ret_s = tscaled.standardize_values(fv, fr)
+                kl_mean = tscaled.update(fo, fa, flp, val_s, ret_s, fadv)[0][-1]
+            for epoch in range(0 if scaled else 4):   # the unscaled update, as before
                 perm = torch.randperm(B, device=dev)
                 kls = []
                 for mb in perm.chunk(60):
@@ -189,13 +234,15 @@ def main():
         torch.cuda.synchronize()
         st = {"iteration": it, "mean_step_reward": rew_buf.mean().item(), "episodes": ep_count.item(),
               "time_out": ep_stats[0].item(), "success": ep_stats[1].item(), "far": ep_stats[2].item(),
-              "collision": ep_stats[3].item(), "kl": kl_mean, "lr": opt.param_groups[0]["lr"] if fused is None else fused.lr,
+              "collision": ep_stats[3].item(), "kl": kl_mean,
+              "lr": fused.lr if fused is not None else tscaled.lr if tscaled is not None else opt.param_groups[0]["lr"],
               "rollout_s": t_roll, "rollout_env_steps_per_s": Tn * n / t_roll, "iteration_s": time.perf_counter() - t0}
         print(json.dumps(st), flush=True)
         if out:
             out.write(json.dumps(st) + "\n"); out.flush()
     if args.save:
-        torch.save(fused.state_dict() if fused is not None else {"policy": policy.state_dict(), "value": value.state_dict()}, args.save)
+        torch.save(fused.state_dict() if fused is not None else tscaled.state_dict() if tscaled is not None
+                   else {"policy": policy.state_dict(), "value": value.state_dict()}, args.save)
     env.close()
 
 

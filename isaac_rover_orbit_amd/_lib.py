@@ -61,6 +61,8 @@ EXPORTS = [
     "rover_sac_workspace_bytes", "rover_sac_critic_step", "rover_sac_policy_step", "rover_sac_polyak",
     "rover_sac_collect_default_hparams", "rover_sac_collect_hparams_bytes", "rover_sac_collect_act",  # rover_sac_collect.h
     "rover_sac_collect_record",
+    "rover_scaler_default_hparams", "rover_scaler_hparams_bytes", "rover_scaler_doubles", "rover_scaler_workspace_bytes",  # rover_scaler.h
+    "rover_scaler_train", "rover_scaler_apply",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -199,6 +201,27 @@ SAC_COLLECT_SAMPLE, SAC_COLLECT_MEAN, SAC_COLLECT_RANDOM = 0, 1, 2
 class SacCollectHparams(C.Structure):
     """Mirror of ``struct rover_sac_collect_hparams`` (include/rover_sac_collect.h)."""
     _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("mode", C.c_int32)]
+
+
+SCALER_MAX_WIDTH, SCALER_CHUNK_ROWS = 1024, 64
+SCALER_INVERSE, SCALER_SANITISE = 1, 2
+
+
+class ScalerHparams(C.Structure):
+    """Mirror of ``struct rover_scaler_hparams`` (include/rover_scaler.h)."""
+    _fields_ = [("eps", C.c_float), ("clip", C.c_float)]
+
+
+def scaler_doubles(width: int) -> int:
+    """Mirror of ``rover_scaler_doubles``: mean[width], var[width], count."""
+    return 2 * width + 1 if 1 <= width <= SCALER_MAX_WIDTH else 0
+
+
+def scaler_workspace_bytes(width: int, max_rows: int) -> int:
+    """Mirror of ``rover_scaler_workspace_bytes``: the batch mean and one float64 sum per column and chunk of 64 rows."""
+    if not 1 <= width <= SCALER_MAX_WIDTH or max_rows < 2:
+        return 0
+    return 8 * width * (1 + (max_rows + SCALER_CHUNK_ROWS - 1) // SCALER_CHUNK_ROWS)
 
 
 class RoverHipError(RuntimeError):
@@ -473,6 +496,15 @@ def load():
     lib.rover_sac_collect_hparams_bytes.restype = C.c_size_t
     lib.rover_sac_collect_act.argtypes = [pd, vp, i32, vp, sch, C.c_uint64, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.rover_sac_collect_record.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.c_int64, vp, sch, C.c_uint64, vp]
+    slh = C.POINTER(ScalerHparams)
+    lib.rover_scaler_default_hparams.argtypes = [slh]
+    lib.rover_scaler_hparams_bytes.restype = C.c_size_t
+    lib.rover_scaler_doubles.argtypes = [i32]
+    lib.rover_scaler_doubles.restype = C.c_size_t
+    lib.rover_scaler_workspace_bytes.argtypes = [i32, i32]
+    lib.rover_scaler_workspace_bytes.restype = C.c_size_t
+    lib.rover_scaler_train.argtypes = [slh, vp, i32, vp, vp, i32, vp, C.c_size_t, vp]
+    lib.rover_scaler_apply.argtypes = [slh, vp, i32, vp, vp, i32, i32, vp, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -508,6 +540,8 @@ def load():
         raise RoverHipError("struct rover_sac_hparams / rover_sac_state of librover_hip.so does not match the Python mirror")
     if lib.rover_sac_collect_hparams_bytes() != C.sizeof(SacCollectHparams):
         raise RoverHipError("struct rover_sac_collect_hparams of librover_hip.so does not match the Python mirror")
+    if lib.rover_scaler_hparams_bytes() != C.sizeof(ScalerHparams):
+        raise RoverHipError("struct rover_scaler_hparams of librover_hip.so does not match the Python mirror")
     if lib.rover_trace_stream_bytes() != C.sizeof(TraceStream):
         raise RoverHipError("struct rover_trace_stream of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
