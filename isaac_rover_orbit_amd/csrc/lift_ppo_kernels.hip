@@ -26,6 +26,7 @@
 #include "../../include/rover_lift_train.h"
 #include "../../include/rover_policy.h"
 #include "rover_internal.hpp"
+#include "train_math.hpp"
 
 namespace {
 
@@ -63,8 +64,6 @@ struct LiftHp {
     float clip, vclip, vscale, ls_min, ls_max, kl_stop, s_eps, s_clip;
 };
 
-// ELU exactly as policy_kernels.hip's activate(): rover_policy.h fixes expm1f
-__device__ __forceinline__ float elu(float v) { return v > 0.0f ? v : expm1f(v); }
 __device__ __forceinline__ float clampf_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }   // NaN passes
 // RunningStandardScaler forward / inverse (rover_lift_train.h), fp32 with explicit roundings
 __device__ __forceinline__ float scaler_fwd(float x, double mean, double var, float eps, float clip)

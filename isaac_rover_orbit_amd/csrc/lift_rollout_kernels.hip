@@ -20,6 +20,7 @@
 #include "../../include/rover_lift_rollout.h"
 #include "../../include/rover_policy.h"
 #include "rover_internal.hpp"
+#include "train_math.hpp"
 
 namespace {
 
@@ -40,8 +41,6 @@ constexpr uint32_t LRO_TAG = 0x4C524F00u;            // "LRO\0": word 3 of the P
 
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// ELU exactly as policy_kernels.hip's activate(): rover_policy.h fixes expm1f
-__device__ __forceinline__ float elu(float v) { return v > 0.0f ? v : expm1f(v); }
 __device__ __forceinline__ float clampf_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }   // NaN passes
 // RunningStandardScaler forward / inverse (rover_lift_train.h), fp32 with explicit roundings: the text of lift_ppo_kernels.hip
 __device__ __forceinline__ float scaler_fwd(float x, double mean, double var, float eps, float clip)
@@ -52,22 +51,6 @@ __device__ __forceinline__ float scaler_fwd(float x, double mean, double var, fl
 __device__ __forceinline__ float scaler_inv(float x, double mean, double var, float clip)
 {
     return __fadd_rn(__fmul_rn(sqrtf((float)var), clampf_nan(x, -clip, clip)), (float)mean);
-}
-
-// Philox4x32-10 (the text of rollout_kernels.hip)
-__device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
 // one 16 x 16 output tile of a forward layer: rover_policy_forward's MFMA sequence (k groups ascending, k = 16 g + 4 j + akq)

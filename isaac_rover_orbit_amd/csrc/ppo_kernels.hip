@@ -24,6 +24,7 @@
 #include "../../include/rover_policy.h"
 #include "../../include/rover_train.h"
 #include "rover_internal.hpp"
+#include "train_math.hpp"
 
 namespace {
 
@@ -48,43 +49,6 @@ enum { S_A1 = 0, S_M = 80, S_A3 = 144, S_A4 = 400, S_A5 = 560, S_DZ1 = 688, S_DZ
 constexpr int NORM_BLOCKS = 128;
 
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-// Cephes expf / tanhf as explicit fp32 sequences: the same text as policy_kernels.hip and oracle/policy_oracle.c
-__device__ __forceinline__ float rv_expf(float x)
-{
-    if (x > 88.0f) return INFINITY;
-    if (x < -88.0f) return 0.0f;
-    const float z = floorf(1.44269504088896341f * x + 0.5f);
-    x = x - z * 0.693359375f;
-    x = x - z * -2.12194440e-4f;
-    const float zz = x * x;
-    float p = 1.9875691500e-4f;
-    p = p * x + 1.3981999507e-3f;
-    p = p * x + 8.3334519073e-3f;
-    p = p * x + 4.1665795894e-2f;
-    p = p * x + 1.6666665459e-1f;
-    p = p * x + 5.0000001201e-1f;
-    p = p * zz + x + 1.0f;
-    return ldexpf(p, (int)z);
-}
-__device__ __forceinline__ float rv_tanhf(float x)
-{
-    const float z = fabsf(x);
-    if (z > 44.0f) return x > 0.0f ? 1.0f : -1.0f;
-    if (z >= 0.625f) {
-        const float s = rv_expf(z + z);
-        const float r = 1.0f - 2.0f / (s + 1.0f);
-        return x < 0.0f ? -r : r;
-    }
-    if (x == 0.0f) return x;
-    const float s = x * x;
-    float p = -5.70498872745e-3f;
-    p = p * s + 2.06390887954e-2f;
-    p = p * s - 5.37397155531e-2f;
-    p = p * s + 1.33314422036e-1f;
-    p = p * s - 3.33332819422e-1f;
-    return p * s * x + x;
-}
 
 // where the parameters of each network and log_std sit in the flat vector (offsets in floats)
 struct PpoNets {
@@ -159,7 +123,6 @@ __device__ __forceinline__ void split_chain16(float (&out)[RB], const float *in,
         }
     }
 }
-__device__ __forceinline__ float leaky(float v, float slope) { return v > 0.0f ? v : v * slope; }
 
 struct RowsArgs {
     PpoNets nets;

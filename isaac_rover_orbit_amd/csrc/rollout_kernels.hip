@@ -21,6 +21,7 @@
 #include "../../include/rover_hip.h"
 #include "../../include/rover_rollout.h"
 #include "rover_internal.hpp"
+#include "train_math.hpp"
 
 namespace {
 
@@ -40,42 +41,6 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// Cephes expf / tanhf as explicit fp32 sequences: the text of policy_kernels.hip and oracle/policy_oracle.c
-__device__ __forceinline__ float rv_expf(float x)
-{
-    if (x > 88.0f) return INFINITY;
-    if (x < -88.0f) return 0.0f;
-    const float z = floorf(1.44269504088896341f * x + 0.5f);
-    x = x - z * 0.693359375f;
-    x = x - z * -2.12194440e-4f;
-    const float zz = x * x;
-    float p = 1.9875691500e-4f;
-    p = p * x + 1.3981999507e-3f;
-    p = p * x + 8.3334519073e-3f;
-    p = p * x + 4.1665795894e-2f;
-    p = p * x + 1.6666665459e-1f;
-    p = p * x + 5.0000001201e-1f;
-    p = p * zz + x + 1.0f;
-    return ldexpf(p, (int)z);
-}
-__device__ __forceinline__ float rv_tanhf(float x)
-{
-    const float z = fabsf(x);
-    if (z > 44.0f) return x > 0.0f ? 1.0f : -1.0f;
-    if (z >= 0.625f) {
-        const float s = rv_expf(z + z);
-        const float r = 1.0f - 2.0f / (s + 1.0f);
-        return x < 0.0f ? -r : r;
-    }
-    if (x == 0.0f) return x;
-    const float s = x * x;
-    float p = -5.70498872745e-3f;
-    p = p * s + 2.06390887954e-2f;
-    p = p * s - 5.37397155531e-2f;
-    p = p * s + 1.33314422036e-1f;
-    p = p * s - 3.33332819422e-1f;
-    return p * s * x + x;
-}
 __device__ __forceinline__ float activate(float v, int act, float slope)
 {
     if (act == ROVER_ACT_LEAKY_RELU) return v > 0.0f ? v : v * slope;
@@ -90,22 +55,6 @@ __device__ __forceinline__ float sanitise(float x)
     if (x == INFINITY) return FLT_MAX;
     if (x == -INFINITY) return 0.0f;
     return x;
-}
-
-// Philox4x32-10 (the text of rover_kernels.hip)
-__device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
 struct RolLaunch {

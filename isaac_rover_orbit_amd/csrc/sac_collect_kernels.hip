@@ -21,6 +21,7 @@
 #include "../../include/rover_td3_explore.h"
 #include "rover_internal.hpp"
 #include "td3_actor_tile.hpp"
+#include "train_math.hpp"
 
 namespace {
 
@@ -30,46 +31,6 @@ constexpr int FLAT_THREADS = 256;             // the random kernel
 constexpr int REC_THREADS = 256, REC_PER = 4; // record kernel: pieces (16 bytes, or one float on the scalar path) per thread
 constexpr float LS_MIN = -20.0f, LS_MAX = 2.0f, U_MIN = -1.0f, U_MAX = 1.0f;
 constexpr float HALF_LN_2PI = 0.91893853320467274178f;
-
-// Cephes expf / tanhf as explicit fp32 sequences: the same text as policy_kernels.hip and sac_kernels.hip
-__device__ __forceinline__ float rv_expf(float x)
-{
-    if (x > 88.0f) return INFINITY;
-    if (x < -88.0f) return 0.0f;
-    const float z = floorf(1.44269504088896341f * x + 0.5f);
-    x = x - z * 0.693359375f;
-    x = x - z * -2.12194440e-4f;
-    const float zz = x * x;
-    float p = 1.9875691500e-4f;
-    p = p * x + 1.3981999507e-3f;
-    p = p * x + 8.3334519073e-3f;
-    p = p * x + 4.1665795894e-2f;
-    p = p * x + 1.6666665459e-1f;
-    p = p * x + 5.0000001201e-1f;
-    p = p * zz + x + 1.0f;
-    return ldexpf(p, (int)z);
-}
-__device__ __forceinline__ float rv_tanhf(float x)
-{
-    const float z = fabsf(x);
-    if (z > 44.0f) return x > 0.0f ? 1.0f : -1.0f;
-    if (z >= 0.625f) {
-        const float s = rv_expf(z + z);
-        const float r = 1.0f - 2.0f / (s + 1.0f);
-        return x < 0.0f ? -r : r;
-    }
-    if (x == 0.0f) return x;
-    const float s = x * x;
-    float p = -5.70498872745e-3f;
-    p = p * s + 2.06390887954e-2f;
-    p = p * s - 5.37397155531e-2f;
-    p = p * s + 1.33314422036e-1f;
-    p = p * s - 3.33332819422e-1f;
-    return p * s * x + x;
-}
-
-// torch.clamp: a NaN stays a NaN
-__device__ __forceinline__ float tclamp(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
 
 // torch.nan_to_num(x, nan = 0, posinf = FLT_MAX, neginf = 0): finite values (and -0) pass unchanged (rollout_kernels.hip)
 __device__ __forceinline__ float sanitise(float x)

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "../../include/rover_policy.h"
+#include "train_math.hpp"
 
 namespace {
 
@@ -36,24 +37,6 @@ constexpr uint32_t NOISE_TAG = 0x54443300u;   // "TD3\0": word 3 of the Philox c
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-__device__ __forceinline__ float leaky(float v, float slope) { return v > 0.0f ? v : v * slope; }
-
-// Philox4x32-10 (the text of rover_kernels.hip)
-__device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 template <int NT>
 __device__ __forceinline__ void mfma_one_group(v4f (&acc)[NT], const float (&a)[4], const v4f (&b)[NT])

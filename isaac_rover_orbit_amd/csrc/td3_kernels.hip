@@ -1,18 +1,9 @@
 // td3_kernels.hip -- fused TD3 update of the rover's actor and twin critics (gfx950 / CDNA4, wave64).
 //
 // skrl TD3._update for the reference actor and the Q(s, a) critic; see include/rover_td3.h for the contract and the
-// reduction order.  The networks run layer by layer over the sampled rows, every dense product on v_mfma_f32_16x16x4_f32,
-// in the pattern of trpo_kernels.hip (adapted here; that file is not shared):
-//   td3_dense_kernel    Z = A W^T + b, act(Z) for up to 4 networks per launch (blockIdx.z): one wave per 16 rows x 64
-//                       columns; the packed weights are the B fragments as they lie (one float4 per lane per 16 k).  Layer 2
-//                       also writes the MLP input's proprioceptive columns and, for a critic, its two action columns;
-//   td3_back_kernel     reverse dA = dZ W (times LeakyReLU' of the stored activation, or not: the action columns), up to 2
-//                       networks per launch;
-//   td3_wgrad_kernel    dW = dZ^T A and db = sum dZ per (16 x 16 tile, 512-row chunk) over up to 12 layers (both critics)
-//                       in the packed layout;
-//   td3_combine_kernel  the chunk partials added in chunk order;
-// plus the gather of the sampled rows from the observation ring, one-thread-per-row heads (y, loss gradients), fixed-order
-// reductions into the device state, Adam and Polyak.
+// reduction order.  The networks' forward, backward and weight gradients, the gather of the sampled rows, Adam and Polyak are
+// offpolicy_net.hpp's, shared with sac_kernels.hip.  This file adds the smoothing of the target action, the one-thread-per-row
+// heads (y, loss gradients), their fixed-order reductions into the device state, the workspace and the entry points.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -23,268 +14,13 @@
 #include "../../include/rover_policy.h"
 #include "../../include/rover_td3.h"
 #include "rover_internal.hpp"
+#include "offpolicy_net.hpp"
+#include "train_math.hpp"
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-constexpr int OBS = 965, PROP = 4, ENC_OFF = 3;
-constexpr int ACOL = 64;                                     // first action column of the critic's MLP input
-constexpr int NL = 6;
-constexpr int AK[NL] = {961, 80, 64, 256, 160, 128};         // in features of the actor's layers
-constexpr int CK[NL] = {961, 80, 66, 256, 160, 128};         // ... of the critic's (MLP input [prop, enc, a])
-constexpr int LN[NL - 1] = {80, 60, 256, 160, 128};          // out features of layers 1 .. 5 (layer 6: 2 actor, 1 critic)
-constexpr int FT = 256;                                      // threads of every multi-thread kernel here
-constexpr int CH = 512;                                      // rows per weight-gradient chunk
-constexpr int MAXZ = 4;                                      // networks per dense launch
-constexpr int MAXJ = 2 * NL;                                 // layers per weight-gradient launch
-// per-row matrices of one network (output of layer l, pitch MW[l]; layer 2's output sits at columns 4 .. 63 of the MLP
-// input M, whose columns 64, 65 hold a critic's action)
-constexpr int MW[NL] = {80, 68, 256, 160, 128, 4};
-constexpr int ROW_F = 80 + 68 + 256 + 160 + 128 + 4;        // 696
+using State = rover_td3_state;
 constexpr int NSUM = 5;                                      // per-row sums of the critic head
-constexpr int RP = 8;                                        // stride of a block's partials
-
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-__host__ __device__ inline size_t al4(size_t n) { return (n + 3) & ~(size_t)3; }
-
-// fixed halving tree over the 256 threads of the block; the total in every thread after the call
-__device__ __forceinline__ float block_sum(float v, float *red)
-{
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = FT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-// ---- gather: the ring rows of s and s' (64-bit row numbers) and the stored transition of every sampled row
-struct GatherArgs {
-    const int64_t *idx; int n; int64_t valid;
-    int num_envs, slots;
-    const int32_t *pos;
-    const float *act, *rew; const uint8_t *term;     // NULL for the actor step
-    int64_t *ro_s, *ro_n;
-    float *a, *r, *nt;
-    rover_td3_state *st;
-};
-__global__ __launch_bounds__(FT) void td3_gather_kernel(GatherArgs A)
-{
-    const int row = blockIdx.x * FT + threadIdx.x;
-    if (row >= A.n) return;
-    int64_t i = A.idx[row];
-    bool bad = i < 0 || i >= A.valid;
-    if (bad) i = 0;
-    const int64_t k = i / A.num_envs, e = i - k * A.num_envs;
-    int32_t p = A.pos[k];
-    if (p < 0 || p >= A.slots) { bad = true; p = 0; }
-    if (bad) A.st->bad_index = 1;                       // every writer stores the same word
-    A.ro_s[row] = (int64_t)p * A.num_envs + e;
-    A.ro_n[row] = (int64_t)(p + 1 == A.slots ? 0 : p + 1) * A.num_envs + e;
-    if (A.act) {
-        A.a[2 * (size_t)row] = A.act[2 * i];
-        A.a[2 * (size_t)row + 1] = A.act[2 * i + 1];
-        A.r[row] = A.rew[i];
-        A.nt[row] = A.term[i] ? 0.0f : 1.0f;
-    }
-}
-
-// ---- dense layer forward, one network per blockIdx.z
-enum { ACT_NONE_ = 0, ACT_LEAKY_ = 1 };
-struct Dense {
-    const float *x; int xp;        // input A: row r at x + (ro ? ro[r] : r) * xp
-    const int64_t *ro;
-    const float *W, *b;            // packed weights / bias
-    float *out; int op, ocol;      // output matrix, pitch, first column
-    const float *prop;             // layer 2: M[r][0 .. 4) = prop[pro[r] * OBS + c] (the observation ring)
-    const int64_t *pro;
-    const float *ain; int aip;     // layer 2 of a critic: M[r][64 + c] = ain[r * aip + c]
-    int K, N, act;
-};
-struct DenseLaunch {
-    Dense d[MAXZ];
-    int rows;
-    float slope;
-};
-__global__ __launch_bounds__(FT) void td3_dense_kernel(DenseLaunch L)
-{
-    const Dense &A = L.d[blockIdx.z];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rr = lane >> 4, cc = lane & 15;
-    const int r0 = blockIdx.x * 64 + wave * 16, t0 = blockIdx.y * 4;    // first row, first 16-column tile
-    const int G = cdiv(A.K, 16), NT = cdiv(A.N, 16);
-    if (A.prop && blockIdx.y == 0) {                                     // the proprioceptive (and action) columns of M
-        const int r = r0 + (lane >> 2), c = lane & 3;
-        if (r < L.rows) {
-            A.out[(size_t)r * A.op + c] = A.prop[(size_t)A.pro[r] * OBS + c];
-            if (A.ain && c < 2) A.out[(size_t)r * A.op + ACOL + c] = A.ain[(size_t)r * A.aip + c];
-        }
-    }
-    const int ra = r0 + cc;                                              // the A operand's row of this lane
-    const bool row_ok = ra < L.rows;
-    const float *xrow = row_ok ? A.x + (A.ro ? (size_t)A.ro[ra] : (size_t)ra) * A.xp : nullptr;
-    v4f acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
-    // sum_k a[r][k] * W[n][k] with W's packed fragments: lane (n & 15) + 16 (k & 3) of fragment (n / 16, k / 16) holds
-    // W[n][16 g + 4 e + (k & 3)] in element e, exactly the B operand (k = rr, j = cc) of the 4 MFMAs of a 16-k group
-    for (int g = 0; g < G; ++g) {
-        float a[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int k = 16 * g + 4 * e + rr;
-            a[e] = (xrow && k < A.K) ? xrow[k] : 0.0f;
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if (t0 + t < NT) {
-                const v4f w = reinterpret_cast<const v4f *>(A.W)[((size_t)(t0 + t) * G + g) * 64 + cc + 16 * rr];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], w[e], acc[t], 0, 0, 0);
-            }
-        }
-    }
-    // D[i][j]: lane holds i = 4 rr + jj, j = cc
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int col = 16 * (t0 + t) + cc;
-        if (t0 + t >= NT || col >= A.N) continue;
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int r = r0 + 4 * rr + jj;
-            if (r >= L.rows) continue;
-            const float s = acc[t][jj] + A.b[col];
-            A.out[(size_t)r * A.op + A.ocol + col] = A.act == ACT_LEAKY_ ? (s > 0.0f ? s : s * L.slope) : s;
-        }
-    }
-}
-
-// ---- reverse: out[r][k - ocol] = (sum_n dZ[r][n] W[n][k]) * LeakyReLU'(aref[r][k]) (aref NULL: no derivative) for k in
-// [k0, k0 + nk), one network per blockIdx.z
-struct Back {
-    const float *dz; int dzp;      // dZ of layer l (rows, N)
-    const float *W; int K, N;      // packed weights of layer l (N x K)
-    const float *aref; int arp;    // stored input activation of layer l, or NULL
-    float *out; int op, ocol;
-    int k0, nk;
-};
-struct BackLaunch {
-    Back d[2];
-    int rows;
-    float slope;
-};
-__device__ __forceinline__ float w_at(const float *Wp, int G, int n, int k)
-{
-    return Wp[((((size_t)(n >> 4) * G + (k >> 4)) * 64 + (n & 15) + 16 * (k & 3)) << 2) + ((k >> 2) & 3)];
-}
-__global__ __launch_bounds__(FT) void td3_back_kernel(BackLaunch L)
-{
-    const Back &A = L.d[blockIdx.z];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int rr = lane >> 4, cc = lane & 15;
-    const int r0 = blockIdx.x * 64 + wave * 16, c0 = blockIdx.y * 64;    // first row, first output column (relative to k0)
-    const int G = cdiv(A.K, 16);
-    const int ra = r0 + cc;
-    const bool row_ok = ra < L.rows;
-    v4f acc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
-    for (int nb = 0; nb < A.N; nb += 4) {
-        const int n = nb + rr;
-        const float a = (row_ok && n < A.N) ? A.dz[(size_t)ra * A.dzp + n] : 0.0f;   // A operand (i = cc, k = rr)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int kc = c0 + 16 * t + cc;                                           // B operand (k = rr, j = cc)
-            const float w = (n < A.N && kc < A.nk) ? w_at(A.W, G, n, A.k0 + kc) : 0.0f;
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w, acc[t], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int kc = c0 + 16 * t + cc;
-        if (kc >= A.nk) continue;
-        const int k = A.k0 + kc;
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int r = r0 + 4 * rr + jj;
-            if (r >= L.rows) continue;
-            const float d = acc[t][jj];
-            A.out[(size_t)r * A.op + (k - A.ocol)] = (!A.aref || A.aref[(size_t)r * A.arp + k] > 0.0f) ? d : d * L.slope;
-        }
-    }
-}
-
-// ---- weight / bias gradients: one wave per (layer, 16 x 16 tile of the packed weights or a 16-row bias tile, chunk)
-struct WgradArgs {
-    const float *am[MAXJ]; int ap[MAXJ];      // input of layer j: row r at am + (ro ? ro[r] : r) * ap
-    const int64_t *ro[MAXJ];
-    const float *dz[MAXJ]; int dzp[MAXJ];     // dZ of layer j, pitch
-    int K[MAXJ], N[MAXJ];
-    uint32_t w_off[MAXJ], b_off[MAXJ];        // packed offsets relative to the block the partials cover
-    int jobs[MAXJ + 1];                       // prefix sums of the per-layer job counts
-    int nl, rows, P;                          // layers; rows; floats of the block (the partial's stride)
-    float *part;                              // (chunks, P)
-};
-__global__ __launch_bounds__(FT) void td3_wgrad_kernel(WgradArgs A)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int job = blockIdx.x * 4 + wave;
-    if (job >= A.jobs[A.nl]) return;
-    int l = 0;
-    while (job >= A.jobs[l + 1]) ++l;
-    job -= A.jobs[l];
-    const int K = A.K[l], N = A.N[l], G = cdiv(K, 16);
-    const int t = job / (G + 1), g = job - t * (G + 1);
-    const bool bias = g == G;
-    const int rr = lane >> 4, cc = lane & 15;
-    const int col = 16 * t + cc, kin = 16 * g + cc;
-    const bool col_ok = col < N, k_ok = !bias && kin < K;
-    const int rb0 = blockIdx.y * CH, rb1 = min(rb0 + CH, A.rows);
-    const float *dz = A.dz[l], *am = A.am[l];
-    const int64_t *ro = A.ro[l];
-    const int dzp = A.dzp[l], ap = A.ap[l];
-    v4f acc = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
-    // A operand: lane (i = cc, k = rr) = dZ[row][16 t + cc]; B operand: lane (k = rr, j = cc) = A[row][16 g + cc]
-    for (int rb = rb0; rb < rb1; rb += 4) {
-        const int r = rb + rr;
-        const bool ok = r < rb1;
-        const float a = ok && col_ok ? dz[(size_t)r * dzp + col] : 0.0f;
-        float b;
-        if (bias) b = ok ? 1.0f : 0.0f;
-        else b = ok && k_ok ? am[(ro ? (size_t)ro[r] : (size_t)r) * ap + kin] : 0.0f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-    }
-    float *part = A.part + (size_t)blockIdx.y * A.P;
-    // lane holds D[i = 4 rr + jj][j = cc] = dW[16 t + i][16 g + j]
-    if (!bias) {
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int i = 4 * rr + jj, j = cc;
-            const bool ok = 16 * t + i < N && 16 * g + j < K;
-            // packed position: lane' = i + 16 (j & 3), element j >> 2
-            part[A.w_off[l] + (((size_t)t * G + g) * 64 + i + 16 * (j & 3)) * 4 + (j >> 2)] = ok ? acc[jj] : 0.0f;
-        }
-    } else if (cc == 0) {
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int c = 16 * t + 4 * rr + jj;
-            if (c < ((N + 3) & ~3)) part[A.b_off[l] + c] = c < N ? acc[jj] : 0.0f;
-        }
-    }
-}
-
-// out[e] = sum_c part[c][e] (c ascending) for e < P
-__global__ __launch_bounds__(FT) void td3_combine_kernel(const float *part, int nch, int P, float *out)
-{
-    const int e = blockIdx.x * FT + threadIdx.x;
-    if (e >= P) return;
-    float s = part[e];
-    for (int c = 1; c < nch; ++c) s += part[(size_t)c * P + e];
-    out[e] = s;
-}
 
 // ---- smoothing of the target action (in place, pitch 4): clamp(a' + clamp(noise, -clip, clip), lo, hi)
 __global__ __launch_bounds__(FT) void td3_smooth_kernel(float *a, const float *noise, int n, float clip, float lo, float hi)
@@ -297,9 +33,6 @@ __global__ __launch_bounds__(FT) void td3_smooth_kernel(float *a, const float *n
         a[(size_t)r * MW[NL - 1] + c] = fminf(fmaxf(a[(size_t)r * MW[NL - 1] + c] + z, lo), hi);
     }
 }
-
-// torch.min: NaN if either is NaN
-__device__ __forceinline__ float tmin(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : (a < b ? a : b); }
 
 // ---- critic head: y, the per-row squared errors and the critics' dZ6; block partials (fixed tree) to rowp[block * RP + i]
 struct CriticHead {
@@ -345,21 +78,6 @@ __global__ __launch_bounds__(FT) void td3_actor_head_kernel(const float *q, floa
     if (threadIdx.x == 0) rowp[(size_t)blockIdx.x * RP] = tot;
 }
 
-// thread t adds partials t, t + 256, ... in order, then the tree; total of row-term i in tot[i] (every thread)
-__device__ void reduce_rows(const float *rowp, int nblk, int nterms, float *tot, float *red)
-{
-    for (int i = 0; i < nterms; ++i) {
-        float s = 0.0f;
-        for (int b = threadIdx.x; b < nblk; b += FT) s += rowp[(size_t)b * RP + i];
-        tot[i] = block_sum(s, red);
-    }
-}
-__device__ void adam_scalars(int step, float beta1, float beta2, float lr, float *step_size, float *bc2_sqrt)
-{
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    *step_size = (float)((double)lr / bc1);
-    *bc2_sqrt = (float)sqrt(bc2);
-}
 __global__ __launch_bounds__(FT) void td3_critic_final_kernel(const float *rowp, int nblk, float inv_n, float beta1, float beta2, float lr,
                                                               rover_td3_state *st)
 {
@@ -389,102 +107,23 @@ __global__ __launch_bounds__(FT) void td3_actor_final_kernel(const float *rowp, 
     }
 }
 
-// ---- Adam (torch's single-tensor order) over P floats; sc = {step_size, bc2_sqrt} in the state; then the replicas
-__global__ __launch_bounds__(FT) void td3_adam_kernel(float *params, const float *grad, float *m, float *v, const float *sc, int P,
-                                                      float beta1, float beta2, float eps, float *rep, int n_copies)
-{
-    const int e = blockIdx.x * FT + threadIdx.x;
-    if (e >= P) return;
-    const float g = grad[e];
-    const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
-    const float mo = m[e], mn = mo + w1 * (g - mo);                     // exp_avg.lerp_(grad, 1 - beta1)
-    const float vn = v[e] * beta2 + w2 * (g * g);                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = sqrtf(vn) / sc[1] + eps;                        // (exp_avg_sq.sqrt() / sqrt(bc2)).add_(eps)
-    const float p = params[e] + (-sc[0]) * (mn / denom);                // param.addcdiv_(exp_avg, denom, -lr / bc1)
-    m[e] = mn;
-    v[e] = vn;
-    params[e] = p;
-    if (rep)
-        for (int c = 0; c < n_copies; ++c) rep[(size_t)c * P + e] = p;
-}
-
-// ---- Polyak: t.mul_(1 - tau); t.add_(tau * p) -- two fp32 roundings per product, one per sum (no contraction)
-__global__ __launch_bounds__(FT) void td3_polyak_kernel(float *t, const float *p, size_t count, float keep, float tau)
-{
-    const size_t e = (size_t)blockIdx.x * FT + threadIdx.x;
-    if (e >= count) return;
-    const float a = t[e] * keep;
-    const float b = p[e] * tau;
-    t[e] = a + b;
-}
-
 // ---- host side
-size_t layer_weight_floats(int N, int K) { return (size_t)cdiv(N, 16) * cdiv(K, 16) * 64 * 4; }
-size_t layer_bias_floats(int N) { return al4((size_t)N); }
-int out_of(int l, bool critic) { return l < NL - 1 ? LN[l] : (critic ? 1 : 2); }
-int in_of(int l, bool critic) { return critic ? CK[l] : AK[l]; }
-size_t net_floats(bool critic)
-{
-    size_t n = 0;
-    for (int l = 0; l < NL; ++l) n += layer_weight_floats(out_of(l, critic), in_of(l, critic)) + layer_bias_floats(out_of(l, critic));
-    return n;
-}
 size_t param_floats() { return (net_floats(false) + 2 * net_floats(true) + 63) & ~(size_t)63; }
 
-// the shapes (and, with `packed`, the offsets the pack sets) of the actor / critic
-bool is_net(const rover_policy_desc *d, bool critic, bool packed)
-{
-    if (!d) return false;
-    if (d->obs_dim != OBS || d->prop_dim != PROP || d->enc_offset != ENC_OFF || d->enc_dim != CK[0] || d->n_enc != 2 || d->n_mlp != 4)
-        return false;
-    if (d->leaky_slope != 0.01f) return false;
-    size_t off = 0;
-    for (int i = 0; i < NL; ++i) {
-        const rover_policy_layer &l = d->layers[i];
-        const int N = out_of(i, critic), K = in_of(i, critic);
-        if (l.K != K || l.N != N) return false;
-        if (l.act != (i < NL - 1 ? ROVER_ACT_LEAKY_RELU : ROVER_ACT_NONE)) return false;
-        if ((l.split_k != 0) != (i == 0 || i == NL - 1)) return false;
-        if (packed && l.w_off != off) return false;
-        off += layer_weight_floats(N, K);
-        if (packed && l.b_off != off) return false;
-        off += layer_bias_floats(N);
-    }
-    return true;
-}
 int check_nets(const rover_policy_desc *actor, const rover_policy_desc *critic)
 {
     if (!actor || !critic) return rover_internal_fail(ROVER_ERR_INVALID, "descriptor is NULL");
-    if (!is_net(actor, false, true) || !is_net(critic, true, true))
+    if (!is_net(actor, false, ROVER_ACT_NONE, true) || !is_net(critic, true, ROVER_ACT_NONE, true))
         return rover_internal_fail(ROVER_ERR_UNSUPPORTED, "the fused TD3 update runs the reference actor (rover_policy_default_desc(2, 0), "
                                                           "packed by rover_policy_pack) and the Q(s, a) critic (rover_td3_critic_desc, "
                                                           "packed by rover_td3_critic_pack) only");
     return ROVER_OK;
 }
 
-struct Net {
-    const float *p;                  // the network's packed block
-    uint32_t w_off[NL], b_off[NL];
-    bool critic;
-};
-Net net_at(const rover_policy_desc *d, const float *block, bool critic)
-{
-    Net n;
-    n.p = block;
-    for (int i = 0; i < NL; ++i) { n.w_off[i] = d->layers[i].w_off; n.b_off[i] = d->layers[i].b_off; }
-    n.critic = critic;
-    return n;
-}
-
 // workspace layout: per-row vectors (ro_s, ro_n as int64; a (2), r, nt, y as float), row partials, then 5 network regions
 // (cache + scratch, ROW_F floats per row each): 0 actor / target actor, 1 / 2 target critics, 3 / 4 critics; then the
 // weight-gradient chunk partials of both critics
-struct Region {
-    float *cache[NL], *scr[NL];
-};
 constexpr int NREG = 5;
-size_t rowp_floats(int rows) { return al4((size_t)RP * cdiv(rows, FT)); }
-size_t part_floats(int rows) { return (size_t)cdiv(rows, CH) * (2 * net_floats(true)); }
 size_t ws_bytes_for(int rows)
 {
     const size_t R = (size_t)rows;
@@ -520,105 +159,6 @@ Ws ws_at(void *ws, int rows)
     return w;
 }
 
-int device_of(const void *p, int *dev)
-{
-    hipPointerAttribute_t at;
-    hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_INVALID, "not a device pointer: %s", hipGetErrorString(e));
-    *dev = at.device;
-    return ROVER_OK;
-}
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, what, hipGetErrorString(e));
-    return ROVER_OK;
-}
-
-// the forward of up to MAXZ networks over `rows` rows; net z reads observation rows ro[z] and (critics) actions ain[z] (pitch 4
-// or 2) and writes its layer outputs to reg[z]->cache
-struct FwdJob {
-    Net net;
-    const int64_t *ro;
-    const float *ain; int aip;
-    Region *reg;
-};
-int forward(const FwdJob *jobs, int nz, const float *obs, int rows, hipStream_t s)
-{
-    for (int l = 0; l < NL; ++l) {
-        DenseLaunch L = {};
-        L.rows = rows;
-        L.slope = 0.01f;
-        int N = 0;
-        for (int z = 0; z < nz; ++z) {
-            const FwdJob &j = jobs[z];
-            Dense &A = L.d[z];
-            N = out_of(l, j.net.critic);
-            if (l == 0) { A.x = obs + ENC_OFF; A.xp = OBS; A.ro = j.ro; }
-            else { A.x = j.reg->cache[l - 1]; A.xp = MW[l - 1]; }
-            A.W = j.net.p + j.net.w_off[l]; A.b = j.net.p + j.net.b_off[l];
-            A.out = j.reg->cache[l]; A.op = MW[l]; A.ocol = l == 1 ? PROP : 0;
-            if (l == 1) {
-                A.prop = obs; A.pro = j.ro;
-                if (j.net.critic) { A.ain = j.ain; A.aip = j.aip; }
-            }
-            A.K = in_of(l, j.net.critic); A.N = N;
-            A.act = l < NL - 1 ? ACT_LEAKY_ : ACT_NONE_;
-        }
-        hipLaunchKernelGGL(td3_dense_kernel, dim3(cdiv(rows, 64), cdiv(N, 64), nz), dim3(FT), 0, s, L);
-        if (int rc = launched("td3_dense_kernel launch: %s")) return rc;
-    }
-    return ROVER_OK;
-}
-
-// reverse of layer l for nz networks at once: dZ_{l-1} = (dZ_l W_l) * LeakyReLU'(a_{l-1}) into scr[l - 1]
-int back_layer(const Net *nets, Region *const *regs, int nz, int l, int rows, hipStream_t s)
-{
-    BackLaunch L = {};
-    L.rows = rows;
-    L.slope = 0.01f;
-    int nk = 0;
-    for (int z = 0; z < nz; ++z) {
-        Back &B = L.d[z];
-        const Net &n = nets[z];
-        B.dz = l == 1 ? regs[z]->scr[1] + PROP : regs[z]->scr[l]; B.dzp = MW[l];
-        B.W = n.p + n.w_off[l]; B.K = in_of(l, n.critic); B.N = out_of(l, n.critic);
-        B.aref = regs[z]->cache[l - 1]; B.arp = MW[l - 1];
-        B.out = regs[z]->scr[l - 1]; B.op = MW[l - 1]; B.ocol = 0;
-        B.k0 = l == 2 ? PROP : 0; B.nk = l == 2 ? LN[1] : in_of(l, n.critic);
-        nk = B.nk;
-    }
-    hipLaunchKernelGGL(td3_back_kernel, dim3(cdiv(rows, 64), cdiv(nk, 64), nz), dim3(FT), 0, s, L);
-    return launched("td3_back_kernel launch: %s");
-}
-
-// weight gradients of nz networks whose packed blocks lie back to back (block_floats each) into out[0 .. nz * block_floats)
-int wgrad(const Net *nets, Region *const *regs, const int64_t *ro, int nz, const float *obs, int rows, float *part, float *out,
-          hipStream_t s)
-{
-    WgradArgs W = {};
-    const uint32_t bf = (uint32_t)net_floats(nets[0].critic);
-    W.jobs[0] = 0;
-    int j = 0;
-    for (int z = 0; z < nz; ++z)
-        for (int l = 0; l < NL; ++l, ++j) {
-            const Net &n = nets[z];
-            W.K[j] = in_of(l, n.critic); W.N[j] = out_of(l, n.critic);
-            if (l == 0) { W.am[j] = obs + ENC_OFF; W.ap[j] = OBS; W.ro[j] = ro; }
-            else { W.am[j] = regs[z]->cache[l - 1]; W.ap[j] = MW[l - 1]; W.ro[j] = nullptr; }
-            // dZ of layer 2 (the encoder's 60 outputs) sits at columns 4 .. 63 of its 68-wide matrix
-            W.dz[j] = l == 1 ? regs[z]->scr[1] + PROP : regs[z]->scr[l]; W.dzp[j] = MW[l];
-            W.w_off[j] = z * bf + n.w_off[l]; W.b_off[j] = z * bf + n.b_off[l];
-            W.jobs[j + 1] = W.jobs[j] + cdiv(W.N[j], 16) * (cdiv(W.K[j], 16) + 1);
-        }
-    W.nl = j; W.rows = rows; W.P = (int)(nz * bf); W.part = part;
-    const int nch = cdiv(rows, CH);
-    hipLaunchKernelGGL(td3_wgrad_kernel, dim3(cdiv(W.jobs[j], 4), nch), dim3(FT), 0, s, W);
-    if (int rc = launched("td3_wgrad_kernel launch: %s")) return rc;
-    hipLaunchKernelGGL(td3_combine_kernel, dim3(cdiv(W.P, FT)), dim3(FT), 0, s, (const float *)part, nch, W.P, out);
-    return launched("td3_combine_kernel launch: %s");
-}
-
 int common_checks(const rover_policy_desc *actor, const rover_policy_desc *critic, const rover_td3_hparams *h, const void *params,
                   const void *grad, const void *adam_m, const void *adam_v, const float *obs_ring, int32_t slots, int32_t num_envs,
                   const int32_t *ring_pos, const int64_t *idx, int32_t n, int64_t valid_rows, const void *ws, size_t ws_bytes,
@@ -637,17 +177,6 @@ int common_checks(const rover_policy_desc *actor, const rover_policy_desc *criti
         return rover_internal_fail(ROVER_ERR_INVALID, "workspace and parameter vectors must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(state) & 7) return rover_internal_fail(ROVER_ERR_INVALID, "state must be 8-byte aligned");
     return ROVER_OK;
-}
-
-int gather(const Ws &w, const int64_t *idx, int n, int64_t valid, int num_envs, int slots, const int32_t *pos, const float *act,
-           const float *rew, const uint8_t *term, rover_td3_state *st, hipStream_t s)
-{
-    GatherArgs G = {};
-    G.idx = idx; G.n = n; G.valid = valid; G.num_envs = num_envs; G.slots = slots; G.pos = pos;
-    G.act = act; G.rew = rew; G.term = term;
-    G.ro_s = w.ro_s; G.ro_n = w.ro_n; G.a = w.a; G.r = w.r; G.nt = w.nt; G.st = st;
-    hipLaunchKernelGGL(td3_gather_kernel, dim3(cdiv(n, FT)), dim3(FT), 0, s, G);
-    return launched("td3_gather_kernel launch: %s");
 }
 
 }  // namespace
@@ -685,7 +214,8 @@ int rover_td3_critic_desc(rover_policy_desc *d)
 int rover_td3_critic_pack(rover_policy_desc *d, const float *const *weights, const float *const *biases, float *packed)
 {
     if (!d || !weights || !biases || !packed) return rover_internal_fail(ROVER_ERR_INVALID, "NULL argument");
-    if (!is_net(d, true, false)) return rover_internal_fail(ROVER_ERR_UNSUPPORTED, "not the TD3 critic layout (rover_td3_critic_desc)");
+    if (!is_net(d, true, ROVER_ACT_NONE, false))
+        return rover_internal_fail(ROVER_ERR_UNSUPPORTED, "not the TD3 critic layout (rover_td3_critic_desc)");
     size_t off = 0;
     for (int li = 0; li < NL; ++li) {
         rover_policy_layer &l = d->layers[li];
@@ -710,7 +240,7 @@ int rover_td3_critic_pack(rover_policy_desc *d, const float *const *weights, con
 
 size_t rover_td3_param_floats(const rover_policy_desc *actor, const rover_policy_desc *critic)
 {
-    if (!is_net(actor, false, true) || !is_net(critic, true, true)) return 0;
+    if (!is_net(actor, false, ROVER_ACT_NONE, true) || !is_net(critic, true, ROVER_ACT_NONE, true)) return 0;
     return param_floats();
 }
 size_t rover_td3_workspace_bytes(int32_t max_rows) { return max_rows > 0 ? ws_bytes_for(max_rows) : 0; }
@@ -739,7 +269,7 @@ int rover_td3_critic_step(const rover_policy_desc *actor, const rover_policy_des
     if (int rc = gather(w, idx, n, valid_rows, num_envs, slots, ring_pos, act, rew, terminated, st, s)) return rc;
     // a' = target_policy(s') [smoothed]
     FwdJob ja = {tpi, w.ro_n, nullptr, 0, &w.reg[0]};
-    if (int rc = forward(&ja, 1, obs_ring, n, s)) return rc;
+    if (int rc = forward<State>(&ja, 1, obs_ring, n, s)) return rc;
     float *a_next = w.reg[0].cache[NL - 1];
     if (noise) {
         hipLaunchKernelGGL(td3_smooth_kernel, dim3(cdiv(n, FT)), dim3(FT), 0, s, a_next, noise, n, h->noise_clip, h->act_min, h->act_max);
@@ -748,7 +278,7 @@ int rover_td3_critic_step(const rover_policy_desc *actor, const rover_policy_des
     // target critics on (s', a') and critics on (s, a) in the same launches
     FwdJob jc[4] = {{tq1, w.ro_n, a_next, MW[NL - 1], &w.reg[1]}, {tq2, w.ro_n, a_next, MW[NL - 1], &w.reg[2]},
                     {q1, w.ro_s, w.a, 2, &w.reg[3]}, {q2, w.ro_s, w.a, 2, &w.reg[4]}};
-    if (int rc = forward(jc, 4, obs_ring, n, s)) return rc;
+    if (int rc = forward<State>(jc, 4, obs_ring, n, s)) return rc;
     CriticHead H = {};
     H.tq1 = w.reg[1].cache[NL - 1]; H.tq2 = w.reg[2].cache[NL - 1]; H.q1 = w.reg[3].cache[NL - 1]; H.q2 = w.reg[4].cache[NL - 1];
     H.r = w.r; H.nt = w.nt; H.gamma = h->gamma; H.inv_n = 1.0f / (float)n;
@@ -762,11 +292,12 @@ int rover_td3_critic_step(const rover_policy_desc *actor, const rover_policy_des
     const Net qs[2] = {q1, q2};
     Region *regs[2] = {&w.reg[3], &w.reg[4]};
     for (int l = NL - 1; l >= 1; --l)
-        if (int rc = back_layer(qs, regs, 2, l, n, s)) return rc;
-    if (int rc = wgrad(qs, regs, w.ro_s, 2, obs_ring, n, w.part, grad + Pa, s)) return rc;
-    hipLaunchKernelGGL(td3_adam_kernel, dim3(cdiv((int)(2 * Pc), FT)), dim3(FT), 0, s, params + Pa, (const float *)grad + Pa, adam_m + Pa,
-                       adam_v + Pa, (const float *)&st->critic_step_size, (int)(2 * Pc), h->beta1, h->beta2, h->eps, (float *)nullptr, 0);
-    return launched("td3_adam_kernel launch: %s");
+        if (int rc = back_layer<State>(qs, regs, 2, l, n, s)) return rc;
+    if (int rc = wgrad<State>(qs, regs, w.ro_s, 2, obs_ring, n, w.part, grad + Pa, s)) return rc;
+    hipLaunchKernelGGL(offpolicy_adam_kernel<State>, dim3(cdiv((int)(2 * Pc), FT)), dim3(FT), 0, s, params + Pa, (const float *)grad + Pa,
+                       adam_m + Pa, adam_v + Pa, (const float *)&st->critic_step_size, (int)(2 * Pc), h->beta1, h->beta2, h->eps,
+                       (float *)nullptr, 0);
+    return launched("offpolicy_adam_kernel launch: %s");
 }
 
 int rover_td3_actor_step(const rover_policy_desc *actor, const rover_policy_desc *critic, const rover_td3_hparams *h,
@@ -790,9 +321,9 @@ int rover_td3_actor_step(const rover_policy_desc *actor, const rover_policy_desc
     Region &RA = w.reg[0], &RQ = w.reg[3];
     if (int rc = gather(w, idx, n, valid_rows, num_envs, slots, ring_pos, nullptr, nullptr, nullptr, st, s)) return rc;
     FwdJob ja = {pi, w.ro_s, nullptr, 0, &RA};
-    if (int rc = forward(&ja, 1, obs_ring, n, s)) return rc;
+    if (int rc = forward<State>(&ja, 1, obs_ring, n, s)) return rc;
     FwdJob jq = {q1, w.ro_s, RA.cache[NL - 1], MW[NL - 1], &RQ};
-    if (int rc = forward(&jq, 1, obs_ring, n, s)) return rc;
+    if (int rc = forward<State>(&jq, 1, obs_ring, n, s)) return rc;
     const float inv_n = 1.0f / (float)n;
     hipLaunchKernelGGL(td3_actor_head_kernel, dim3(cdiv(n, FT)), dim3(FT), 0, s, (const float *)RQ.cache[NL - 1], RQ.scr[NL - 1], inv_n, n,
                        w.rowp);
@@ -802,7 +333,7 @@ int rover_td3_actor_step(const rover_policy_desc *actor, const rover_policy_desc
     // critic_1's MLP backward down to its input M, then only the two action columns: dL/da into the actor's dZ6
     Region *rq[1] = {&RQ};
     for (int l = NL - 1; l >= 3; --l)
-        if (int rc = back_layer(&q1, rq, 1, l, n, s)) return rc;
+        if (int rc = back_layer<State>(&q1, rq, 1, l, n, s)) return rc;
     {
         BackLaunch L = {};
         L.rows = n; L.slope = 0.01f;
@@ -812,8 +343,8 @@ int rover_td3_actor_step(const rover_policy_desc *actor, const rover_policy_desc
         B.aref = nullptr; B.arp = 0;
         B.out = RA.scr[NL - 1]; B.op = MW[NL - 1]; B.ocol = ACOL;
         B.k0 = ACOL; B.nk = 2;
-        hipLaunchKernelGGL(td3_back_kernel, dim3(cdiv(n, 64), 1, 1), dim3(FT), 0, s, L);
-        if (int rc = launched("td3_back_kernel launch: %s")) return rc;
+        hipLaunchKernelGGL(offpolicy_back_kernel<State>, dim3(cdiv(n, 64), 1, 1), dim3(FT), 0, s, L);
+        if (int rc = launched("offpolicy_back_kernel launch: %s")) return rc;
     }
     if (dact_out) {
         hipError_t e = hipMemcpy2DAsync(dact_out, 2 * sizeof(float), RA.scr[NL - 1], MW[NL - 1] * sizeof(float), 2 * sizeof(float), n,
@@ -822,11 +353,11 @@ int rover_td3_actor_step(const rover_policy_desc *actor, const rover_policy_desc
     }
     Region *ra[1] = {&RA};
     for (int l = NL - 1; l >= 1; --l)
-        if (int rc = back_layer(&pi, ra, 1, l, n, s)) return rc;
-    if (int rc = wgrad(&pi, ra, w.ro_s, 1, obs_ring, n, w.part, grad, s)) return rc;
-    hipLaunchKernelGGL(td3_adam_kernel, dim3(cdiv((int)Pa, FT)), dim3(FT), 0, s, params, (const float *)grad, adam_m, adam_v,
+        if (int rc = back_layer<State>(&pi, ra, 1, l, n, s)) return rc;
+    if (int rc = wgrad<State>(&pi, ra, w.ro_s, 1, obs_ring, n, w.part, grad, s)) return rc;
+    hipLaunchKernelGGL(offpolicy_adam_kernel<State>, dim3(cdiv((int)Pa, FT)), dim3(FT), 0, s, params, (const float *)grad, adam_m, adam_v,
                        (const float *)&st->actor_step_size, (int)Pa, h->beta1, h->beta2, h->eps, replicas_actor, (int)n_copies);
-    return launched("td3_adam_kernel launch: %s");
+    return launched("offpolicy_adam_kernel launch: %s");
 }
 
 int rover_td3_polyak(const rover_td3_hparams *h, float *target, const float *params, size_t count, void *stream)
@@ -837,9 +368,9 @@ int rover_td3_polyak(const rover_td3_hparams *h, float *target, const float *par
     if (int rc = device_of(target, &dev)) return rc;
     DeviceGuard guard(dev);
     const float keep = (float)(1.0 - (double)h->polyak);
-    hipLaunchKernelGGL(td3_polyak_kernel, dim3((unsigned)((count + FT - 1) / FT)), dim3(FT), 0, static_cast<hipStream_t>(stream), target,
-                       params, count, keep, h->polyak);
-    return launched("td3_polyak_kernel launch: %s");
+    hipLaunchKernelGGL(offpolicy_polyak_kernel<State>, dim3((unsigned)((count + FT - 1) / FT)), dim3(FT), 0,
+                       static_cast<hipStream_t>(stream), target, params, count, keep, h->polyak);
+    return launched("offpolicy_polyak_kernel launch: %s");
 }
 
 }  // extern "C"
