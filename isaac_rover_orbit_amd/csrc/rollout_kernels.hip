@@ -48,15 +48,6 @@ __device__ __forceinline__ float activate(float v, int act, float slope)
     return v;
 }
 
-// torch.nan_to_num(x, nan = 0, posinf = FLT_MAX, neginf = 0): finite values (and -0) pass unchanged
-__device__ __forceinline__ float sanitise(float x)
-{
-    if (x != x) return 0.0f;
-    if (x == INFINITY) return FLT_MAX;
-    if (x == -INFINITY) return 0.0f;
-    return x;
-}
-
 struct RolLaunch {
     int n_copies;              // replicas of the packed buffers; workgroup b reads replica b % n_copies
     unsigned copy_floats_a, copy_floats_b;

@@ -20,6 +20,7 @@
 #include "../../include/rover_hip.h"
 #include "../../include/rover_scaler.h"
 #include "rover_internal.hpp"
+#include "train_math.hpp"   // sanitise
 
 namespace {
 
@@ -90,14 +91,6 @@ __global__ __launch_bounds__(MAX_W) void scaler_merge_kernel(double *scaler, int
 }
 
 // ---- transform
-// torch.nan_to_num(x, nan = 0, posinf = FLT_MAX, neginf = 0), the text of rollout_kernels.hip
-__device__ __forceinline__ float sanitise(float x)
-{
-    if (x != x) return 0.0f;
-    if (x == INFINITY) return FLT_MAX;
-    if (x == -INFINITY) return 0.0f;
-    return x;
-}
 __device__ __forceinline__ float clampf_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }   // NaN passes
 
 struct ApplyArgs {

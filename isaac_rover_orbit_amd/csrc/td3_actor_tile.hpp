@@ -1,5 +1,6 @@
 // td3_actor_tile.hpp -- the TD3 actor's forward on one 16-row tile as a device function, shared by the kernels that run the actor in
-// front of an exploration epilogue (td3_collect_kernels.hip, td3_explore_kernels.hip), and the exploration noise draw they share.
+// front of an exploration epilogue (td3_collect_kernels.hip, td3_explore_kernels.hip, sac_collect_kernels.hip), the exploration noise
+// draw they share and the check of the actor's shapes.
 //
 // The network part is the single-network kernel's (policy_kernels.hip, ref_network<true>): the same tile, the same per-wave tile
 // assignment, the same k-ordered MFMA chains and the same split-K combine order, so the mean is bit-identical to
@@ -327,11 +328,9 @@ __device__ __forceinline__ float td3_noise_eps(uint32_t g, uint32_t ctr_lo, uint
 {
     uint32_t w4[4];
     philox4x32(g, ctr_lo, ctr_hi, tag | (uint32_t)(c >> 1), seed_lo, seed_hi, w4);
-    const float u1 = ((float)(w4[0] >> 9) + 0.5f) * 0x1p-23f, u2 = ((float)(w4[1] >> 9) + 0.5f) * 0x1p-23f;   // exact, inside (0, 1)
-    const float rho = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincospif(2.0f * u2, &sn, &cs);             // the angle 2 pi u2 with an exact argument
-    return (c & 1) ? rho * sn : rho * cs;
+    float e0, e1;
+    box_muller(w4[0], w4[1], e0, e1);
+    return (c & 1) ? e1 : e0;
 }
 
 // mean + (noise * scale), clamped as torch.clamp: two fp32 operations, then a NaN sum stays NaN (fmaxf alone would make it `low`)
@@ -343,8 +342,8 @@ __device__ __forceinline__ float td3_add_noise_clamp(float mean, float noise, fl
     return a != a ? a : cl;
 }
 
-// the shapes the act kernel is written for (rover_policy_default_desc), with no final activation
-inline bool is_reference_actor(const rover_policy_desc *d)
+// the shapes the act kernels are written for (rover_policy_default_desc) with 1 .. 16 outputs under `final_act`
+inline bool is_reference_actor(const rover_policy_desc *d, int final_act)
 {
     if (d->obs_dim != OBS || d->prop_dim != PROP || d->enc_offset != ENC_OFF || d->enc_dim != 961 || d->n_enc != 2 || d->n_mlp != 4) return false;
     const int K[6] = {961, 80, 64, 256, 160, 128}, N[5] = {80, 60, 256, 160, 128};
@@ -353,7 +352,7 @@ inline bool is_reference_actor(const rover_policy_desc *d)
         if (i < 5 && (d->layers[i].N != N[i] || d->layers[i].act != ROVER_ACT_LEAKY_RELU)) return false;
         if ((d->layers[i].split_k != 0) != (i == 0 || i == 5)) return false;
     }
-    return d->layers[5].N >= 1 && d->layers[5].N <= 16 && d->layers[5].act == ROVER_ACT_NONE;
+    return d->layers[5].N >= 1 && d->layers[5].N <= 16 && d->layers[5].act == final_act;
 }
 
 }  // namespace

@@ -6,6 +6,7 @@
 //                                    and the branches on it are wave-uniform.
 //   rover_td3_explore_random_kernel  RANDOM: one lane per action value, no LDS, no actor
 //   rover_td3_smooth_draw_kernel     one lane per (batch position, action pair)
+// The act entry point's common checks and its launch are offpolicy_collect.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,12 +15,11 @@
 
 #include "../../include/rover_hip.h"
 #include "../../include/rover_td3_explore.h"
+#include "offpolicy_collect.hpp"
 #include "rover_internal.hpp"
 #include "td3_actor_tile.hpp"
 
 namespace {
-
-constexpr int FLAT_THREADS = 256;   // the two draw kernels
 
 struct TdxLaunch {
     int n_copies;              // replicas of the packed buffer; workgroup b reads replica b % n_copies
@@ -79,8 +79,7 @@ __global__ __launch_bounds__(FLAT_THREADS) void rover_td3_explore_random_kernel(
     const unsigned row = e / A, c = e - row * A;
     uint32_t w4[4];
     philox4x32(R.id0 + row, R.ctr_lo, R.ctr_hi, ROVER_TD3_TAG_RANDOM | (c >> 2), R.seed_lo, R.seed_hi, w4);
-    const uint32_t w = (c & 2) ? ((c & 1) ? w4[3] : w4[2]) : ((c & 1) ? w4[1] : w4[0]);   // selects, not a private array
-    const float u = ((float)(w >> 9) + 0.5f) * 0x1p-23f;   // exact, inside (0, 1)
+    const float u = unit_uniform((c & 2) ? ((c & 1) ? w4[3] : w4[2]) : ((c & 1) ? w4[1] : w4[0]));   // selects, not a private array
     const float t = R.range * u;
     const float a = R.low + t;
     R.act_out[e] = a;
@@ -96,12 +95,12 @@ __global__ __launch_bounds__(FLAT_THREADS) void rover_td3_smooth_draw_kernel(uin
     const unsigned i = e / pairs, p = e - i * pairs;
     uint32_t w4[4];
     philox4x32(i, ctr_lo, ctr_hi, ROVER_TD3_TAG_SMOOTH | p, seed_lo, seed_hi, w4);
-    const float u1 = ((float)(w4[0] >> 9) + 0.5f) * 0x1p-23f, u2 = ((float)(w4[1] >> 9) + 0.5f) * 0x1p-23f;   // exact, inside (0, 1)
-    const float rho = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincospif(2.0f * u2, &sn, &cs);
-    out[2 * (size_t)e] = std * (rho * cs);
-    out[2 * (size_t)e + 1] = std * (rho * sn);
+    float e0, e1;
+    // normal_pair's two lines (offpolicy_collect.hpp) written out, not called: through one more inlined function the compiler
+    // commutes the operands of six v_xor of the Philox rounds, and this kernel's instruction stream is kept as it was
+    box_muller(w4[0], w4[1], e0, e1);
+    out[2 * (size_t)e] = std * e0;
+    out[2 * (size_t)e + 1] = std * e1;
 }
 
 }  // namespace
@@ -127,24 +126,20 @@ int rover_td3_explore_act(const rover_policy_desc *actor, const float *packed, i
                           uint64_t counter, const float *obs, int32_t n, float *ou_state, float *mean_out, float *act_out,
                           float *env_act_out, float *eps_out, void *stream)
 {
-    if (!actor || !h) return rover_internal_fail(ROVER_ERR_INVALID, "rover_td3_explore_act: NULL descriptor / hparams");
-    if (!packed || !obs || !act_out || !env_act_out) return rover_internal_fail(ROVER_ERR_INVALID, "rover_td3_explore_act: NULL required pointer");
-    if (n < 1 || n_copies < 1) return rover_internal_fail(ROVER_ERR_INVALID, "rover_td3_explore_act: n and n_copies must be >= 1");
-    if (reinterpret_cast<uintptr_t>(packed) & 15) return rover_internal_fail(ROVER_ERR_INVALID, "packed weights must be 16-byte aligned");
+    if (int rc = collect_act_check("rover_td3_explore_act", actor, h, packed, obs, act_out, env_act_out, n, n_copies)) return rc;
     const int mode = h->mode;
     if (mode != ROVER_TD3_EXPLORE_OFF && mode != ROVER_TD3_EXPLORE_GAUSSIAN && mode != ROVER_TD3_EXPLORE_OU && mode != ROVER_TD3_EXPLORE_RANDOM)
         return rover_internal_fail(ROVER_ERR_INVALID, "rover_td3_explore_act: unknown mode");
     if (mode != ROVER_TD3_EXPLORE_OFF && !(h->action_low <= h->action_high))
         return rover_internal_fail(ROVER_ERR_INVALID, "rover_td3_explore_act: action_low > action_high");
     if (mode == ROVER_TD3_EXPLORE_OU && !ou_state) return rover_internal_fail(ROVER_ERR_INVALID, "rover_td3_explore_act: OU needs ou_state");
-    if (!is_reference_actor(actor))
+    if (!is_reference_actor(actor, ROVER_ACT_NONE))
         return rover_internal_fail(ROVER_ERR_UNSUPPORTED, "rover_td3_explore_act: the actor must have the reference architecture with no "
                                                           "final activation");
-    const uint32_t ctr_lo = (uint32_t)(counter & 0xFFFFFFFFu), ctr_hi = (uint32_t)(counter >> 32);
-    hipError_t e;
     if (mode == ROVER_TD3_EXPLORE_RANDOM) {
         RandomLaunch R;
-        R.seed_lo = h->seed_lo; R.seed_hi = h->seed_hi; R.ctr_lo = ctr_lo; R.ctr_hi = ctr_hi;
+        R.seed_lo = h->seed_lo; R.seed_hi = h->seed_hi;
+        R.ctr_lo = (uint32_t)(counter & 0xFFFFFFFFu); R.ctr_hi = (uint32_t)(counter >> 32);
         R.id0 = (uint32_t)h->env_id_offset;
         R.low = h->action_low; R.range = h->action_high - h->action_low;
         R.act_out = act_out; R.env_act_out = env_act_out;
@@ -153,25 +148,15 @@ int rover_td3_explore_act(const rover_policy_desc *actor, const float *packed, i
         const unsigned total = (unsigned)n * A;
         hipLaunchKernelGGL(rover_td3_explore_random_kernel, dim3((total + FLAT_THREADS - 1) / FLAT_THREADS), dim3(FLAT_THREADS), 0,
                            static_cast<hipStream_t>(stream), R, total, A);
-        e = hipGetLastError();
+        hipError_t e = hipGetLastError();
         if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, "rover_td3_explore_random_kernel launch: %s", hipGetErrorString(e));
         return ROVER_OK;
     }
     TdxLaunch L;
-    L.n_copies = n_copies;
-    L.copy_floats = (unsigned)rover_policy_packed_floats(actor);
     L.hp = *h;
-    L.ctr_lo = ctr_lo; L.ctr_hi = ctr_hi;
     L.ou_state = mode == ROVER_TD3_EXPLORE_OU ? ou_state : nullptr;
     L.mean_out = mean_out; L.act_out = act_out; L.env_act_out = env_act_out; L.eps_out = eps_out;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(rover_td3_explore_act_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)LDS_BYTES);
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(rover_td3_explore_act_kernel, dim3(ceil_div(n, TDC_ROWS)), dim3(TDC_THREADS), LDS_BYTES,
-                       static_cast<hipStream_t>(stream), *actor, L, packed, obs, n);
-    e = hipGetLastError();
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, "rover_td3_explore_act_kernel launch: %s", hipGetErrorString(e));
-    return ROVER_OK;
+    return collect_act_launch("rover_td3_explore_act", rover_td3_explore_act_kernel, actor, L, packed, n_copies, counter, obs, n, stream);
 }
 
 int rover_td3_smooth_draw(uint32_t seed_lo, uint32_t seed_hi, uint64_t counter, float std, float *noise_out, int32_t n, int32_t A,

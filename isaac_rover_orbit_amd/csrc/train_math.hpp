@@ -1,5 +1,5 @@
 // train_math.hpp -- the scalar device math the trainers and collectors share (gfx950 / CDNA4): the Cephes expf / tanhf sequences,
-// torch's NaN-keeping clamp and min, the two activations and Philox4x32-10.
+// torch's NaN-keeping clamp and min, its nan_to_num of the observation rows, the two activations and Philox4x32-10.
 //
 // A collector and the update that recomputes its numbers are bit-exact only while both run the same fp32 sequence; they now
 // include this one text.  Everything here is force-inlined, so a kernel compiles to what it was with the text in place.
@@ -11,6 +11,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 
@@ -58,6 +59,15 @@ __device__ __forceinline__ float tclamp(float x, float lo, float hi) { return x 
 // torch.min: NaN if either is NaN
 __device__ __forceinline__ float tmin(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : (a < b ? a : b); }
 
+// torch.nan_to_num(x, nan = 0, posinf = FLT_MAX, neginf = 0): finite values (and -0) pass unchanged
+__device__ __forceinline__ float sanitise(float x)
+{
+    if (x != x) return 0.0f;
+    if (x == INFINITY) return FLT_MAX;
+    if (x == -INFINITY) return 0.0f;
+    return x;
+}
+
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.0f ? v : v * slope; }
 // ELU exactly as policy_kernels.hip's activate(): rover_policy.h fixes expm1f
 __device__ __forceinline__ float elu(float v) { return v > 0.0f ? v : expm1f(v); }
@@ -76,6 +86,19 @@ __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2
         k1 += 0xBB67AE85u;
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// a Philox word as a uniform inside (0, 1): ((w >> 9) + 0.5) * 2^-23, exact in fp32
+__device__ __forceinline__ float unit_uniform(uint32_t w) { return ((float)(w >> 9) + 0.5f) * 0x1p-23f; }
+// the standard normal pair of two Philox words (the Box-Muller form and sincospif of rover_rollout.h): the angle 2 pi u2 with an
+// exact argument, e0 on the cosine and e1 on the sine
+__device__ __forceinline__ void box_muller(uint32_t w0, uint32_t w1, float &e0, float &e1)
+{
+    const float u1 = unit_uniform(w0), u2 = unit_uniform(w1);
+    const float rho = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincospif(2.0f * u2, &sn, &cs);
+    e0 = rho * cs;
+    e1 = rho * sn;
 }
 
 }  // namespace

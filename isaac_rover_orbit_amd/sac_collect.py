@@ -33,8 +33,8 @@ import torch
 
 from . import _lib
 from .rollout import _MASK, philox4x32, standard_normals, unit_uniform
-from .td3 import ACT_DIM, OBS_DIM, ReplayMemory
-from .td3_collect import TorchTD3Collector, _CollectorBase, _f32_cuda
+from .td3 import ACT_DIM, ReplayMemory
+from .td3_collect import TorchTD3Collector, _f32_cuda, _FusedCollector, _launch, _launch_act, _ptr
 from .td3_explore import SAC_ACTION_TAG as ACTION_TAG  # "SAC\0": word 3 of the Philox counter of the action draws, | action pair
 from .td3_explore import SAC_RANDOM_TAG as RANDOM_TAG  # "SAR\0": ... of the random steps' uniforms, | action quad
 from .td3_explore import smooth_normals
@@ -195,25 +195,12 @@ def collect_act(actor, log_std, rows: torch.Tensor, counter: int, hp: "_lib.SacC
                 env_act_out: torch.Tensor, *, mean_out=None, eps_out=None, logp_out=None, sigma_out=None) -> None:
     """One ``rover_sac_collect_act`` launch on the current stream over the already-sanitised ``rows`` (n, 965); ``log_std`` (RANDOM and
     MEAN do not read it) and the outputs left ``None`` are passed as NULL."""
-    wide = (("act_out", act_out), ("env_act_out", env_act_out), ("mean_out", mean_out), ("eps_out", eps_out))
-    for name, t in (("rows", rows), ("log_std", log_std), ("logp_out", logp_out), ("sigma_out", sigma_out)) + wide:
-        _f32_cuda(name, t, actor.packed.device)
     n = int(rows.shape[0])
-    if rows.dim() != 2 or rows.shape[1] != OBS_DIM:
-        raise ValueError(f"rows must have shape (n, {OBS_DIM})")
-    for name, t in wide:
-        if t is not None and t.numel() != n * ACT_DIM:
-            raise ValueError(f"{name} must hold ({n}, {ACT_DIM}) values")
-    for name, t, numel in (("log_std", log_std, ACT_DIM), ("logp_out", logp_out, n), ("sigma_out", sigma_out, ACT_DIM)):
-        if t is not None and t.numel() != numel:
-            raise ValueError(f"{name} must hold {numel} values")
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    stream = C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
-    with torch.cuda.device(rows.device):
-        _lib.check(_lib.load().rover_sac_collect_act(C.byref(actor.desc), actor.packed.data_ptr(), actor.n_copies, ptr(log_std),
-                                                     C.byref(hp), C.c_uint64(int(counter)), rows.data_ptr(), n, ptr(mean_out),
-                                                     act_out.data_ptr(), env_act_out.data_ptr(), ptr(eps_out), ptr(logp_out),
-                                                     ptr(sigma_out), stream), "rover_sac_collect_act")
+    wide = (("act_out", act_out), ("env_act_out", env_act_out), ("mean_out", mean_out), ("eps_out", eps_out))
+    narrow = (("log_std", log_std, ACT_DIM), ("logp_out", logp_out, n), ("sigma_out", sigma_out, ACT_DIM))
+    _launch_act("rover_sac_collect_act", actor, rows, ACT_DIM, wide, narrow, C.byref(actor.desc), actor.packed.data_ptr(),
+                actor.n_copies, _ptr(log_std), C.byref(hp), C.c_uint64(int(counter)), rows.data_ptr(), n, _ptr(mean_out),
+                act_out.data_ptr(), env_act_out.data_ptr(), _ptr(eps_out), _ptr(logp_out), _ptr(sigma_out))
 
 
 def collect_record(raw: torch.Tensor, ring_slot: torch.Tensor, hp: "_lib.SacCollectHparams", counter: int = 0, *, rew=None,
@@ -231,52 +218,41 @@ def collect_record(raw: torch.Tensor, ring_slot: torch.Tensor, hp: "_lib.SacColl
         if idx_out is not None and int(eps_out.shape[0]) != batch:
             raise ValueError("idx_out and eps_out must hold the same batch")
         batch = int(eps_out.shape[0])
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    stream = C.c_void_p(torch.cuda.current_stream(raw.device).cuda_stream)
-    with torch.cuda.device(raw.device):
-        _lib.check(_lib.load().rover_sac_collect_record(raw.data_ptr(), n, ring_slot.data_ptr(), ptr(rew), ptr(terminated), ptr(rew_out),
-                                                        ptr(term_out), ptr(ring_pos_entry), int(ring_pos_value), ptr(idx_out), batch,
-                                                        int(mem_rows), ptr(eps_out), C.byref(hp), C.c_uint64(int(counter)), stream),
-                   "rover_sac_collect_record")
+    _launch("rover_sac_collect_record", raw.device, raw.data_ptr(), n, ring_slot.data_ptr(), _ptr(rew), _ptr(terminated), _ptr(rew_out),
+            _ptr(term_out), _ptr(ring_pos_entry), int(ring_pos_value), _ptr(idx_out), batch, int(mem_rows), _ptr(eps_out), C.byref(hp),
+            C.c_uint64(int(counter)))
 
 
-class SACCollector(_SacModeMixin, _CollectorBase):
+class SACCollector(_SacModeMixin, _FusedCollector):
     """The fused collector: ``actor`` is a tanh ``RoverNet`` (reference architecture, two outputs), ``log_std`` a float32 cuda tensor
     of 2 floats and ``memory`` a ``ReplayMemory`` on the same device, all held BY REFERENCE -- with ``FusedSAC.actor`` and
     ``FusedSAC.log_std`` the collector always sees the trainer's current parameters.  ``act`` returns a buffer the next call
-    overwrites, ``record`` likewise (one index / draw buffer pair per batch size).
+    overwrites, ``record`` likewise (one index / draw buffer pair per batch size): ``begin`` and ``record`` are the fused base
+    class's, ``record`` returning ``(idx, eps)``.
     """
+
+    _NAME = "SACCollector"
+    _DRAWS = True
 
     def __init__(self, actor, log_std: torch.Tensor, memory: ReplayMemory, seed: int = 42, env_id_offset: int = 0,
                  random_timesteps: int = 0):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("SACCollector needs a ROCm GPU (no CPU fallback; TorchSACCollector is the CPU specification)")
         super().__init__(memory, seed, env_id_offset, 0.0, (-1.0, 1.0))
         self._init_sac(random_timesteps)
-        self._lib = _lib.load()
-        self.actor, self.log_std = actor, log_std
-        if memory.obs.device != actor.packed.device:
-            raise ValueError("the memory must live on the actor's device")
+        self._bind(actor)
+        self.log_std = log_std
         if actor.out_dim != ACT_DIM:
             raise ValueError("the actor must have 2 outputs")
         _f32_cuda("log_std", log_std, actor.packed.device)
         if log_std.numel() != ACT_DIM:
             raise ValueError("log_std must hold 2 floats")
-        self._env_act = torch.zeros(self.n, ACT_DIM, dtype=torch.float32, device=memory.obs.device)
-        self._batches: dict = {}
 
     def hparams(self, mode: int = SAMPLE) -> "_lib.SacCollectHparams":
-        hp = default_hparams()
-        hp.seed_lo, hp.seed_hi = self.seed & _MASK, (self.seed >> 32) & _MASK
-        hp.env_id_offset, hp.mode = self.env_id_offset, int(mode)
+        hp = self._seeded(default_hparams())
+        hp.mode = int(mode)
         return hp
 
-    @torch.no_grad()
-    def begin(self, raw_obs) -> None:
-        """The rows after a reset go, sanitised, into the ring's cursor slot.  No draw: the counter stays."""
-        m = self.memory
-        collect_record(self._raw(raw_obs), m.obs[m.cursor], self.hparams())
-        m._last_next, m._last_version = None, -1
+    def _record(self, raw, ring_slot, counter=0, idx=None, eps=None, **transition) -> None:
+        collect_record(raw, ring_slot, self.hparams(), counter, idx_out=idx, eps_out=eps, **transition)
 
     @torch.no_grad()
     def act(self, timestep: int, deterministic: bool = False, mean_out=None, eps_out=None, logp_out=None,
@@ -289,31 +265,3 @@ class SACCollector(_SacModeMixin, _CollectorBase):
                     sigma_out=sigma_out)
         self.counter += 1
         return self._env_act
-
-    @torch.no_grad()
-    def record(self, raw_obs, rew: torch.Tensor, terminated: torch.Tensor, batch_size: int | None = None):
-        """The transition of the step just taken: the env's rows, sanitised, into the next ring slot, reward / terminated / ring_pos of
-        memory slot k; with ``batch_size`` returns ``(idx, eps)``, the int64 row indices of a batch over the memory INCLUDING this
-        transition and the update's float32 draws (batch_size, 4); else ``None``.  Advances the memory as ``ReplayMemory.add`` does,
-        and the counter by one."""
-        m = self.memory
-        raw = self._raw(raw_obs)
-        self._transition(rew, terminated)
-        if not rew.is_cuda:
-            raise ValueError("rew and terminated must be cuda tensors")
-        batch_size = self._batch(batch_size)
-        k, w = m.memory_index, m.cursor
-        self._advance()
-        idx = eps = None
-        if batch_size is not None:
-            pair = self._batches.get(batch_size)
-            if pair is None:
-                pair = self._batches[batch_size] = (torch.zeros(batch_size, dtype=torch.int64, device=m.obs.device),
-                                                    torch.zeros(batch_size, 4, dtype=torch.float32, device=m.obs.device))
-            idx, eps = pair
-        collect_record(raw, m.obs[(w + 1) % m.slots], self.hparams(), self.counter, rew=rew, terminated=terminated,
-                       rew_out=m.rewards[k], term_out=m.terminated[k], ring_pos_entry=m.ring_pos[k:k + 1], ring_pos_value=w,
-                       idx_out=idx, mem_rows=len(m), eps_out=eps)
-        self.counter += 1
-        return None if batch_size is None else (idx, eps)
-

@@ -163,74 +163,144 @@ def _f32_cuda(name: str, t, device) -> None:
         raise ValueError(f"{name} must be a contiguous float32 cuda tensor on the actor's device")
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _launch(fn: str, device, *args) -> None:
+    """One call of the library's ``fn`` on the current stream of ``device``, the stream as its last argument."""
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.load(), fn)(*args, stream), fn)
+
+
+def _launch_act(fn: str, actor, rows: torch.Tensor, width: int, wide, narrow, *args) -> None:
+    """The checks of an act wrapper, then ``_launch(fn, rows.device, *args)``: ``rows`` (n, 965); ``wide`` pairs (name, tensor of
+    (n, width) values); ``narrow`` triples (name, tensor, number of values).  Every tensor may be ``None``."""
+    device = actor.packed.device
+    _f32_cuda("rows", rows, device)
+    for name, t, _ in narrow:
+        _f32_cuda(name, t, device)
+    for name, t in wide:
+        _f32_cuda(name, t, device)
+    n = int(rows.shape[0])
+    if rows.dim() != 2 or rows.shape[1] != OBS_DIM:
+        raise ValueError(f"rows must have shape (n, {OBS_DIM})")
+    for name, t in wide:
+        if t is not None and t.numel() != n * width:
+            raise ValueError(f"{name} must hold ({n}, {width}) values")
+    for name, t, numel in narrow:
+        if t is not None and t.numel() != numel:
+            raise ValueError(f"{name} must hold {numel} values")
+    _launch(fn, rows.device, *args)
+
+
 def collect_act(actor, rows: torch.Tensor, counter: int, hp: "_lib.Td3CollectHparams", act_out: torch.Tensor,
                 env_act_out: torch.Tensor, *, mean_out=None, eps_out=None) -> None:
     """One ``rover_td3_collect_act`` launch on the current stream over the already-sanitised ``rows`` (n, 965); ``mean_out`` /
     ``eps_out`` left ``None`` are passed as NULL."""
-    for name, t in (("rows", rows), ("act_out", act_out), ("env_act_out", env_act_out), ("mean_out", mean_out), ("eps_out", eps_out)):
-        _f32_cuda(name, t, actor.packed.device)
-    n = int(rows.shape[0])
-    if rows.dim() != 2 or rows.shape[1] != OBS_DIM:
-        raise ValueError(f"rows must have shape (n, {OBS_DIM})")
-    for name, t in (("act_out", act_out), ("env_act_out", env_act_out), ("mean_out", mean_out), ("eps_out", eps_out)):
-        if t is not None and t.numel() != n * actor.out_dim:
-            raise ValueError(f"{name} must hold ({n}, {actor.out_dim}) values")
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    stream = C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
-    with torch.cuda.device(rows.device):
-        _lib.check(_lib.load().rover_td3_collect_act(C.byref(actor.desc), actor.packed.data_ptr(), actor.n_copies, C.byref(hp),
-                                                     C.c_uint64(int(counter)), rows.data_ptr(), n, ptr(mean_out), act_out.data_ptr(),
-                                                     env_act_out.data_ptr(), ptr(eps_out), stream), "rover_td3_collect_act")
+    wide = (("act_out", act_out), ("env_act_out", env_act_out), ("mean_out", mean_out), ("eps_out", eps_out))
+    _launch_act("rover_td3_collect_act", actor, rows, actor.out_dim, wide, (), C.byref(actor.desc), actor.packed.data_ptr(),
+                actor.n_copies, C.byref(hp), C.c_uint64(int(counter)), rows.data_ptr(), int(rows.shape[0]), _ptr(mean_out),
+                act_out.data_ptr(), env_act_out.data_ptr(), _ptr(eps_out))
 
 
 def collect_record(raw: torch.Tensor, ring_slot: torch.Tensor, hp: "_lib.Td3CollectHparams", counter: int = 0, *, rew=None,
                    terminated=None, rew_out=None, term_out=None, ring_pos_entry=None, ring_pos_value: int = 0, idx_out=None,
                    mem_rows: int = 0) -> None:
     """One ``rover_td3_collect_record`` launch on the current stream; every argument left ``None`` is passed as NULL."""
-    n = int(raw.shape[0])
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    stream = C.c_void_p(torch.cuda.current_stream(raw.device).cuda_stream)
-    with torch.cuda.device(raw.device):
-        _lib.check(_lib.load().rover_td3_collect_record(raw.data_ptr(), n, ring_slot.data_ptr(), ptr(rew), ptr(terminated), ptr(rew_out),
-                                                        ptr(term_out), ptr(ring_pos_entry), int(ring_pos_value), ptr(idx_out),
-                                                        0 if idx_out is None else int(idx_out.numel()), int(mem_rows), C.byref(hp),
-                                                        C.c_uint64(int(counter)), stream), "rover_td3_collect_record")
+    _launch("rover_td3_collect_record", raw.device, raw.data_ptr(), int(raw.shape[0]), ring_slot.data_ptr(), _ptr(rew), _ptr(terminated),
+            _ptr(rew_out), _ptr(term_out), _ptr(ring_pos_entry), int(ring_pos_value), _ptr(idx_out),
+            0 if idx_out is None else int(idx_out.numel()), int(mem_rows), C.byref(hp), C.c_uint64(int(counter)))
 
 
-class TD3Collector(_CollectorBase):
-    """The fused collector: ``actor`` is a ``RoverNet`` (reference architecture, no final activation) and ``memory`` a
-    ``ReplayMemory`` on the same device, both held BY REFERENCE -- with ``FusedTD3.actor`` the collector always sees the trainer's
-    current parameters.  ``act`` returns a buffer the next call overwrites, ``record`` likewise (one index buffer per batch size).
-    """
+class _FusedCollector(_CollectorBase):
+    """What the fused collectors share: the env's action buffer, ``begin``, ``record`` and the seed / offset part of the hparams.
+    A subclass names itself in ``_NAME``, launches its record kernel in ``_record`` and, with ``_DRAWS``, has ``record`` fill and
+    return the update's (batch, 4) standard normals beside the indices."""
 
-    def __init__(self, actor, memory: ReplayMemory, seed: int = 42, env_id_offset: int = 0, noise_std: float = 0.0, clip=(-1.0, 1.0)):
+    _NAME = ""
+    _DRAWS = False
+
+    def __init__(self, memory: ReplayMemory, seed: int, env_id_offset: int, noise_std: float, clip):
         if not torch.cuda.is_available():
-            raise _lib.RoverHipError("TD3Collector needs a ROCm GPU (no CPU fallback; TorchTD3Collector is the CPU specification)")
+            raise _lib.RoverHipError(f"{self._NAME} needs a ROCm GPU (no CPU fallback; Torch{self._NAME} is the CPU specification)")
         super().__init__(memory, seed, env_id_offset, noise_std, clip)
+
+    def _bind(self, actor) -> None:
         self._lib = _lib.load()
         self.actor = actor
-        if memory.obs.device != actor.packed.device:
+        if self.memory.obs.device != actor.packed.device:
             raise ValueError("the memory must live on the actor's device")
-        if actor.out_dim != self.A or actor.out_dim > 16:
-            raise ValueError("the memory's action width must be the actor's output width (at most 16)")
-        self._env_act = torch.zeros(self.n, self.A, dtype=torch.float32, device=memory.obs.device)
-        self._idx: dict = {}
+        self._env_act = torch.zeros(self.n, self.A, dtype=torch.float32, device=self.memory.obs.device)
+        self._bufs: dict = {}
 
-    def hparams(self, scale: float | None = None) -> "_lib.Td3CollectHparams":
-        hp = default_hparams()
+    def _seeded(self, hp):
         hp.seed_lo, hp.seed_hi = self.seed & _MASK, (self.seed >> 32) & _MASK
         hp.env_id_offset = self.env_id_offset
-        hp.explore = int(self._exploring(scale))
-        hp.noise_std, hp.noise_scale = self.noise_std, 1.0 if scale is None else float(scale)
-        hp.action_low, hp.action_high = self.clip
         return hp
+
+    def _record(self, raw, ring_slot, counter=0, idx=None, eps=None, **transition) -> None:
+        raise NotImplementedError
 
     @torch.no_grad()
     def begin(self, raw_obs) -> None:
         """The rows after a reset go, sanitised, into the ring's cursor slot.  No draw: the counter stays."""
         m = self.memory
-        collect_record(self._raw(raw_obs), m.obs[m.cursor], self.hparams())
+        self._record(self._raw(raw_obs), m.obs[m.cursor])
         m._last_next, m._last_version = None, -1
+
+    @torch.no_grad()
+    def record(self, raw_obs, rew: torch.Tensor, terminated: torch.Tensor, batch_size: int | None = None):
+        """The transition of the step just taken: the env's rows, sanitised, into the next ring slot, reward / terminated / ring_pos of
+        memory slot k; with ``batch_size`` the int64 row indices of a batch over the memory INCLUDING this transition -- with
+        ``_DRAWS`` the pair ``(idx, eps)``, eps the update's float32 draws (batch_size, 4) -- else ``None``.  Advances the memory as
+        ``ReplayMemory.add`` does, and the counter by one."""
+        m = self.memory
+        raw = self._raw(raw_obs)
+        self._transition(rew, terminated)
+        if not rew.is_cuda:
+            raise ValueError("rew and terminated must be cuda tensors")
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        k, w = m.memory_index, m.cursor
+        self._advance()
+        idx = eps = None
+        if batch_size is not None:
+            batch = int(batch_size)
+            if batch not in self._bufs:
+                self._bufs[batch] = (torch.zeros(batch, dtype=torch.int64, device=m.obs.device),
+                                     torch.zeros(batch, 4, dtype=torch.float32, device=m.obs.device) if self._DRAWS else None)
+            idx, eps = self._bufs[batch]
+        self._record(raw, m.obs[(w + 1) % m.slots], self.counter, idx, eps, rew=rew, terminated=terminated, rew_out=m.rewards[k],
+                     term_out=m.terminated[k], ring_pos_entry=m.ring_pos[k:k + 1], ring_pos_value=w, mem_rows=len(m))
+        self.counter += 1
+        return (idx, eps) if self._DRAWS and idx is not None else idx
+
+
+class TD3Collector(_FusedCollector):
+    """The fused collector: ``actor`` is a ``RoverNet`` (reference architecture, no final activation) and ``memory`` a
+    ``ReplayMemory`` on the same device, both held BY REFERENCE -- with ``FusedTD3.actor`` the collector always sees the trainer's
+    current parameters.  ``act`` returns a buffer the next call overwrites, ``record`` likewise (one index buffer per batch size).
+    """
+
+    _NAME = "TD3Collector"
+
+    def __init__(self, actor, memory: ReplayMemory, seed: int = 42, env_id_offset: int = 0, noise_std: float = 0.0, clip=(-1.0, 1.0)):
+        super().__init__(memory, seed, env_id_offset, noise_std, clip)
+        self._bind(actor)
+        if actor.out_dim != self.A or actor.out_dim > 16:
+            raise ValueError("the memory's action width must be the actor's output width (at most 16)")
+
+    def hparams(self, scale: float | None = None) -> "_lib.Td3CollectHparams":
+        hp = self._seeded(default_hparams())
+        hp.explore = int(self._exploring(scale))
+        hp.noise_std, hp.noise_scale = self.noise_std, 1.0 if scale is None else float(scale)
+        hp.action_low, hp.action_high = self.clip
+        return hp
+
+    def _record(self, raw, ring_slot, counter=0, idx=None, eps=None, **transition) -> None:
+        collect_record(raw, ring_slot, self.hparams(), counter, idx_out=idx, **transition)
 
     @torch.no_grad()
     def act(self, scale: float | None = None, mean_out=None, eps_out=None) -> torch.Tensor:
@@ -242,28 +312,3 @@ class TD3Collector(_CollectorBase):
                     mean_out=mean_out, eps_out=eps_out)
         self.counter += 1
         return self._env_act
-
-    @torch.no_grad()
-    def record(self, raw_obs, rew: torch.Tensor, terminated: torch.Tensor, batch_size: int | None = None):
-        """The transition of the step just taken: the env's rows, sanitised, into the next ring slot, reward / terminated / ring_pos of
-        memory slot k; with ``batch_size`` the int64 row indices of a batch over the memory INCLUDING this transition (else ``None``).
-        Advances the memory as ``ReplayMemory.add`` does, and the counter by one."""
-        m = self.memory
-        raw = self._raw(raw_obs)
-        self._transition(rew, terminated)
-        if not rew.is_cuda:
-            raise ValueError("rew and terminated must be cuda tensors")
-        k, w = m.memory_index, m.cursor
-        self._advance()
-        idx = None
-        if batch_size is not None:
-            if int(batch_size) < 1:
-                raise ValueError("batch_size must be >= 1")
-            idx = self._idx.get(int(batch_size))
-            if idx is None:
-                idx = self._idx[int(batch_size)] = torch.zeros(int(batch_size), dtype=torch.int64, device=m.obs.device)
-        collect_record(raw, m.obs[(w + 1) % m.slots], self.hparams(), self.counter, rew=rew, terminated=terminated,
-                       rew_out=m.rewards[k], term_out=m.terminated[k], ring_pos_entry=m.ring_pos[k:k + 1], ring_pos_value=w,
-                       idx_out=idx, mem_rows=len(m))
-        self.counter += 1
-        return idx

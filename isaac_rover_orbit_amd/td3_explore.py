@@ -33,8 +33,8 @@ import torch
 from . import _lib
 from .lift_rollout import LIFT_ROLLOUT_TAG
 from .rollout import ROLLOUT_TAG, _MASK, philox4x32, standard_normals, unit_uniform
-from .td3 import HPARAMS, OBS_DIM, ReplayMemory, exploration_scale
-from .td3_collect import INDEX_TAG, NOISE_TAG, TD3Collector, TorchTD3Collector, _f32_cuda
+from .td3 import HPARAMS, ReplayMemory, exploration_scale
+from .td3_collect import INDEX_TAG, NOISE_TAG, TD3Collector, TorchTD3Collector, _launch, _launch_act, _ptr
 
 RANDOM_TAG = 0x54335200           # "T3R\0": word 3 of the Philox counter of the random actions, | action quad
 SMOOTH_TAG = 0x54334E00           # "T3N\0": ... of the smoothing noise, | action pair
@@ -185,33 +185,18 @@ def explore_act(actor, rows: torch.Tensor, counter: int, hp: "_lib.Td3ExploreHpa
                 env_act_out: torch.Tensor, *, ou_state=None, mean_out=None, eps_out=None) -> None:
     """One ``rover_td3_explore_act`` launch on the current stream over the already-sanitised ``rows`` (n, 965); ``ou_state`` /
     ``mean_out`` / ``eps_out`` left ``None`` are passed as NULL."""
-    outs = (("act_out", act_out), ("env_act_out", env_act_out), ("ou_state", ou_state), ("mean_out", mean_out), ("eps_out", eps_out))
-    for name, t in (("rows", rows),) + outs:
-        _f32_cuda(name, t, actor.packed.device)
-    n = int(rows.shape[0])
-    if rows.dim() != 2 or rows.shape[1] != OBS_DIM:
-        raise ValueError(f"rows must have shape (n, {OBS_DIM})")
-    for name, t in outs:
-        if t is not None and t.numel() != n * actor.out_dim:
-            raise ValueError(f"{name} must hold ({n}, {actor.out_dim}) values")
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    stream = C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
-    with torch.cuda.device(rows.device):
-        _lib.check(_lib.load().rover_td3_explore_act(C.byref(actor.desc), actor.packed.data_ptr(), actor.n_copies, C.byref(hp),
-                                                     C.c_uint64(int(counter)), rows.data_ptr(), n, ptr(ou_state), ptr(mean_out),
-                                                     act_out.data_ptr(), env_act_out.data_ptr(), ptr(eps_out), stream),
-                   "rover_td3_explore_act")
+    wide = (("act_out", act_out), ("env_act_out", env_act_out), ("ou_state", ou_state), ("mean_out", mean_out), ("eps_out", eps_out))
+    _launch_act("rover_td3_explore_act", actor, rows, actor.out_dim, wide, (), C.byref(actor.desc), actor.packed.data_ptr(),
+                actor.n_copies, C.byref(hp), C.c_uint64(int(counter)), rows.data_ptr(), int(rows.shape[0]), _ptr(ou_state),
+                _ptr(mean_out), act_out.data_ptr(), env_act_out.data_ptr(), _ptr(eps_out))
 
 
 def smooth_draw(seed: int, counter: int, std: float, out: torch.Tensor) -> torch.Tensor:
     """One ``rover_td3_smooth_draw`` launch on the current stream into ``out`` (n, A), a contiguous float32 cuda tensor."""
     if not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 2:
         raise ValueError("out must be a contiguous float32 cuda tensor of shape (n, A)")
-    stream = C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)
-    with torch.cuda.device(out.device):
-        _lib.check(_lib.load().rover_td3_smooth_draw(int(seed) & _MASK, (int(seed) >> 32) & _MASK, C.c_uint64(int(counter)), float(std),
-                                                     out.data_ptr(), int(out.shape[0]), int(out.shape[1]), stream),
-                   "rover_td3_smooth_draw")
+    _launch("rover_td3_smooth_draw", out.device, int(seed) & _MASK, (int(seed) >> 32) & _MASK, C.c_uint64(int(counter)), float(std),
+            out.data_ptr(), int(out.shape[0]), int(out.shape[1]))
     return out
 
 
@@ -229,9 +214,8 @@ class TD3Explorer(_ExplorerMixin, TD3Collector):
         self._smooth: dict = {}
 
     def explore_hparams(self, mode: int, scale: float | None = None) -> "_lib.Td3ExploreHparams":
-        hp = default_hparams()
-        hp.seed_lo, hp.seed_hi = self.seed & _MASK, (self.seed >> 32) & _MASK
-        hp.env_id_offset, hp.mode = self.env_id_offset, mode
+        hp = self._seeded(default_hparams())
+        hp.mode = mode
         hp.noise_std, hp.noise_scale = self.noise_std, 1.0 if scale is None else float(scale)
         hp.ou_theta, hp.ou_sigma, hp.ou_base_scale = self.ou
         hp.action_low, hp.action_high = self.clip

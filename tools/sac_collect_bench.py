@@ -26,7 +26,7 @@ from isaac_rover_orbit_amd import terrain as T  # noqa: E402
 from isaac_rover_orbit_amd.cfg import RoverEnvCfg  # noqa: E402
 from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
 from isaac_rover_orbit_amd.sac import LOG_STD_MAX, LOG_STD_MIN, FusedSAC  # noqa: E402
-from isaac_rover_orbit_amd.sac_collect import MEAN, SACCollector, collect_act, default_hparams  # noqa: E402
+from isaac_rover_orbit_amd.sac_collect import MEAN, SACCollector, collect_act, collect_record, default_hparams  # noqa: E402
 from isaac_rover_orbit_amd.td3 import Critic, ReplayMemory  # noqa: E402
 from isaac_rover_orbit_amd.td3_explore import smooth_draw  # noqa: E402
 
@@ -40,15 +40,21 @@ def load_example():
 
 
 def kernel_times(actor, log_std, rows, reps=300):
-    """us per launch, back to back on one stream: rover_policy_forward, the act kernel in MEAN and in SAMPLE mode."""
+    """us per launch, back to back on one stream: rover_policy_forward, the act kernel in MEAN and in SAMPLE mode, and the record
+    kernel on the same rows with a batch of n indices and draws."""
     n = rows.shape[0]
     f = dict(dtype=torch.float32, device="cuda")
     mean, act, env_act = (torch.empty(n, 2, **f) for _ in range(3))
     sample, plain = default_hparams(), default_hparams()
     plain.mode = MEAN
+    slot, rew, rew_out, eps = torch.empty_like(rows), torch.zeros(n, **f), torch.empty(n, **f), torch.empty(n, 4, **f)
+    term, term_out = torch.zeros(n, dtype=torch.bool, device="cuda"), torch.empty(n, dtype=torch.bool, device="cuda")
+    pos, idx = torch.zeros(1, dtype=torch.int32, device="cuda"), torch.empty(n, dtype=torch.int64, device="cuda")
     forms = {"policy_forward": lambda: actor(rows, mean),
              "act_mean": lambda: collect_act(actor, log_std, rows, 1, plain, act, env_act),
-             "act_sample": lambda: collect_act(actor, log_std, rows, 1, sample, act, env_act)}
+             "act_sample": lambda: collect_act(actor, log_std, rows, 1, sample, act, env_act),
+             "record": lambda: collect_record(rows, slot, sample, 1, rew=rew, terminated=term, rew_out=rew_out, term_out=term_out,
+                                              ring_pos_entry=pos, ring_pos_value=3, idx_out=idx, mem_rows=17 * n, eps_out=eps)}
     res = {name: [] for name in forms}
     for _ in range(5):                               # alternate the forms; each window ends in a synchronise
         for name, fn in forms.items():

@@ -26,7 +26,7 @@ from isaac_rover_orbit_amd import terrain as T  # noqa: E402
 from isaac_rover_orbit_amd.cfg import RoverEnvCfg  # noqa: E402
 from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
 from isaac_rover_orbit_amd.td3 import Critic, FusedTD3, ReplayMemory, explore  # noqa: E402
-from isaac_rover_orbit_amd.td3_collect import TD3Collector, collect_act, default_hparams  # noqa: E402
+from isaac_rover_orbit_amd.td3_collect import TD3Collector, collect_act, collect_record, default_hparams  # noqa: E402
 
 
 def load_example():
@@ -38,15 +38,21 @@ def load_example():
 
 
 def kernel_times(actor, rows, reps=300):
-    """us per launch, back to back on one stream: rover_policy_forward, the act kernel without and with exploration."""
+    """us per launch, back to back on one stream: rover_policy_forward, the act kernel without and with exploration, and the record
+    kernel on the same rows with a batch of n indices."""
     n = rows.shape[0]
     f = dict(dtype=torch.float32, device="cuda")
     mean, act, env_act = (torch.empty(n, 2, **f) for _ in range(3))
     plain, noisy = default_hparams(), default_hparams()
     noisy.explore, noisy.noise_std = 1, 0.1
+    slot, rew, rew_out = torch.empty_like(rows), torch.zeros(n, **f), torch.empty(n, **f)
+    term, term_out = torch.zeros(n, dtype=torch.bool, device="cuda"), torch.empty(n, dtype=torch.bool, device="cuda")
+    pos, idx = torch.zeros(1, dtype=torch.int32, device="cuda"), torch.empty(n, dtype=torch.int64, device="cuda")
     forms = {"policy_forward": lambda: actor(rows, mean),
              "act": lambda: collect_act(actor, rows, 1, plain, act, env_act),
-             "act_explore": lambda: collect_act(actor, rows, 1, noisy, act, env_act)}
+             "act_explore": lambda: collect_act(actor, rows, 1, noisy, act, env_act),
+             "record": lambda: collect_record(rows, slot, plain, 1, rew=rew, terminated=term, rew_out=rew_out, term_out=term_out,
+                                              ring_pos_entry=pos, ring_pos_value=3, idx_out=idx, mem_rows=17 * n)}
     res = {name: [] for name in forms}
     for _ in range(5):                               # alternate the forms; each window ends in a synchronise
         for name, fn in forms.items():
