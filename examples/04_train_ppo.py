@@ -13,6 +13,10 @@ which needs packages that are not part of this repository.
 (``TorchScaledPPO`` or ``FusedScaledPPO``) and ``isaac_rover_orbit_amd.rollout_scaled.ScaledRolloutCollector`` for the fused
 rollout.  The default, ``none``, trains on the raw rows as before.
 
+``--kl_early_stop 0.008 --scheduler none`` is rover_ppo.yaml as skrl 1.1 reads it (``kl_threshold`` is skrl's KL early stop and the
+file has no ``learning_rate_scheduler``); rover_rpo.yaml is the same.  ``--rewards_shaper_scale`` / ``--time_limit_bootstrap`` are
+the agent files' switches of those names.  The defaults keep this example's own reading: no early stop, KL-adaptive rate.
+
     python examples/04_train_ppo.py --num_envs 4096 --iterations 100
 """
 import argparse
@@ -72,7 +76,7 @@ def ppo_loss(policy, value, o, a, old_lp, old_v, ret, adv, clip=CLIP, vclip=VCLI
     return pl + vl, kl
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--iterations", type=int, default=100)
@@ -88,7 +92,29 @@ def main():
     ap.add_argument("--preprocess", choices=("none", "running"), default="none",
                     help="running: skrl's RunningStandardScaler on states and values (state_preprocessor / value_preprocessor of "
                          "rover_ppo.yaml), as HIP kernels wherever --update / --rollout is fused")
-    args = ap.parse_args()
+    ap.add_argument("--kl_early_stop", type=float, default=0.0, metavar="F",
+                    help="skrl's KL early stop (its kl_threshold): an epoch stops at the first minibatch whose KL exceeds F, before that "
+                         "minibatch's optimiser step; 0 (default): never.  --kl_early_stop 0.008 --scheduler none is rover_ppo.yaml as "
+                         "skrl reads it, and rover_rpo.yaml is the same")
+    ap.add_argument("--scheduler", choices=("kl_adaptive", "none"), default="kl_adaptive",
+                    help="learning-rate scheduler stepped per epoch on the mean of the recorded KLs: skrl's KLAdaptiveRL (default), or "
+                         "none (rover_ppo.yaml has its learning_rate_scheduler commented out)")
+    ap.add_argument("--rewards_shaper_scale", type=float, default=None, metavar="F",
+                    help="the agent files' rewards_shaper_scale: rewards are multiplied by F as they are recorded (default: off)")
+    ap.add_argument("--time_limit_bootstrap", action="store_true",
+                    help="skrl's time_limit_bootstrap: rewards += discount * value * truncated as they are recorded")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
+    if args.kl_early_stop < 0:
+        raise SystemExit("--kl_early_stop must be >= 0")
+    scheduler = None if args.scheduler == "none" else args.scheduler
+    skrl_loops = args.kl_early_stop > 0 or scheduler is None                    # the update follows skrl's loops, not the default ones
+    shaped = args.rewards_shaper_scale is not None or args.time_limit_bootstrap
+    shape_kw = dict(rewards_shaper_scale=args.rewards_shaper_scale, time_limit_bootstrap=args.time_limit_bootstrap, discount=GAMMA)
+    upd_kw = dict(kl_early_stop=args.kl_early_stop, scheduler=scheduler) if skrl_loops else {}
     torch.manual_seed(42)
     dev = torch.device("cuda")
     n, Tn = args.num_envs, args.rollouts
@@ -109,6 +135,14 @@ def main():
     elif scaled:
         from isaac_rover_orbit_amd.ppo_scaled import TorchScaledPPO
         tscaled = TorchScaledPPO(policy, value, lr=1e-4, device=dev)
+        if skrl_loops:
+            from isaac_rover_orbit_amd.ppo_skrl import TorchSkrlPPO
+            tscaled = TorchSkrlPPO(policy, value, lr=1e-4, device=dev)
+    tskrl = None                                # the torch update on the raw rows with skrl's loops
+    if fused is None and not scaled and skrl_loops:
+        from isaac_rover_orbit_amd.ppo_skrl import TorchSkrlPPO
+        tskrl = TorchSkrlPPO(policy, value, lr=1e-4, scalers=False, device=dev)
+        opt = tskrl.opt
     # what the networks read and what the buffer stores of the critic, for the torch rollout glue
     if not scaled:
         standardise, unscale = (lambda x: x), (lambda v: v)
@@ -168,7 +202,7 @@ def main():
             if collector is not None:           # the raw rows go in; slot t of every buffer comes out
                 obs, rew, term, trunc, info = env.step(collector.act(t, o))
                 o = obs["policy"]
-                collector.record(t, rew, term, trunc)
+                collector.record(t, rew, term, trunc, **(shape_kw if shaped else {}))
                 lv = env.episode_log_vector
                 ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
                 continue
@@ -180,6 +214,10 @@ def main():
             obs_buf[t], act_buf[t] = o, a
             obs, rew, term, trunc, info = env.step(a.clamp(-1.0, 1.0))      # clip_actions (models.py:66)
             o = torch.nan_to_num(obs["policy"], neginf=0.0)
+            if shaped:
+                from isaac_rover_orbit_amd.ppo_skrl import shape_rewards
+                rew = shape_rewards(rew, val_buf[t], trunc, 1.0 if args.rewards_shaper_scale is None else args.rewards_shaper_scale,
+                                    GAMMA, args.time_limit_bootstrap)
             rew_buf[t], done_buf[t] = rew, (term | trunc).float()
             lv = env.episode_log_vector
             ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
@@ -192,10 +230,11 @@ def main():
                 adv = (adv - adv.mean()) / (adv.std() + 1e-8)
             if scaled:                          # skrl PPO._update: the value scaler trains on the values, then on the returns
                 val_s, ret_s = fused.standardize_values(val_buf, ret)
-                kls, _ = fused.update(obs_buf, act_buf, logp_buf, val_s, ret_s, adv)
+                kls, _ = fused.update(obs_buf, act_buf, logp_buf, val_s, ret_s, adv, **upd_kw)
             else:
-                kls, _ = fused.update(obs_buf, act_buf, logp_buf, val_buf, ret, adv)
+                kls, _ = fused.update(obs_buf, act_buf, logp_buf, val_buf, ret, adv, **upd_kw)
             kl_mean = kls[-1]
+            last = fused.last_update
         else:
             # ---- GAE (skrl PPO: bootstraps through time-outs like the reference's config)
             with torch.no_grad():
@@ -213,10 +252,15 @@ def main():
             B = Tn * n
             fo, fa, flp, fv, fr, fadv = (x.reshape(B, *x.shape[2:]) for x in (obs_buf, act_buf, logp_buf, val_buf, ret, adv))
             kl_mean = 0.0
+            last = None
             if scaled:                          # the same update behind the two scalers (ppo_scaled.TorchScaledPPO)
                 val_s, ret_s = tscaled.standardize_values(fv, fr)
-                kl_mean = tscaled.update(fo, fa, flp, val_s, ret_s, fadv)[0][-1]
-            for epoch in range(0 if scaled else 4):   # the unscaled update, as before
+                kl_mean = tscaled.update(fo, fa, flp, val_s, ret_s, fadv, **upd_kw)[0][-1]
+                last = getattr(tscaled, "last_update", None)
+            elif tskrl is not None:             # skrl's loops on the raw rows (ppo_skrl.TorchSkrlPPO)
+                kl_mean = tskrl.update(fo, fa, flp, fv, fr, fadv, **upd_kw)[0][-1]
+                last = tskrl.last_update
+            for epoch in range(0 if scaled or tskrl is not None else 4):   # the unscaled update, as before
                 perm = torch.randperm(B, device=dev)
                 kls = []
                 for mb in perm.chunk(60):
@@ -236,6 +280,7 @@ def main():
               "time_out": ep_stats[0].item(), "success": ep_stats[1].item(), "far": ep_stats[2].item(),
               "collision": ep_stats[3].item(), "kl": kl_mean,
               "lr": fused.lr if fused is not None else tscaled.lr if tscaled is not None else opt.param_groups[0]["lr"],
+              "recorded": last["recorded"] if last else [60] * 4, "stopped": last["stopped"] if last else [False] * 4,
               "rollout_s": t_roll, "rollout_env_steps_per_s": Tn * n / t_roll, "iteration_s": time.perf_counter() - t0}
         print(json.dumps(st), flush=True)
         if out:

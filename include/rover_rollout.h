@@ -12,7 +12,8 @@
  *     env_act  = clip_actions ? clamp(act, low, high) : act
  *     logp     = sum_c (-0.5 x_c^2 - ls_c - 0.9189385332),  x_c = (act_c - mean_c) / std_c
  *
- * in ONE launch (rover_rollout_act), and the reward / done record in a second, small one (rover_rollout_record).
+ * in ONE launch (rover_rollout_act), and the reward / done record in a second, small one (rover_rollout_record, or
+ * rover_rollout_record_shaped with skrl's rewards_shaper_scale and time_limit_bootstrap).
  *
  * The draws are counter-based: row r of a call has the global id g = env_id_offset + r, and the normal pair p = c / 2 of step
  * `counter` comes from
@@ -73,6 +74,18 @@ int rover_rollout_act(const rover_policy_desc *actor, const float *packed_a,
 /* rew_out[i] = rew[i], done_out[i] = (terminated[i] | truncated[i]) ? 1.0f : 0.0f for i < n (one small launch). */
 int rover_rollout_record(const float *rew, const uint8_t *terminated, const uint8_t *truncated, int32_t n,
                          float *rew_out, float *done_out, void *stream);
+
+/* rover_rollout_record with skrl's reward shaper and time-limit bootstrap (PPO.record_transition), one launch:
+ *     r = rew[i] * reward_scale                                  (rewards_shaper_scale: rover_envs/utils/config.py:84-88)
+ *     time_limit_bootstrap != 0:  rew_out[i] = r + (discount * val[i]) * trunc,  trunc = truncated[i] ? 1.0f : 0.0f
+ *     time_limit_bootstrap == 0:  rew_out[i] = r                 (val is not read and may be NULL)
+ * in fp32, every product and the sum formed (nothing contracted): skrl's `rewards += discount_factor * values * truncated` with
+ * `discount` rounded to fp32.  An infinite val on a row that is not truncated gives inf * 0 = NaN, as in torch.  val: THIS step's
+ * critic output on the return's scale (the collector's value slot): skrl bootstraps with the value of the pre-step states.
+ * done_out as rover_rollout_record.  The float arrays are 4-byte aligned, nothing wider is assumed. */
+int rover_rollout_record_shaped(const float *rew, const uint8_t *terminated, const uint8_t *truncated, const float *val, int32_t n,
+                                float reward_scale, float discount, int32_t time_limit_bootstrap, float *rew_out, float *done_out,
+                                void *stream);
 
 #ifdef __cplusplus
 }

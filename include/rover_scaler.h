@@ -68,6 +68,14 @@ size_t rover_scaler_workspace_bytes(int32_t width, int32_t max_rows);
 int rover_scaler_train(const rover_scaler_hparams *h, double *scaler, int32_t width, const float *x, const int64_t *idx,
                        int32_t rows, void *ws, size_t ws_bytes, void *stream);
 
+/* rover_scaler_train behind a gate word (device memory, 4-byte aligned; rover_ppo_epoch.stop of rover_train_gate.h): each of the
+ * four launches returns at once when *gate != 0 and the block and the workspace are untouched; otherwise bit-identical to
+ * rover_scaler_train.  No kernel of this header writes the gate.  skrl standardises (and in the first epoch trains) a minibatch's
+ * states before it computes the KL, so the minibatch that stops an epoch still trains the state scaler and the skipped ones do
+ * not: the gate is read as the minibatch before left it. */
+int rover_scaler_train_gated(const rover_scaler_hparams *h, double *scaler, int32_t width, const float *x, const int64_t *idx,
+                             int32_t rows, void *ws, size_t ws_bytes, const int32_t *gate, void *stream);
+
 /* out = scaler(x), one launch, no update of the block.
  *   idx == NULL: rows [0, rows) of x into rows [0, rows) of out.
  *   idx given:   row idx[i] of x into row idx[i] of out, i < rows: in place within a (B, width) image, rows not named are not

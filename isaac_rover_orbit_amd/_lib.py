@@ -62,7 +62,9 @@ EXPORTS = [
     "rover_sac_collect_default_hparams", "rover_sac_collect_hparams_bytes", "rover_sac_collect_act",  # rover_sac_collect.h
     "rover_sac_collect_record",
     "rover_scaler_default_hparams", "rover_scaler_hparams_bytes", "rover_scaler_doubles", "rover_scaler_workspace_bytes",  # rover_scaler.h
-    "rover_scaler_train", "rover_scaler_apply",
+    "rover_scaler_train", "rover_scaler_apply", "rover_scaler_train_gated",
+    "rover_ppo_epoch_bytes", "rover_ppo_minibatch_gated", "rover_ppo_apply_gated", "rover_ppo_epoch_end",  # rover_train_gate.h
+    "rover_rollout_record_shaped",  # rover_rollout.h
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -93,6 +95,12 @@ class PpoState(C.Structure):
     """Mirror of ``struct rover_ppo_state`` (include/rover_train.h; it lives in device memory)."""
     _fields_ = [("lr", C.c_double), ("step", C.c_int32), ("grad_norm", C.c_float), ("clip_coef", C.c_float),
                 ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("reserved", C.c_float)]
+
+
+class PpoEpoch(C.Structure):
+    """Mirror of ``struct rover_ppo_epoch`` (include/rover_train_gate.h; it lives in device memory)."""
+    _fields_ = [("stop", C.c_int32), ("recorded", C.c_int32), ("epochs", C.c_int32), ("stopped_epochs", C.c_int32),
+                ("stop_minibatch", C.c_int32), ("stop_kl", C.c_float), ("reserved", C.c_int32 * 2)]
 
 
 class LiftPpoHparams(C.Structure):
@@ -403,6 +411,12 @@ def load():
     lib.rover_ppo_gae.argtypes = [C.POINTER(PpoHparams), vp, vp, vp, vp, i32, i32, vp, vp, vp]
     lib.rover_ppo_kl_schedule.argtypes = [C.POINTER(PpoHparams), vp, i32, vp, vp, vp]
     lib.rover_policy_unpack.argtypes = [C.POINTER(PolicyDesc), vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.rover_ppo_epoch_bytes.restype = C.c_size_t
+    lib.rover_ppo_minibatch_gated.argtypes = [C.POINTER(PolicyDesc), C.POINTER(PolicyDesc), C.POINTER(PpoHparams), vp, vp, vp, vp, vp,
+                                              vp, vp, vp, i32, vp, C.c_size_t, vp, vp, vp, vp, f32, vp, vp]
+    lib.rover_ppo_apply_gated.argtypes = [C.POINTER(PolicyDesc), C.POINTER(PolicyDesc), C.POINTER(PpoHparams), vp, vp, vp, vp, vp, vp,
+                                          vp, i32, vp, C.c_size_t, vp, vp]
+    lib.rover_ppo_epoch_end.argtypes = [C.POINTER(PpoHparams), vp, i32, vp, vp, i32, vp, vp]
     lib.rover_lift_policy_desc.argtypes = [C.POINTER(PolicyDesc), i32]
     lib.rover_lift_ppo_default_hparams.argtypes = [C.POINTER(LiftPpoHparams)]
     lib.rover_lift_ppo_hparams_bytes.restype = C.c_size_t
@@ -452,6 +466,7 @@ def load():
     lib.rover_rollout_act.argtypes = [pd, vp, pd, vp, i32, C.POINTER(RolloutHparams), C.c_uint64, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                       vp, vp]
     lib.rover_rollout_record.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    lib.rover_rollout_record_shaped.argtypes = [vp, vp, vp, vp, i32, f32, f32, i32, vp, vp, vp]
     lib.rover_lift_rollout_default_hparams.argtypes = [C.POINTER(LiftRolloutHparams)]
     lib.rover_lift_rollout_hparams_bytes.restype = C.c_size_t
     lib.rover_lift_rollout_act.argtypes = [pd, vp, pd, vp, i32, C.POINTER(LiftRolloutHparams), C.c_uint64, vp, i32, vp, vp, vp, vp, vp,
@@ -505,6 +520,7 @@ def load():
     lib.rover_scaler_workspace_bytes.restype = C.c_size_t
     lib.rover_scaler_train.argtypes = [slh, vp, i32, vp, vp, i32, vp, C.c_size_t, vp]
     lib.rover_scaler_apply.argtypes = [slh, vp, i32, vp, vp, i32, i32, vp, vp, vp]
+    lib.rover_scaler_train_gated.argtypes = [slh, vp, i32, vp, vp, i32, vp, C.c_size_t, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
@@ -522,6 +538,8 @@ def load():
         raise RoverHipError("struct rover_viewer_config of librover_hip.so does not match the Python mirror")
     if lib.rover_ppo_hparams_bytes() != C.sizeof(PpoHparams) or lib.rover_ppo_state_bytes() != C.sizeof(PpoState):
         raise RoverHipError("struct rover_ppo_hparams / rover_ppo_state of librover_hip.so does not match the Python mirror")
+    if lib.rover_ppo_epoch_bytes() != C.sizeof(PpoEpoch):
+        raise RoverHipError("struct rover_ppo_epoch of librover_hip.so does not match the Python mirror")
     if lib.rover_lift_ppo_hparams_bytes() != C.sizeof(LiftPpoHparams) or lib.rover_lift_ppo_state_bytes() != C.sizeof(LiftPpoState):
         raise RoverHipError("struct rover_lift_ppo_hparams / rover_lift_ppo_state of librover_hip.so does not match the Python mirror")
     if lib.rover_trpo_hparams_bytes() != C.sizeof(TrpoHparams) or lib.rover_trpo_state_bytes() != C.sizeof(TrpoState):

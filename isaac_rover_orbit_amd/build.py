@@ -38,7 +38,8 @@ HEADERS = [os.path.join(_PKG, "csrc", "rover_model.hpp"), os.path.join(_PKG, "cs
            os.path.join(os.path.dirname(_PKG), "include", "rover_trace.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_sac.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_sac_collect.h"),
-           os.path.join(os.path.dirname(_PKG), "include", "rover_scaler.h")]
+           os.path.join(os.path.dirname(_PKG), "include", "rover_scaler.h"),
+           os.path.join(os.path.dirname(_PKG), "include", "rover_train_gate.h")]
 OBJ_DIR = os.path.join(os.path.dirname(_PKG), "build", "obj")
 OUTPUT = os.path.join(_PKG, "librover_hip.so")
 # fp32 parity with the CPU oracle: no contraction, no fast-math (correctly rounded div / sqrt are hipcc defaults)

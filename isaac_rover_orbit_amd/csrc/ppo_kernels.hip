@@ -10,6 +10,9 @@
 //                        v_mfma_f32_16x16x4_f32 with the rows as k, written in the packed layout;
 //   ppo_mb_final_kernel  one workgroup: log_std gradient, KL and loss terms from the partials.
 // and per optimiser step ppo_sumsq_kernel -> ppo_adam_prep_kernel -> ppo_adam_kernel (norm, clip, Adam, replica refresh).
+// Each of the six has a gated twin for skrl's KL early stop (include/rover_train_gate.h): the same code behind one load of
+// rover_ppo_epoch.stop -- the rows and wgrad kernels as a second instantiation over a wider argument struct, the four small ones as
+// *_gated_kernel around a shared device function; ppo_epoch_end_kernel closes an epoch.
 //
 // The backward reads W[n][k] straight from the packed (B-fragment ordered) parameter vector by index, neither a transposed copy
 // nor an LDS stage: a thread owns one input column k for 16 rows and reads each W[n][k] once per 16 rows, so the 160 KB of
@@ -23,6 +26,7 @@
 #include "../../include/rover_hip.h"
 #include "../../include/rover_policy.h"
 #include "../../include/rover_train.h"
+#include "../../include/rover_train_gate.h"
 #include "rover_internal.hpp"
 #include "train_math.hpp"
 
@@ -133,10 +137,22 @@ struct RowsArgs {
     float *ws;          // the matrices (past WS_HEAD)
     float *part;        // 8 floats per workgroup
     float *mean_out, *value_out;
+    static constexpr bool gated = false;
+};
+// The gated twins (include/rover_train_gate.h) take the same arguments and the stop word: the same kernel text behind one load and
+// a branch the whole grid takes the same way.  Nothing with more than one workgroup writes the word.  The two big kernels are
+// templates over their argument struct, so the ungated instantiation is the kernel it always was, instruction for instruction.
+struct RowsArgsGated : RowsArgs {
+    const int32_t *stop;
+    static constexpr bool gated = true;
 };
 
-__global__ __launch_bounds__(FT) void ppo_rows_kernel(RowsArgs A)
+template <class ARGS>
+__global__ __launch_bounds__(FT) void ppo_rows_kernel(ARGS A)
 {
+    if constexpr (ARGS::gated) {
+        if (*A.stop) return;
+    }
     extern __shared__ __align__(16) float lds[];
     const int tid = threadIdx.x;
     const int row0 = blockIdx.x * RB, rows = min(RB, A.n - row0), n = A.n;
@@ -307,9 +323,18 @@ struct WgradArgs {
     int n;
     float *grad;
     int jobs[2][NL + 1];   // prefix sums of the per-layer job counts, per network
+    static constexpr bool gated = false;
 };
-__global__ __launch_bounds__(FT) void ppo_wgrad_kernel(WgradArgs A)
+struct WgradArgsGated : WgradArgs {
+    const int32_t *stop;
+    static constexpr bool gated = true;
+};
+template <class ARGS>
+__global__ __launch_bounds__(FT) void ppo_wgrad_kernel(ARGS A)
 {
+    if constexpr (ARGS::gated) {
+        if (*A.stop) return;
+    }
     __shared__ float part[4][256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int job = blockIdx.x, net = 0;
@@ -377,8 +402,8 @@ __device__ __forceinline__ float block_sum(float v, float *red)
     return red[0];
 }
 
-__global__ __launch_bounds__(FT) void ppo_mb_final_kernel(const float *part, int nblocks, int n, uint32_t ls_off, PpoHp hp,
-                                                          const float *params, float *grad, float *stats)
+__device__ __forceinline__ void ppo_mb_final_body(const float *part, int nblocks, int n, uint32_t ls_off, const PpoHp &hp,
+                                                  const float *params, float *grad, float *stats)
 {
     __shared__ float red[FT];
     float tot[5];
@@ -402,9 +427,33 @@ __global__ __launch_bounds__(FT) void ppo_mb_final_kernel(const float *part, int
         stats[3] = 0.0f;
     }
 }
+__global__ __launch_bounds__(FT) void ppo_mb_final_kernel(const float *part, int nblocks, int n, uint32_t ls_off, PpoHp hp,
+                                                          const float *params, float *grad, float *stats)
+{
+    ppo_mb_final_body(part, nblocks, n, ls_off, hp, params, grad, stats);
+}
+// One workgroup: every thread reads the stop word on entry; thread 0 records the KL it has just written and may set the word,
+// behind the barriers of the sums, so the write follows every read of this launch.
+__global__ __launch_bounds__(FT) void ppo_mb_final_gated_kernel(const float *part, int nblocks, int n, uint32_t ls_off, PpoHp hp,
+                                                                const float *params, float *grad, float *stats, float kl_stop,
+                                                                rover_ppo_epoch *ep)
+{
+    if (ep->stop) return;
+    ppo_mb_final_body(part, nblocks, n, ls_off, hp, params, grad, stats);
+    if (threadIdx.x == 0) {
+        const float kl = stats[0];
+        const int32_t rec = ep->recorded;
+        ep->recorded = rec + 1;
+        if (kl_stop > 0.0f && kl > kl_stop) {     // strict, fp32: false for a NaN KL
+            ep->stop = 1;
+            ep->stop_minibatch = rec;
+            ep->stop_kl = kl;
+        }
+    }
+}
 
 // ---- clip_grad_norm_ + Adam
-__global__ __launch_bounds__(FT) void ppo_sumsq_kernel(const float *grad, int P, float *part)
+__device__ __forceinline__ void ppo_sumsq_body(const float *grad, int P, float *part)
 {
     __shared__ float red[FT];
     const int chunk = cdiv(P, NORM_BLOCKS), e0 = blockIdx.x * chunk, e1 = min(e0 + chunk, P);
@@ -413,8 +462,13 @@ __global__ __launch_bounds__(FT) void ppo_sumsq_kernel(const float *grad, int P,
     const float tot = block_sum(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
-__global__ __launch_bounds__(FT) void ppo_adam_prep_kernel(const float *part, float max_norm, float beta1, float beta2,
-                                                           rover_ppo_state *st)
+__global__ __launch_bounds__(FT) void ppo_sumsq_kernel(const float *grad, int P, float *part) { ppo_sumsq_body(grad, P, part); }
+__global__ __launch_bounds__(FT) void ppo_sumsq_gated_kernel(const float *grad, int P, float *part, const int32_t *stop)
+{
+    if (*stop) return;
+    ppo_sumsq_body(grad, P, part);
+}
+__device__ __forceinline__ void ppo_adam_prep_body(const float *part, float max_norm, float beta1, float beta2, rover_ppo_state *st)
 {
     __shared__ float red[FT];
     const float tot = block_sum((int)threadIdx.x < NORM_BLOCKS ? part[threadIdx.x] : 0.0f, red);
@@ -429,9 +483,20 @@ __global__ __launch_bounds__(FT) void ppo_adam_prep_kernel(const float *part, fl
         st->bc2_sqrt = (float)sqrt(bc2);
     }
 }
-__global__ __launch_bounds__(FT) void ppo_adam_kernel(float *params, float *grad, float *m, float *v, const rover_ppo_state *st,
-                                                      int P, float beta1, float beta2, float eps, float *rep_a, float *rep_b,
-                                                      uint32_t Pa, uint32_t Pb, int n_copies)
+__global__ __launch_bounds__(FT) void ppo_adam_prep_kernel(const float *part, float max_norm, float beta1, float beta2,
+                                                           rover_ppo_state *st)
+{
+    ppo_adam_prep_body(part, max_norm, beta1, beta2, st);
+}
+__global__ __launch_bounds__(FT) void ppo_adam_prep_gated_kernel(const float *part, float max_norm, float beta1, float beta2,
+                                                                 rover_ppo_state *st, const int32_t *stop)
+{
+    if (*stop) return;
+    ppo_adam_prep_body(part, max_norm, beta1, beta2, st);
+}
+__device__ __forceinline__ void ppo_adam_body(float *params, float *grad, float *m, float *v, const rover_ppo_state *st, int P,
+                                              float beta1, float beta2, float eps, float *rep_a, float *rep_b, uint32_t Pa,
+                                              uint32_t Pb, int n_copies)
 {
     const int e = blockIdx.x * FT + threadIdx.x;
     if (e >= P) return;
@@ -453,6 +518,19 @@ __global__ __launch_bounds__(FT) void ppo_adam_kernel(float *params, float *grad
             for (int c = 0; c < n_copies; ++c) rep_b[(size_t)c * Pb + (e - Pa)] = p;
     }
 }
+__global__ __launch_bounds__(FT) void ppo_adam_kernel(float *params, float *grad, float *m, float *v, const rover_ppo_state *st,
+                                                      int P, float beta1, float beta2, float eps, float *rep_a, float *rep_b,
+                                                      uint32_t Pa, uint32_t Pb, int n_copies)
+{
+    ppo_adam_body(params, grad, m, v, st, P, beta1, beta2, eps, rep_a, rep_b, Pa, Pb, n_copies);
+}
+__global__ __launch_bounds__(FT) void ppo_adam_gated_kernel(float *params, float *grad, float *m, float *v, const rover_ppo_state *st,
+                                                            int P, float beta1, float beta2, float eps, float *rep_a, float *rep_b,
+                                                            uint32_t Pa, uint32_t Pb, int n_copies, const int32_t *stop)
+{
+    if (*stop) return;
+    ppo_adam_body(params, grad, m, v, st, P, beta1, beta2, eps, rep_a, rep_b, Pa, Pb, n_copies);
+}
 
 __global__ void ppo_kl_kernel(const float *stats, int nmb, float thr, float factor, float lr_min, float lr_max,
                               rover_ppo_state *st, float *kl_out)
@@ -465,6 +543,35 @@ __global__ void ppo_kl_kernel(const float *stats, int nmb, float thr, float fact
     else if ((double)kl < 0.5 * (double)thr) lr = fmin(lr * (double)factor, (double)lr_max);
     st->lr = lr;
     if (kl_out) *kl_out = kl;
+}
+
+// one thread: the mean of the recorded KLs, the scheduler when it is switched on, and the epoch's bookkeeping
+__global__ void ppo_epoch_end_kernel(const float *stats, int nmb, float thr, float factor, float lr_min, float lr_max,
+                                     rover_ppo_state *st, rover_ppo_epoch *ep, int schedule, float *kl_out)
+{
+    const int rec = min(max(ep->recorded, 0), nmb);
+    float kl = 0.0f;
+    if (rec > 0) {
+        float s = 0.0f;
+        for (int i = 0; i < rec; ++i) s += stats[4 * i];
+        kl = s / (float)rec;
+        if (schedule) {
+            double lr = st->lr;
+            if ((double)kl > 2.0 * (double)thr) lr = fmax(lr / (double)factor, (double)lr_min);
+            else if ((double)kl < 0.5 * (double)thr) lr = fmin(lr * (double)factor, (double)lr_max);
+            st->lr = lr;
+        }
+    }
+    if (kl_out) *kl_out = kl;
+    const int32_t stopped = ep->stopped_epochs + (ep->stop != 0);
+    ep->epochs += 1;
+    ep->stopped_epochs = stopped;
+    if (stopped == 0) {
+        ep->stop_minibatch = -1;
+        ep->stop_kl = 0.0f;
+    }
+    ep->stop = 0;
+    ep->recorded = 0;
 }
 
 __global__ __launch_bounds__(FT) void ppo_gae_kernel(const float *rew, const float *done, const float *val, const float *last_v, int T,
@@ -580,10 +687,15 @@ size_t rover_ppo_param_floats(const rover_policy_desc *policy, const rover_polic
 }
 size_t rover_ppo_workspace_bytes(int32_t max_rows) { return max_rows > 0 ? sizeof(float) * ws_floats(max_rows) : 0; }
 
-int rover_ppo_minibatch(const rover_policy_desc *policy, const rover_policy_desc *value, const rover_ppo_hparams *h,
-                        const float *params, const float *obs, const float *act, const float *logp, const float *val,
-                        const float *ret, const float *adv, const int64_t *idx, int32_t n, void *ws, size_t ws_bytes,
-                        float *grad, float *stats, float *mean_out, float *value_out, void *stream)
+}  // extern "C"
+
+namespace {
+
+// rover_ppo_minibatch (ep == NULL: the ungated kernels, the launches as they always were) and rover_ppo_minibatch_gated
+int minibatch_impl(const rover_policy_desc *policy, const rover_policy_desc *value, const rover_ppo_hparams *h, const float *params,
+                   const float *obs, const float *act, const float *logp, const float *val, const float *ret, const float *adv,
+                   const int64_t *idx, int32_t n, void *ws, size_t ws_bytes, float *grad, float *stats, float *mean_out,
+                   float *value_out, float kl_stop, rover_ppo_epoch *ep, void *stream)
 {
     if (int rc = check_pair(policy, value)) return rc;
     if (!h || !params || !obs || !act || !logp || !val || !ret || !adv || !idx || !ws || !grad || !stats)
@@ -596,7 +708,8 @@ int rover_ppo_minibatch(const rover_policy_desc *policy, const rover_policy_desc
     if (int rc = device_of(params, &dev)) return rc;
     DeviceGuard guard(dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RowsArgs R;
+    RowsArgsGated R;
+    R.stop = ep ? &ep->stop : nullptr;
     R.nets = nets_of(policy, value);
     R.hp = {h->clip_ratio, h->value_clip, h->value_loss_scale, h->log_std_min, h->log_std_max};
     R.params = params; R.obs = obs; R.act = act; R.logp = logp; R.val = val; R.ret = ret; R.adv = adv; R.idx = idx; R.n = n;
@@ -604,12 +717,15 @@ int rover_ppo_minibatch(const rover_policy_desc *policy, const rover_policy_desc
     R.part = R.ws + (size_t)2 * S_ROW * n;
     R.mean_out = mean_out; R.value_out = value_out;
     const int nblk = cdiv(n, RB);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ppo_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       ROWS_LDS_BYTES);
+    hipError_t e = hipFuncSetAttribute(ep ? reinterpret_cast<const void *>(ppo_rows_kernel<RowsArgsGated>)
+                                          : reinterpret_cast<const void *>(ppo_rows_kernel<RowsArgs>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES);
     if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(ppo_rows_kernel, dim3(nblk), dim3(FT), ROWS_LDS_BYTES, s, R);
+    if (ep) hipLaunchKernelGGL(ppo_rows_kernel<RowsArgsGated>, dim3(nblk), dim3(FT), ROWS_LDS_BYTES, s, R);
+    else hipLaunchKernelGGL(ppo_rows_kernel<RowsArgs>, dim3(nblk), dim3(FT), ROWS_LDS_BYTES, s, static_cast<const RowsArgs &>(R));
     if (int rc = launched("ppo_rows_kernel launch: %s")) return rc;
-    WgradArgs W;
+    WgradArgsGated W;
+    W.stop = R.stop;
     W.nets = R.nets; W.obs = obs; W.idx = idx; W.ws = R.ws; W.n = n; W.grad = grad;
     for (int k = 0; k < 2; ++k) {
         W.jobs[k][0] = 0;
@@ -618,16 +734,22 @@ int rover_ppo_minibatch(const rover_policy_desc *policy, const rover_policy_desc
             W.jobs[k][l + 1] = W.jobs[k][l] + cdiv(N, 16) * (cdiv(LK[l], 16) + 1);
         }
     }
-    hipLaunchKernelGGL(ppo_wgrad_kernel, dim3(W.jobs[0][NL] + W.jobs[1][NL]), dim3(FT), 0, s, W);
+    if (ep) hipLaunchKernelGGL(ppo_wgrad_kernel<WgradArgsGated>, dim3(W.jobs[0][NL] + W.jobs[1][NL]), dim3(FT), 0, s, W);
+    else hipLaunchKernelGGL(ppo_wgrad_kernel<WgradArgs>, dim3(W.jobs[0][NL] + W.jobs[1][NL]), dim3(FT), 0, s, static_cast<const WgradArgs &>(W));
     if (int rc = launched("ppo_wgrad_kernel launch: %s")) return rc;
-    hipLaunchKernelGGL(ppo_mb_final_kernel, dim3(1), dim3(FT), 0, s, (const float *)R.part, nblk, (int)n, R.nets.ls_off, R.hp,
-                       params, grad, stats);
+    if (ep)
+        hipLaunchKernelGGL(ppo_mb_final_gated_kernel, dim3(1), dim3(FT), 0, s, (const float *)R.part, nblk, (int)n, R.nets.ls_off, R.hp,
+                           params, grad, stats, kl_stop, ep);
+    else
+        hipLaunchKernelGGL(ppo_mb_final_kernel, dim3(1), dim3(FT), 0, s, (const float *)R.part, nblk, (int)n, R.nets.ls_off, R.hp,
+                           params, grad, stats);
     return launched("ppo_mb_final_kernel launch: %s");
 }
 
-int rover_ppo_apply(const rover_policy_desc *policy, const rover_policy_desc *value, const rover_ppo_hparams *h, float *params,
-                    float *grad, float *adam_m, float *adam_v, void *state, float *replicas_policy, float *replicas_value,
-                    int32_t n_copies, void *ws, size_t ws_bytes, void *stream)
+// rover_ppo_apply (ep == NULL) and rover_ppo_apply_gated
+int apply_impl(const rover_policy_desc *policy, const rover_policy_desc *value, const rover_ppo_hparams *h, float *params, float *grad,
+               float *adam_m, float *adam_v, void *state, float *replicas_policy, float *replicas_value, int32_t n_copies, void *ws,
+               size_t ws_bytes, const rover_ppo_epoch *ep, void *stream)
 {
     if (int rc = check_pair(policy, value)) return rc;
     if (!h || !params || !grad || !adam_m || !adam_v || !state || !ws) return rover_internal_fail(ROVER_ERR_INVALID, "NULL argument");
@@ -642,14 +764,87 @@ int rover_ppo_apply(const rover_policy_desc *policy, const rover_policy_desc *va
     const int P = (int)(nets.ls_off + 4);
     float *part = static_cast<float *>(ws);
     rover_ppo_state *st = static_cast<rover_ppo_state *>(state);
-    hipLaunchKernelGGL(ppo_sumsq_kernel, dim3(NORM_BLOCKS), dim3(FT), 0, s, (const float *)grad, P, part);
+    const int32_t *stop = ep ? &ep->stop : nullptr;
+    if (ep) hipLaunchKernelGGL(ppo_sumsq_gated_kernel, dim3(NORM_BLOCKS), dim3(FT), 0, s, (const float *)grad, P, part, stop);
+    else hipLaunchKernelGGL(ppo_sumsq_kernel, dim3(NORM_BLOCKS), dim3(FT), 0, s, (const float *)grad, P, part);
     if (int rc = launched("ppo_sumsq_kernel launch: %s")) return rc;
-    hipLaunchKernelGGL(ppo_adam_prep_kernel, dim3(1), dim3(FT), 0, s, (const float *)part, h->max_grad_norm, h->beta1, h->beta2, st);
+    if (ep)
+        hipLaunchKernelGGL(ppo_adam_prep_gated_kernel, dim3(1), dim3(FT), 0, s, (const float *)part, h->max_grad_norm, h->beta1, h->beta2,
+                           st, stop);
+    else
+        hipLaunchKernelGGL(ppo_adam_prep_kernel, dim3(1), dim3(FT), 0, s, (const float *)part, h->max_grad_norm, h->beta1, h->beta2, st);
     if (int rc = launched("ppo_adam_prep_kernel launch: %s")) return rc;
-    hipLaunchKernelGGL(ppo_adam_kernel, dim3(cdiv(P, FT)), dim3(FT), 0, s, params, grad, adam_m, adam_v, (const rover_ppo_state *)st, P,
-                       h->beta1, h->beta2, h->eps, replicas_policy, replicas_value, nets.net_floats[0], nets.net_floats[1],
-                       (int)n_copies);
+    if (ep)
+        hipLaunchKernelGGL(ppo_adam_gated_kernel, dim3(cdiv(P, FT)), dim3(FT), 0, s, params, grad, adam_m, adam_v,
+                           (const rover_ppo_state *)st, P, h->beta1, h->beta2, h->eps, replicas_policy, replicas_value,
+                           nets.net_floats[0], nets.net_floats[1], (int)n_copies, stop);
+    else
+        hipLaunchKernelGGL(ppo_adam_kernel, dim3(cdiv(P, FT)), dim3(FT), 0, s, params, grad, adam_m, adam_v, (const rover_ppo_state *)st,
+                           P, h->beta1, h->beta2, h->eps, replicas_policy, replicas_value, nets.net_floats[0], nets.net_floats[1],
+                           (int)n_copies);
     return launched("ppo_adam_kernel launch: %s");
+}
+
+}  // namespace
+
+extern "C" {
+
+int rover_ppo_minibatch(const rover_policy_desc *policy, const rover_policy_desc *value, const rover_ppo_hparams *h,
+                        const float *params, const float *obs, const float *act, const float *logp, const float *val,
+                        const float *ret, const float *adv, const int64_t *idx, int32_t n, void *ws, size_t ws_bytes,
+                        float *grad, float *stats, float *mean_out, float *value_out, void *stream)
+{
+    return minibatch_impl(policy, value, h, params, obs, act, logp, val, ret, adv, idx, n, ws, ws_bytes, grad, stats, mean_out,
+                          value_out, 0.0f, nullptr, stream);
+}
+
+int rover_ppo_apply(const rover_policy_desc *policy, const rover_policy_desc *value, const rover_ppo_hparams *h, float *params,
+                    float *grad, float *adam_m, float *adam_v, void *state, float *replicas_policy, float *replicas_value,
+                    int32_t n_copies, void *ws, size_t ws_bytes, void *stream)
+{
+    return apply_impl(policy, value, h, params, grad, adam_m, adam_v, state, replicas_policy, replicas_value, n_copies, ws, ws_bytes,
+                      nullptr, stream);
+}
+
+size_t rover_ppo_epoch_bytes(void) { return sizeof(rover_ppo_epoch); }
+
+int rover_ppo_minibatch_gated(const rover_policy_desc *policy, const rover_policy_desc *value, const rover_ppo_hparams *h,
+                              const float *params, const float *obs, const float *act, const float *logp, const float *val,
+                              const float *ret, const float *adv, const int64_t *idx, int32_t n, void *ws, size_t ws_bytes,
+                              float *grad, float *stats, float *mean_out, float *value_out, float kl_early_stop, void *epoch,
+                              void *stream)
+{
+    if (!epoch) return rover_internal_fail(ROVER_ERR_INVALID, "rover_ppo_minibatch_gated: epoch is NULL");
+    if (reinterpret_cast<uintptr_t>(epoch) & 7) return rover_internal_fail(ROVER_ERR_INVALID, "epoch must be 8-byte aligned");
+    return minibatch_impl(policy, value, h, params, obs, act, logp, val, ret, adv, idx, n, ws, ws_bytes, grad, stats, mean_out,
+                          value_out, kl_early_stop, static_cast<rover_ppo_epoch *>(epoch), stream);
+}
+
+int rover_ppo_apply_gated(const rover_policy_desc *policy, const rover_policy_desc *value, const rover_ppo_hparams *h,
+                          float *params, float *grad, float *adam_m, float *adam_v, void *state, float *replicas_policy,
+                          float *replicas_value, int32_t n_copies, void *ws, size_t ws_bytes, const void *epoch, void *stream)
+{
+    if (!epoch) return rover_internal_fail(ROVER_ERR_INVALID, "rover_ppo_apply_gated: epoch is NULL");
+    if (reinterpret_cast<uintptr_t>(epoch) & 7) return rover_internal_fail(ROVER_ERR_INVALID, "epoch must be 8-byte aligned");
+    return apply_impl(policy, value, h, params, grad, adam_m, adam_v, state, replicas_policy, replicas_value, n_copies, ws, ws_bytes,
+                      static_cast<const rover_ppo_epoch *>(epoch), stream);
+}
+
+int rover_ppo_epoch_end(const rover_ppo_hparams *h, const float *stats, int32_t n_minibatches, void *state, void *epoch,
+                        int32_t schedule, float *kl_out, void *stream)
+{
+    if (!h || !stats || !state || !epoch) return rover_internal_fail(ROVER_ERR_INVALID, "rover_ppo_epoch_end: NULL argument");
+    if (n_minibatches < 1) return rover_internal_fail(ROVER_ERR_INVALID, "n_minibatches must be >= 1");
+    if (schedule != 0 && schedule != 1) return rover_internal_fail(ROVER_ERR_INVALID, "schedule must be 0 or 1");
+    if ((reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(epoch)) & 7)
+        return rover_internal_fail(ROVER_ERR_INVALID, "state and epoch must be 8-byte aligned");
+    int dev;
+    if (int rc = device_of(stats, &dev)) return rc;
+    DeviceGuard guard(dev);
+    hipLaunchKernelGGL(ppo_epoch_end_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), stats, (int)n_minibatches,
+                       h->kl_threshold, h->lr_factor, h->lr_min, h->lr_max, static_cast<rover_ppo_state *>(state),
+                       static_cast<rover_ppo_epoch *>(epoch), (int)schedule, kl_out);
+    return launched("ppo_epoch_end_kernel launch: %s");
 }
 
 int rover_ppo_gae(const rover_ppo_hparams *h, const float *rew, const float *done, const float *val, const float *last_v,

@@ -449,6 +449,21 @@ __global__ __launch_bounds__(256) void rover_rollout_record_kernel(const float *
     done_out[i] = (terminated[i] | truncated[i]) ? 1.0f : 0.0f;
 }
 
+// reward shaping and skrl's time-limit bootstrap in the record launch; every product and sum is formed (no contraction)
+__global__ __launch_bounds__(256) void rover_rollout_record_shaped_kernel(const float *__restrict__ rew, const uint8_t *__restrict__ terminated,
+                                                                          const uint8_t *__restrict__ truncated, const float *__restrict__ val,
+                                                                          int n, float scale, float discount, int bootstrap,
+                                                                          float *__restrict__ rew_out, float *__restrict__ done_out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t tr = truncated[i];
+    float r = __fmul_rn(rew[i], scale);
+    if (bootstrap) r = __fadd_rn(r, __fmul_rn(__fmul_rn(discount, val[i]), tr ? 1.0f : 0.0f));
+    rew_out[i] = r;
+    done_out[i] = (terminated[i] | tr) ? 1.0f : 0.0f;
+}
+
 // the shapes the kernel is written for (rover_policy_default_desc)
 bool is_reference_architecture(const rover_policy_desc *d)
 {
@@ -537,6 +552,25 @@ int rover_rollout_record(const float *rew, const uint8_t *terminated, const uint
                        terminated, truncated, n, rew_out, done_out);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, "rover_rollout_record_kernel launch: %s", hipGetErrorString(e));
+    return ROVER_OK;
+}
+
+int rover_rollout_record_shaped(const float *rew, const uint8_t *terminated, const uint8_t *truncated, const float *val, int32_t n,
+                                float reward_scale, float discount, int32_t time_limit_bootstrap, float *rew_out, float *done_out,
+                                void *stream)
+{
+    if (!rew || !terminated || !truncated || !rew_out || !done_out)
+        return rover_internal_fail(ROVER_ERR_INVALID, "rover_rollout_record_shaped: NULL pointer");
+    if (time_limit_bootstrap && !val)
+        return rover_internal_fail(ROVER_ERR_INVALID, "rover_rollout_record_shaped: val is NULL with time_limit_bootstrap");
+    if (n < 1) return rover_internal_fail(ROVER_ERR_INVALID, "rover_rollout_record_shaped: n must be >= 1");
+    if ((reinterpret_cast<uintptr_t>(rew) | reinterpret_cast<uintptr_t>(val) | reinterpret_cast<uintptr_t>(rew_out) |
+         reinterpret_cast<uintptr_t>(done_out)) & 3)
+        return rover_internal_fail(ROVER_ERR_INVALID, "rover_rollout_record_shaped: float arrays must be 4-byte aligned");
+    hipLaunchKernelGGL(rover_rollout_record_shaped_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), rew,
+                       terminated, truncated, val, n, reward_scale, discount, time_limit_bootstrap != 0, rew_out, done_out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, "rover_rollout_record_shaped_kernel launch: %s", hipGetErrorString(e));
     return ROVER_OK;
 }
 

@@ -10,6 +10,8 @@
 //   scaler_apply_kernel                   forward / inverse (+ nan_to_num, + the raw copy) over rows or over rows named by idx:
 //                                         a wave per span (one row with idx, 1024 consecutive floats without), moved as a scalar
 //                                         head, 16-byte vectors and a scalar tail where the three arrays share their alignment.
+// The statistics kernels have *_gated_kernel twins (rover_scaler_train_gated): the same device function behind one load of a gate
+// word that no kernel here writes.
 // The launch boundary is the only synchronisation between workgroups: no flags, no fences, no atomics.
 #include <hip/hip_runtime.h>
 
@@ -37,8 +39,7 @@ __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ---- statistics
 template <bool DEV>
-__global__ __launch_bounds__(TT) void scaler_partial_kernel(const float *x, const int64_t *idx, int rows, int width, const double *mean,
-                                                            double *part)
+__device__ __forceinline__ void scaler_partial_body(const float *x, const int64_t *idx, int rows, int width, const double *mean, double *part)
 {
     __shared__ double red[TT / 64][CB];
     const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
@@ -61,8 +62,21 @@ __global__ __launch_bounds__(TT) void scaler_partial_kernel(const float *x, cons
     __syncthreads();
     if (q == 0 && c < width) part[(size_t)blockIdx.x * width + c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
 }
+template <bool DEV>
+__global__ __launch_bounds__(TT) void scaler_partial_kernel(const float *x, const int64_t *idx, int rows, int width, const double *mean,
+                                                            double *part)
+{
+    scaler_partial_body<DEV>(x, idx, rows, width, mean, part);
+}
+template <bool DEV>
+__global__ __launch_bounds__(TT) void scaler_partial_gated_kernel(const float *x, const int64_t *idx, int rows, int width,
+                                                                  const double *mean, double *part, const int32_t *gate)
+{
+    if (*gate) return;
+    scaler_partial_body<DEV>(x, idx, rows, width, mean, part);
+}
 
-__global__ __launch_bounds__(TT) void scaler_mean_kernel(const double *part, int n_chunks, int rows, int width, double *mean)
+__device__ __forceinline__ void scaler_mean_body(const double *part, int n_chunks, int rows, int width, double *mean)
 {
     const int c = blockIdx.x * TT + threadIdx.x;
     if (c >= width) return;
@@ -70,9 +84,18 @@ __global__ __launch_bounds__(TT) void scaler_mean_kernel(const double *part, int
     for (int k = 0; k < n_chunks; ++k) s += part[(size_t)k * width + c];
     mean[c] = s / (double)rows;
 }
+__global__ __launch_bounds__(TT) void scaler_mean_kernel(const double *part, int n_chunks, int rows, int width, double *mean)
+{
+    scaler_mean_body(part, n_chunks, rows, width, mean);
+}
+__global__ __launch_bounds__(TT) void scaler_mean_gated_kernel(const double *part, int n_chunks, int rows, int width, double *mean,
+                                                               const int32_t *gate)
+{
+    if (*gate) return;
+    scaler_mean_body(part, n_chunks, rows, width, mean);
+}
 
-__global__ __launch_bounds__(MAX_W) void scaler_merge_kernel(double *scaler, int width, int rows, const double *bmean, const double *part,
-                                                             int n_chunks)
+__device__ __forceinline__ void scaler_merge_body(double *scaler, int width, int rows, const double *bmean, const double *part, int n_chunks)
 {
     const int c = threadIdx.x;
     double *mean = scaler, *var = scaler + width;
@@ -88,6 +111,17 @@ __global__ __launch_bounds__(MAX_W) void scaler_merge_kernel(double *scaler, int
     }
     __syncthreads();   // every column has read the old count
     if (c == 0) scaler[2 * width] = tot;
+}
+__global__ __launch_bounds__(MAX_W) void scaler_merge_kernel(double *scaler, int width, int rows, const double *bmean, const double *part,
+                                                             int n_chunks)
+{
+    scaler_merge_body(scaler, width, rows, bmean, part, n_chunks);
+}
+__global__ __launch_bounds__(MAX_W) void scaler_merge_gated_kernel(double *scaler, int width, int rows, const double *bmean,
+                                                                   const double *part, int n_chunks, const int32_t *gate)
+{
+    if (*gate) return;
+    scaler_merge_body(scaler, width, rows, bmean, part, n_chunks);
 }
 
 // ---- transform
@@ -201,8 +235,13 @@ size_t rover_scaler_workspace_bytes(int32_t width, int32_t max_rows)
     return width_ok(width) && max_rows >= 2 ? sizeof(double) * ws_doubles(width, max_rows) : 0;
 }
 
-int rover_scaler_train(const rover_scaler_hparams *h, double *scaler, int32_t width, const float *x, const int64_t *idx, int32_t rows,
-                       void *ws, size_t ws_bytes, void *stream)
+}  // extern "C"
+
+namespace {
+
+// rover_scaler_train (gate == NULL: the ungated kernels, the launches as they always were) and rover_scaler_train_gated
+int train_impl(const rover_scaler_hparams *h, double *scaler, int32_t width, const float *x, const int64_t *idx, int32_t rows, void *ws,
+               size_t ws_bytes, const int32_t *gate, void *stream)
 {
     if (!h || !scaler || !x || !ws) return rover_internal_fail(ROVER_ERR_INVALID, "rover_scaler_train: NULL argument");
     if (!width_ok(width)) return rover_internal_fail(ROVER_ERR_INVALID, "rover_scaler_train: width must be in [1, 1024]");
@@ -219,6 +258,20 @@ int rover_scaler_train(const rover_scaler_hparams *h, double *scaler, int32_t wi
     double *bmean = static_cast<double *>(ws), *part = bmean + width;
     const int n_chunks = cdiv(rows, CH);
     const dim3 grid((unsigned)n_chunks, (unsigned)cdiv(width, CB));
+    if (gate) {
+        hipLaunchKernelGGL(scaler_partial_gated_kernel<false>, grid, dim3(TT), 0, s, x, idx, (int)rows, (int)width, (const double *)nullptr,
+                           part, gate);
+        if (int rc = launched("scaler_partial_kernel launch: %s")) return rc;
+        hipLaunchKernelGGL(scaler_mean_gated_kernel, dim3(cdiv(width, TT)), dim3(TT), 0, s, (const double *)part, n_chunks, (int)rows,
+                           (int)width, bmean, gate);
+        if (int rc = launched("scaler_mean_kernel launch: %s")) return rc;
+        hipLaunchKernelGGL(scaler_partial_gated_kernel<true>, grid, dim3(TT), 0, s, x, idx, (int)rows, (int)width, (const double *)bmean,
+                           part, gate);
+        if (int rc = launched("scaler_partial_kernel launch: %s")) return rc;
+        hipLaunchKernelGGL(scaler_merge_gated_kernel, dim3(1), dim3(MAX_W), 0, s, scaler, (int)width, (int)rows, (const double *)bmean,
+                           (const double *)part, n_chunks, gate);
+        return launched("scaler_merge_kernel launch: %s");
+    }
     hipLaunchKernelGGL(scaler_partial_kernel<false>, grid, dim3(TT), 0, s, x, idx, (int)rows, (int)width, (const double *)nullptr, part);
     if (int rc = launched("scaler_partial_kernel launch: %s")) return rc;
     hipLaunchKernelGGL(scaler_mean_kernel, dim3(cdiv(width, TT)), dim3(TT), 0, s, (const double *)part, n_chunks, (int)rows, (int)width,
@@ -229,6 +282,24 @@ int rover_scaler_train(const rover_scaler_hparams *h, double *scaler, int32_t wi
     hipLaunchKernelGGL(scaler_merge_kernel, dim3(1), dim3(MAX_W), 0, s, scaler, (int)width, (int)rows, (const double *)bmean,
                        (const double *)part, n_chunks);
     return launched("scaler_merge_kernel launch: %s");
+}
+
+}  // namespace
+
+extern "C" {
+
+int rover_scaler_train(const rover_scaler_hparams *h, double *scaler, int32_t width, const float *x, const int64_t *idx, int32_t rows,
+                       void *ws, size_t ws_bytes, void *stream)
+{
+    return train_impl(h, scaler, width, x, idx, rows, ws, ws_bytes, nullptr, stream);
+}
+
+int rover_scaler_train_gated(const rover_scaler_hparams *h, double *scaler, int32_t width, const float *x, const int64_t *idx,
+                             int32_t rows, void *ws, size_t ws_bytes, const int32_t *gate, void *stream)
+{
+    if (!gate) return rover_internal_fail(ROVER_ERR_INVALID, "rover_scaler_train_gated: gate is NULL");
+    if (reinterpret_cast<uintptr_t>(gate) & 3) return rover_internal_fail(ROVER_ERR_INVALID, "rover_scaler_train_gated: gate must be 4-byte aligned");
+    return train_impl(h, scaler, width, x, idx, rows, ws, ws_bytes, gate, stream);
 }
 
 int rover_scaler_apply(const rover_scaler_hparams *h, const double *scaler, int32_t width, const float *x, const int64_t *idx,

@@ -5,6 +5,11 @@ vector in the packed layout the forward kernels read, with Adam's moments beside
 does with torch autograd: GAE, then epochs of shuffled minibatches of the clipped PPO loss, ``clip_grad_norm_`` and Adam, with
 the KL-adaptive learning rate after each epoch.  ``.actor`` / ``.critic`` alias the trainer's parameters (replicas refreshed by
 every optimiser step), so a rollout needs no re-packing.  No CPU fallback.
+
+``update(kl_early_stop=0.008, scheduler=None)`` is rover_ppo.yaml as skrl 1.1 reads it (``include/rover_train_gate.h``): an epoch
+stops at the first minibatch whose KL exceeds the threshold, before that minibatch's optimiser step, and no scheduler touches the
+learning rate.  The stop is one word of device memory that the kernels set and obey; the host still synchronises once.
+``ppo_skrl.TorchSkrlPPO`` is the specification.
 """
 from __future__ import annotations
 
@@ -106,6 +111,8 @@ class FusedPPO:
         self.adam_v = torch.zeros_like(self.params)
         self.state = torch.zeros(4, dtype=torch.float64, device=self.device)   # struct rover_ppo_state (32 bytes)
         self.state[0] = float(lr)
+        self.epoch_state = torch.zeros(8, dtype=torch.int32, device=self.device)    # struct rover_ppo_epoch (32 bytes), zeroed
+        self.last_update = None                                                 # per-epoch {"recorded", "stopped"} of a gated update
         self.rep_p = self.params[:self.n_p].repeat(self.n_copies)
         self.rep_v = self.params[self.n_p:self.n_p + self.n_v].repeat(self.n_copies)
         self.actor = RoverNet.from_packed(self.desc_p, self.rep_p, self.n_copies)
@@ -187,6 +194,54 @@ class FusedPPO:
                                              self.rep_p.data_ptr(), self.rep_v.data_ptr(), self.n_copies, self.ws.data_ptr(),
                                              self.ws.numel(), self._stream()), "rover_ppo_apply")
 
+    def minibatch_gated(self, obs, act, logp, val, ret, adv, idx, stats, kl_early_stop: float = 0.0, mean_out=None, value_out=None):
+        """``minibatch`` behind ``epoch_state``'s stop word (``rover_ppo_minibatch_gated``): nothing is written once it is set;
+        otherwise the KL is recorded and sets the word where it exceeds ``kl_early_stop`` (> 0)."""
+        self._check(idx, "idx", torch.int64)
+        n = int(idx.numel())
+        self._ensure_ws(max(n, 1))
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        _lib.check(self._lib.rover_ppo_minibatch_gated(C.byref(self.desc_p), C.byref(self.desc_v), C.byref(self.hp),
+                                                       self.params.data_ptr(), obs.data_ptr(), act.data_ptr(), logp.data_ptr(),
+                                                       val.data_ptr(), ret.data_ptr(), adv.data_ptr(), idx.data_ptr(), n,
+                                                       self.ws.data_ptr(), self.ws.numel(), self.grad.data_ptr(), stats.data_ptr(),
+                                                       ptr(mean_out), ptr(value_out), float(kl_early_stop),
+                                                       self.epoch_state.data_ptr(), self._stream()), "rover_ppo_minibatch_gated")
+        return stats
+
+    def apply_gated(self):
+        """``apply`` behind the stop word: no step, nothing written, once it is set (``rover_ppo_apply_gated``)."""
+        _lib.check(self._lib.rover_ppo_apply_gated(C.byref(self.desc_p), C.byref(self.desc_v), C.byref(self.hp), self.params.data_ptr(),
+                                                   self.grad.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
+                                                   self.state.data_ptr(), self.rep_p.data_ptr(), self.rep_v.data_ptr(), self.n_copies,
+                                                   self.ws.data_ptr(), self.ws.numel(), self.epoch_state.data_ptr(), self._stream()),
+                   "rover_ppo_apply_gated")
+
+    def epoch_end(self, stats: torch.Tensor, schedule: bool, kl_out: torch.Tensor | None = None):
+        """Closes a gated epoch on the device: the mean of the recorded KLs into ``kl_out``, the KL-adaptive rate when ``schedule``,
+        and the stop word cleared (``rover_ppo_epoch_end``)."""
+        self._check(stats, "stats")
+        _lib.check(self._lib.rover_ppo_epoch_end(C.byref(self.hp), stats.data_ptr(), int(stats.shape[0]), self.state.data_ptr(),
+                                                 self.epoch_state.data_ptr(), int(bool(schedule)),
+                                                 None if kl_out is None else kl_out.data_ptr(), self._stream()), "rover_ppo_epoch_end")
+
+    @staticmethod
+    def _gated(kl_early_stop: float, scheduler) -> bool:
+        """Whether ``update`` takes the gated entries; the defaults (0, "kl_adaptive") keep the ungated launch sequence."""
+        if scheduler not in (None, "kl_adaptive"):
+            raise ValueError('scheduler must be None or "kl_adaptive"')
+        if not float(kl_early_stop) >= 0.0:
+            raise ValueError("kl_early_stop must be >= 0 (0: no early stop)")
+        return float(kl_early_stop) > 0.0 or scheduler is None
+
+    def _finish_gated(self, kls: torch.Tensor, snaps: torch.Tensor):
+        """The one synchronisation of a gated update: the epoch KLs, the per-epoch stop word / record count (snapshots of
+        ``epoch_state`` taken on the stream before each ``epoch_end``) and the learning rate in one copy.  Returns (KLs, lr)."""
+        E = kls.numel()
+        host = torch.cat([kls.view(torch.int32), snaps[:, 0], snaps[:, 1], self.state[:1].view(torch.int32)]).cpu()
+        self.last_update = {"recorded": host[2 * E:3 * E].tolist(), "stopped": [bool(x) for x in host[E:2 * E].tolist()]}
+        return host[:E].view(torch.float32).tolist(), float(host[3 * E:].clone().view(torch.float64)[0])
+
     def kl_schedule(self, stats: torch.Tensor, kl_out: torch.Tensor | None = None):
         """KL-adaptive learning rate from the (n_minibatches, 4) stats of one epoch, on the device."""
         self._check(stats, "stats")
@@ -194,9 +249,17 @@ class FusedPPO:
                                                    None if kl_out is None else kl_out.data_ptr(), self._stream()),
                    "rover_ppo_kl_schedule")
 
-    def update(self, obs, act, logp, val, ret, adv, perms=None, epochs: int | None = None, minibatches: int | None = None):
+    def update(self, obs, act, logp, val, ret, adv, perms=None, epochs: int | None = None, minibatches: int | None = None,
+               kl_early_stop: float = 0.0, scheduler: str | None = "kl_adaptive"):
         """The example's PPO update on flat (B, ...) or (T, n_envs, ...) rollout buffers: ``epochs`` passes over
-        ``torch.randperm(B).chunk(minibatches)`` (or the given ``perms[epoch]``).  Returns (epoch KLs, learning rate)."""
+        ``torch.randperm(B).chunk(minibatches)`` (or the given ``perms[epoch]``).  Returns (epoch KLs, learning rate).
+
+        ``kl_early_stop`` > 0: skrl's KL early stop (its ``kl_threshold``); ``scheduler=None``: no learning-rate scheduler.  Either
+        takes the gated kernels: the launches are enqueued for every minibatch and those behind a stop return at once, the epoch
+        KLs are the means over the recorded minibatches, and ``last_update`` holds per-epoch ``recorded`` / ``stopped``.  Still one
+        host synchronisation, at the end.  ``last_stats`` keeps the (epochs, minibatches, 4) records on the device, NaN behind a
+        stop."""
+        gated = self._gated(kl_early_stop, scheduler)
         epochs = self.epochs if epochs is None else int(epochs)
         mbs = self.minibatches if minibatches is None else int(minibatches)
         obs = obs.reshape(-1, obs.shape[-1])
@@ -207,15 +270,32 @@ class FusedPPO:
             self._check(t, nm)
         if obs.shape[1] != 965 or act.shape[1] != 2:
             raise ValueError("obs must be (B, 965) and act (B, 2)")
-        stats = torch.empty(epochs, mbs, 4, device=self.device)
         kls = torch.empty(epochs, device=self.device)
+        if gated:                                   # records behind a stop are never written: they stay NaN
+            stats = torch.full((epochs, mbs, 4), float("nan"), device=self.device)
+            self.epoch_state.zero_()
+            snaps = torch.empty(epochs, 8, dtype=torch.int32, device=self.device)
+        else:
+            stats = torch.empty(epochs, mbs, 4, device=self.device)
+        self.last_stats = stats                     # (epochs, minibatches, 4): KL, policy loss, value loss, 0 per minibatch
         for e in range(epochs):
             perm = perms[e] if perms is not None else torch.randperm(B, device=self.device)
             chunks = perm.chunk(mbs)
             if len(chunks) != mbs:
                 raise ValueError(f"{B} rows do not make {mbs} minibatches")
             for j, mb in enumerate(chunks):
-                self.minibatch(obs, act, logp, val, ret, adv, mb.contiguous(), stats=stats[e, j])
-                self.apply()
-            self.kl_schedule(stats[e], kls[e:e + 1])
+                if gated:
+                    self.minibatch_gated(obs, act, logp, val, ret, adv, mb.contiguous(), stats[e, j], kl_early_stop)
+                    self.apply_gated()
+                else:
+                    self.minibatch(obs, act, logp, val, ret, adv, mb.contiguous(), stats=stats[e, j])
+                    self.apply()
+            if gated:
+                snaps[e].copy_(self.epoch_state)
+                self.epoch_end(stats[e], scheduler is not None, kls[e:e + 1])
+            else:
+                self.kl_schedule(stats[e], kls[e:e + 1])
+        if gated:
+            return self._finish_gated(kls, snaps)
+        self.last_update = None
         return kls.cpu().tolist(), self.lr

@@ -10,8 +10,11 @@ one pass rewrites the whole image with the final statistics, and the later epoch
 ``TorchScaledPPO`` is the specification: the example's loss (examples/04_train_ppo.py) on ``Net`` modules, ``torch.optim.Adam``
 and two ``lift_ppo.RunningStandardScaler`` s in the same order.
 
-Not here (as in the rover example): skrl's KL early stop (the example reads ``kl_threshold`` as the adaptive-rate threshold),
-the entropy term (scale 0), ``rewards_shaper_scale`` (null in the rover files) and ``time_limit_bootstrap``.
+``update(kl_early_stop=0.008, scheduler=None)`` is skrl's KL early stop without a scheduler, rover_ppo.yaml as skrl reads it
+(``include/rover_train_gate.h``; ``ppo_skrl.TorchSkrlPPO`` is its specification): the state scaler's training launches of the
+first epoch sit behind the trainer's stop word (``rover_scaler_train_gated``), so the minibatch that stops the epoch still trains the
+scaler and the skipped ones do not, as in skrl.  ``rewards_shaper_scale`` / ``time_limit_bootstrap`` are the collectors'
+(``rollout.RolloutCollector.record``).  Not here: the entropy term at a non-zero scale (0 in the rover files).
 """
 from __future__ import annotations
 
@@ -173,11 +176,19 @@ class FusedScaledPPO:
             out.append(self.value_scaler.forward(flat).reshape(x.shape))
         return out[0], out[1]
 
+    @property
+    def last_update(self):
+        return self.inner.last_update
+
     def update(self, obs, act, logp, val, ret, adv, perms=None, epochs: int | None = None, minibatches: int | None = None,
-               train_state_scaler: bool = True):
+               train_state_scaler: bool = True, kl_early_stop: float = 0.0, scheduler: str | None = "kl_adaptive"):
         """``TorchScaledPPO.update`` on the device.  ``obs``: the RAW (sanitised) rows of the rollout buffer, never written;
-        ``val`` / ``ret`` from ``standardize_values``.  Returns (epoch KLs, learning rate); one host synchronisation, at the end."""
+        ``val`` / ``ret`` from ``standardize_values``.  Returns (epoch KLs, learning rate); one host synchronisation, at the end.
+        ``kl_early_stop`` / ``scheduler`` as ``FusedPPO.update``: the gated path, the first epoch's scaler training included (the
+        forward into the image runs ungated: rows written behind a stop are rewritten by the pass after the first epoch or never
+        read)."""
         tr = self.inner
+        gated = tr._gated(kl_early_stop, scheduler)
         epochs = tr.epochs if epochs is None else int(epochs)
         mbs = tr.minibatches if minibatches is None else int(minibatches)
         obs = obs.reshape(-1, obs.shape[-1])
@@ -191,8 +202,14 @@ class FusedScaledPPO:
         if self._image.shape[0] < B:
             self._image = torch.empty(B, OBS_DIM, dtype=torch.float32, device=self.device)
         image = self._image[:B]
-        stats = torch.empty(epochs, mbs, 4, device=self.device)
         kls = torch.empty(epochs, device=self.device)
+        if gated:
+            stats = torch.full((epochs, mbs, 4), float("nan"), device=self.device)
+            tr.epoch_state.zero_()
+            snaps = torch.empty(epochs, 8, dtype=torch.int32, device=self.device)
+        else:
+            stats = torch.empty(epochs, mbs, 4, device=self.device)
+        tr.last_stats = stats
         for e in range(epochs):
             perm = perms[e] if perms is not None else torch.randperm(B, device=self.device)
             chunks = perm.chunk(mbs)
@@ -202,11 +219,22 @@ class FusedScaledPPO:
                 mb = mb.contiguous()
                 if e == 0:                      # skrl: state_preprocessor(states, train=not epoch)
                     if train_state_scaler:
-                        self.state_scaler.train(obs, mb)
+                        self.state_scaler.train(obs, mb, gate=tr.epoch_state if gated else None)
                     self.state_scaler.forward(obs, mb, out=image)
-                tr.minibatch(image, act, logp, val, ret, adv, mb, stats=stats[e, j])
-                tr.apply()
+                if gated:
+                    tr.minibatch_gated(image, act, logp, val, ret, adv, mb, stats[e, j], kl_early_stop)
+                    tr.apply_gated()
+                else:
+                    tr.minibatch(image, act, logp, val, ret, adv, mb, stats=stats[e, j])
+                    tr.apply()
             if e == 0 and epochs > 1:           # the statistics are final: one pass, then no scaler work in the later epochs
                 self.state_scaler.forward(obs, out=image)
-            tr.kl_schedule(stats[e], kls[e:e + 1])
+            if gated:
+                snaps[e].copy_(tr.epoch_state)
+                tr.epoch_end(stats[e], scheduler is not None, kls[e:e + 1])
+            else:
+                tr.kl_schedule(stats[e], kls[e:e + 1])
+        if gated:
+            return tr._finish_gated(kls, snaps)
+        tr.last_update = None
         return kls.cpu().tolist(), tr.lr

@@ -133,7 +133,12 @@ class TorchRollout(_RolloutBase):
         return a.clamp(-1.0, 1.0) if self.clip_actions else a
 
     @torch.no_grad()
-    def record(self, t: int, rew, terminated, truncated) -> None:
+    def record(self, t: int, rew, terminated, truncated, rewards_shaper_scale=None, time_limit_bootstrap: bool = False,
+               discount: float = 0.99) -> None:
+        if rewards_shaper_scale is not None or time_limit_bootstrap:
+            from .ppo_skrl import shape_rewards
+            rew = shape_rewards(rew, self.val[t], truncated, 1.0 if rewards_shaper_scale is None else rewards_shaper_scale, discount,
+                                time_limit_bootstrap)
         self.rew[t] = rew
         self.done[t] = (terminated.bool() | truncated.bool()).float()
 
@@ -222,13 +227,24 @@ class RolloutCollector(_RolloutBase):
         return self._env_act
 
     @torch.no_grad()
-    def record(self, t: int, rew: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor) -> None:
+    def record(self, t: int, rew: torch.Tensor, terminated: torch.Tensor, truncated: torch.Tensor, rewards_shaper_scale=None,
+               time_limit_bootstrap: bool = False, discount: float = 0.99) -> None:
+        """Slot ``t`` of ``rew`` / ``done``.  ``rewards_shaper_scale`` (a float; the reference's ``reward_shaper_function``) and
+        ``time_limit_bootstrap`` (skrl: ``rewards += discount * values * truncated``, with slot ``t`` of ``val``, the value of the
+        pre-step states) take ``rover_rollout_record_shaped``; both at their defaults: the plain launch."""
         for name, x, dts in (("rew", rew, (torch.float32,)), ("terminated", terminated, (torch.bool, torch.uint8)),
                              ("truncated", truncated, (torch.bool, torch.uint8))):
             if not x.is_cuda or x.dtype not in dts or not x.is_contiguous() or x.numel() != self.n or x.device != self.device:
                 raise ValueError(f"{name} must be a contiguous {dts[0]} cuda tensor of {self.n} elements")
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         with torch.cuda.device(self.device):
+            if rewards_shaper_scale is not None or time_limit_bootstrap:
+                scale = 1.0 if rewards_shaper_scale is None else float(rewards_shaper_scale)
+                _lib.check(self._lib.rover_rollout_record_shaped(rew.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
+                                                                 self.val[t].data_ptr(), self.n, scale, float(discount),
+                                                                 int(bool(time_limit_bootstrap)), self.rew[t].data_ptr(),
+                                                                 self.done[t].data_ptr(), stream), "rover_rollout_record_shaped")
+                return
             _lib.check(self._lib.rover_rollout_record(rew.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self.n,
                                                       self.rew[t].data_ptr(), self.done[t].data_ptr(), stream), "rover_rollout_record")
 

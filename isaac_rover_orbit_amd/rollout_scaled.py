@@ -8,6 +8,9 @@ and stores ``value_preprocessor(values, inverse=True)``.  ``ScaledRolloutCollect
     2. the unchanged ``rover_rollout_act`` on the scratch (its own ``nan_to_num`` is the identity on clamped finite rows);
     3. ``rover_scaler_apply`` in inverse mode, width 1: the critic's outputs -> ``val[t]``.
 
+``record`` is ``RolloutCollector``'s, ``rewards_shaper_scale`` / ``time_limit_bootstrap`` included: slot ``t`` of ``val`` is on the
+original scale, the return's, as skrl's bootstrap wants it.
+
 Both scalers are ``scaler.DeviceScaler`` s held BY REFERENCE (``FusedScaledPPO.state_scaler`` / ``.value_scaler``): an update of
 the trainer's is seen by the next step.  ``TorchScaledRollout`` is the CPU specification on ``rollout.TorchRollout``.
 """

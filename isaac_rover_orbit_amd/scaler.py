@@ -88,14 +88,23 @@ class DeviceScaler:
         return idx.data_ptr(), int(idx.numel())
 
     @torch.no_grad()
-    def train(self, x: torch.Tensor, idx: torch.Tensor | None = None) -> None:
-        """Updates the statistics with the rows ``idx`` of ``x`` (all rows when ``idx`` is None); at least two rows."""
+    def train(self, x: torch.Tensor, idx: torch.Tensor | None = None, gate: torch.Tensor | None = None) -> None:
+        """Updates the statistics with the rows ``idx`` of ``x`` (all rows when ``idx`` is None); at least two rows.  ``gate``: an
+        int32 device word (``FusedPPO.epoch_state[:1]``); the four launches return at once where it is not zero
+        (``rover_scaler_train_gated``)."""
         x = self._rows(x, "x")
         ip, n = self._idx(idx)
         rows = x.numel() // self.width if n is None else n
         need = int(self._lib.rover_scaler_workspace_bytes(self.width, rows))
         if self.ws.numel() < need:
             self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if gate is not None:
+            if not gate.is_cuda or gate.dtype != torch.int32 or gate.device != self.block.device or gate.numel() < 1:
+                raise ValueError("gate must be an int32 cuda tensor on the scaler's device")
+            _lib.check(self._lib.rover_scaler_train_gated(C.byref(self.hp), self.block.data_ptr(), self.width, x.data_ptr(), ip, rows,
+                                                          self.ws.data_ptr(), self.ws.numel(), gate.data_ptr(), self._stream()),
+                       "rover_scaler_train_gated")
+            return
         _lib.check(self._lib.rover_scaler_train(C.byref(self.hp), self.block.data_ptr(), self.width, x.data_ptr(), ip, rows,
                                                 self.ws.data_ptr(), self.ws.numel(), self._stream()), "rover_scaler_train")
 

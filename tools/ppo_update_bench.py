@@ -5,7 +5,13 @@ example's shapes: 4096 envs x 60 rollouts, 4 epochs x 60 minibatches of 4096 row
     python tools/ppo_update_bench.py [--reps 20] [--out profiles/ppo_update_bench.json] [--fused-only]
 
 Per item: device-synchronised wall clock after warm-up, the two paths alternated in one process (median, min, max over
---reps).  --fused-only runs the fused update alone (for a rocprofv3 --kernel-trace --stats run of its kernels)."""
+--reps).  --fused-only runs the fused update alone (for a rocprofv3 --kernel-trace --stats run of its kernels).
+
+--gate times the gated update (include/rover_train_gate.h) instead, in one call, after warm-up, the four items alternated within
+every repetition on the same permutations: the ungated update twice (their difference is the run-to-run spread), the gated update
+with a threshold above every KL (every launch does its work behind the stop word's load), and the gated update with a threshold
+below every KL (every epoch stops at its first minibatch: 59 skipped minibatches and 60 skipped applies per epoch, launch overhead
+only)."""
 import argparse
 import json
 import os
@@ -42,6 +48,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--update-reps", type=int, default=3)
     ap.add_argument("--fused-only", action="store_true")
+    ap.add_argument("--gate", action="store_true", help="time the gated update against the ungated one (--gate-reps repetitions)")
+    ap.add_argument("--gate-reps", type=int, default=7)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from isaac_rover_orbit_amd.ppo import FusedPPO
@@ -95,6 +103,32 @@ def main():
 
     vb = vals.view(T, n)
     res = {"envs": n, "rollouts": T, "minibatch_rows": mb_rows, "device": torch.cuda.get_device_name(0)}
+    if args.gate:
+        perms = [torch.randperm(B, device=dev) for _ in range(4)]
+        items = {"ungated_a": {}, "gated_no_stop": dict(kl_early_stop=1e30), "ungated_b": {},
+                 "gated_stop_at_first": dict(kl_early_stop=1e-30)}
+        order = list(items)
+        times = {k: [] for k in items}
+        info = {}
+        for r in range(-2, args.gate_reps):             # two warm-up rounds
+            for k in (order if r % 2 == 0 else order[::-1]):
+                t = timed(lambda: fused.update(obs, act, logp, vals, ret, adv, perms=perms, **items[k]))
+                if r >= 0:
+                    times[k].append(t)
+                info[k] = fused.last_update
+        for k in items:
+            res["update_" + k] = dict(summary(times[k]), last_update=info[k])
+        a, b = res["update_ungated_a"]["median_ms"], res["update_ungated_b"]["median_ms"]
+        res["ungated_spread_ms"] = abs(a - b)
+        res["gated_no_stop_minus_ungated_ms"] = res["update_gated_no_stop"]["median_ms"] - 0.5 * (a + b)
+        res["skipped_minibatch_and_apply_us"] = 1e3 * res["update_gated_stop_at_first"]["median_ms"] / (4 * 60)
+        line = json.dumps(res)
+        print(line, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
     mbs = [perm[i * mb_rows:(i + 1) * mb_rows].contiguous() for i in range(60)]
     for i in range(3):                                  # warm-up
         fused_mb(mbs[i])
