@@ -31,10 +31,13 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from isaac_rover_orbit_amd import terrain as T  # noqa: E402
 from isaac_rover_orbit_amd.cfg import RoverEnvCfg  # noqa: E402
+from isaac_rover_orbit_amd import tracker as tracking  # noqa: E402
 from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
+from isaac_rover_orbit_amd.envs.rover_env import LOG_KEYS  # noqa: E402
 from isaac_rover_orbit_amd.policy import RoverNet  # noqa: E402
 
 GAMMA, LAM, CLIP, VCLIP, KL_THR = 0.99, 0.95, 0.2, 0.2, 0.008
+EPISODE_INFO_TAGS = tracking.episode_info_tags(LOG_KEYS)      # infos["episode"], as the reference's trainer tags it
 
 
 class Net(nn.Module):
@@ -103,6 +106,7 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the agent files' rewards_shaper_scale: rewards are multiplied by F as they are recorded (default: off)")
     ap.add_argument("--time_limit_bootstrap", action="store_true",
                     help="skrl's time_limit_bootstrap: rewards += discount * value * truncated as they are recorded")
+    tracking.add_arguments(ap)
     return ap
 
 
@@ -178,6 +182,8 @@ def main():
                 collector = RolloutCollector(*nets, policy.log_std_parameter.detach(), n, Tn, seed=42)
         obs_buf, act_buf, logp_buf, val_buf = collector.obs, collector.actions, collector.logp, collector.val
         rew_buf, done_buf = collector.rew, collector.done
+    # --track: skrl's curves on the device; the fused update's per-minibatch statistics feed skrl PPO's own scalars
+    tracker = tracking.from_args(args, n, EPISODE_INFO_TAGS + (tracking.PPO_TAGS if fused is not None else ()), dev)
     obs, _ = env.reset()
     o = obs["policy"] if collector is not None else torch.nan_to_num(obs["policy"], neginf=0.0)
     out = open(args.out, "w") if args.out else None
@@ -205,6 +211,10 @@ def main():
                 collector.record(t, rew, term, trunc, **(shape_kw if shaped else {}))
                 lv = env.episode_log_vector
                 ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
+                if tracker is not None:         # the env's raw reward; lv is behind the env's own log reduction
+                    tracker.step(rew, term, trunc)
+                    tracker.track_vector(EPISODE_INFO_TAGS, lv)
+                    tracker.post_interaction(it * Tn + t)
                 continue
             s = standardise(o)                  # the buffer keeps the raw rows; the networks read the standardised ones
             mean = actor(s)
@@ -214,6 +224,10 @@ def main():
             obs_buf[t], act_buf[t] = o, a
             obs, rew, term, trunc, info = env.step(a.clamp(-1.0, 1.0))      # clip_actions (models.py:66)
             o = torch.nan_to_num(obs["policy"], neginf=0.0)
+            if tracker is not None:
+                tracker.step(rew, term, trunc)
+                tracker.track_vector(EPISODE_INFO_TAGS, env.episode_log_vector)
+                tracker.post_interaction(it * Tn + t)
             if shaped:
                 from isaac_rover_orbit_amd.ppo_skrl import shape_rewards
                 rew = shape_rewards(rew, val_buf[t], trunc, 1.0 if args.rewards_shaper_scale is None else args.rewards_shaper_scale,
@@ -235,6 +249,8 @@ def main():
                 kls, _ = fused.update(obs_buf, act_buf, logp_buf, val_buf, ret, adv, **upd_kw)
             kl_mean = kls[-1]
             last = fused.last_update
+            if tracker is not None:
+                tracking.track_ppo_update(tracker, fused)
         else:
             # ---- GAE (skrl PPO: bootstraps through time-outs like the reference's config)
             with torch.no_grad():

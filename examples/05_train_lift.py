@@ -22,7 +22,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from isaac_rover_orbit_amd import lift_ppo as LP  # noqa: E402
-from isaac_rover_orbit_amd.envs.lift_env import FrankaCubeLiftEnv, LiftEnvCfg, REWARD_ORDER, TERMINATION_ORDER  # noqa: E402
+from isaac_rover_orbit_amd import tracker as tracking  # noqa: E402
+from isaac_rover_orbit_amd.envs.lift_env import LOG_KEYS, FrankaCubeLiftEnv, LiftEnvCfg, REWARD_ORDER, TERMINATION_ORDER  # noqa: E402
 
 LOG_NAMES = [f"Episode Reward/{k}" for k in REWARD_ORDER] + [f"Episode Termination/{k}" for k in TERMINATION_ORDER]
 
@@ -39,6 +40,7 @@ def main():
                     help="PPO update: the torch spec (autograd + torch.optim.Adam) or the fused HIP kernels")
     ap.add_argument("--rollout", choices=("torch", "fused"), default="torch",
                     help="per-step rollout glue: torch ops, or the fused HIP collector (needs --update fused)")
+    tracking.add_arguments(ap)
     args = ap.parse_args()
     if args.rollout == "fused" and args.update != "fused":
         ap.error("--rollout fused requires --update fused")
@@ -68,6 +70,8 @@ def main():
     o = obs["policy"].clone()
     out = open(args.out, "w") if args.out else None
     log = env._log
+    EPISODE_INFO_TAGS = tracking.episode_info_tags(LOG_KEYS)      # infos["episode"], as the reference's trainer tags it
+    tracker = tracking.from_args(args, n, EPISODE_INFO_TAGS, dev)     # --track: skrl's curves, kept on the device
     for it in range(args.iterations):
         t0 = time.perf_counter()
         if fused is None:
@@ -101,10 +105,18 @@ def main():
                 k = log[8]                                                # envs reset in this step; log[0:8] are their means
                 ep_sum += torch.where(k > 0, log[0:8] * torch.where(torch.arange(8, device=dev) < 6, k, 1.0), 0.0)
                 ep_count += k
+                if tracker is not None:                                   # the env's raw reward; log is reduced every step
+                    tracker.step(rew, term, trunc)
+                    tracker.track_vector(EPISODE_INFO_TAGS, log)
+                    tracker.post_interaction(it * Tn + t)
             for t in range(Tn if col is not None else 0):                 # the same steps, two launches around env.step
                 obs, rew, term, trunc, _ = env.step(col.act(t, o))
                 o = obs["policy"]
                 col.record(t, rew, term, trunc, log)
+                if tracker is not None:                                   # the env's raw reward; log is reduced every step
+                    tracker.step(rew, term, trunc)
+                    tracker.track_vector(EPISODE_INFO_TAGS, log)
+                    tracker.post_interaction(it * Tn + t)
             torch.cuda.synchronize(); t_roll = time.perf_counter() - t0
             last_v = col.last_value(o) if col is not None else value_inv(critic(state_pre(o))).squeeze(1)
             if fused is not None:

@@ -23,6 +23,8 @@ from isaac_rover_orbit_amd import terrain as T  # noqa: E402
 from isaac_rover_orbit_amd.cfg import RoverEnvCfg  # noqa: E402
 from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
 from isaac_rover_orbit_amd.policy import RoverNet  # noqa: E402
+from isaac_rover_orbit_amd import tracker as tracking  # noqa: E402
+from isaac_rover_orbit_amd.envs.rover_env import LOG_KEYS  # noqa: E402
 from isaac_rover_orbit_amd.trpo import FusedTRPO, TorchTRPO  # noqa: E402
 
 _spec = importlib.util.spec_from_file_location("train_ppo_example", os.path.join(ROOT, "examples", "04_train_ppo.py"))
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--rollout", choices=("torch", "fused"), default="torch",
                     help="rollout glue around env.step: torch ops with torch.randn noise, or isaac_rover_orbit_amd.rollout.RolloutCollector "
                          "(one HIP launch per step: sanitise, both networks, counter-based Gaussian actions, log-prob)")
+    tracking.add_arguments(ap)
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     dev = torch.device("cuda")
@@ -74,6 +77,8 @@ def main():
                                          policy.log_std_parameter.detach(), n, Tn, seed=args.seed)
         obs_buf, act_buf, logp_buf, val_buf = collector.obs, collector.actions, collector.logp, collector.val
         rew_buf, done_buf = collector.rew, collector.done
+    EPISODE_INFO_TAGS = tracking.episode_info_tags(LOG_KEYS)      # infos["episode"], as the reference's trainer tags it
+    tracker = tracking.from_args(args, n, EPISODE_INFO_TAGS, dev)     # --track: skrl's curves, kept on the device
     obs, _ = env.reset()
     o = obs["policy"] if collector is not None else torch.nan_to_num(obs["policy"], neginf=0.0)
     out = open(args.out, "w") if args.out else None
@@ -99,6 +104,10 @@ def main():
                 collector.record(t, rew, term, trunc)
                 lv = env.episode_log_vector
                 ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
+                if tracker is not None:             # skrl's curves on the device: the raw reward, lv behind the env's own log reduction
+                    tracker.step(rew, term, trunc)
+                    tracker.track_vector(EPISODE_INFO_TAGS, lv)
+                    tracker.post_interaction(it * Tn + t)
                 continue
             mean = actor(o)
             a = mean + std * torch.randn_like(mean)
@@ -110,6 +119,10 @@ def main():
             rew_buf[t], done_buf[t] = rew, (term | trunc).float()
             lv = env.episode_log_vector
             ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
+            if tracker is not None:             # skrl's curves on the device: the raw reward, lv behind the env's own log reduction
+                tracker.step(rew, term, trunc)
+                tracker.track_vector(EPISODE_INFO_TAGS, lv)
+                tracker.post_interaction(it * Tn + t)
         torch.cuda.synchronize(); t_roll = time.perf_counter() - t0
         perms = [torch.randperm(B, device=dev) for _ in range(4)]
         with torch.no_grad():

@@ -33,6 +33,8 @@ from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
 from isaac_rover_orbit_amd.td3 import (HPARAMS, Critic, FusedTD3, ReplayMemory, TorchTD3, exploration_scale,  # noqa: E402
                                        explore)
 from isaac_rover_orbit_amd.td3_explore import TD3Explorer  # noqa: E402
+from isaac_rover_orbit_amd import tracker as tracking  # noqa: E402
+from isaac_rover_orbit_amd.envs.rover_env import LOG_KEYS  # noqa: E402
 
 _spec = importlib.util.spec_from_file_location("train_ppo_example", os.path.join(ROOT, "examples", "04_train_ppo.py"))
 ppo_example = importlib.util.module_from_spec(_spec)
@@ -64,6 +66,7 @@ def build_parser() -> argparse.ArgumentParser:
                     help="collect without an update before this timestep (skrl learning_starts)")
     ap.add_argument("--smooth_noise_std", type=float, default=0.0,
                     help="std of the target action's smoothing noise (skrl smooth_regularization_noise; 0: none; needs --rollout fused)")
+    tracking.add_arguments(ap)
     return ap
 
 
@@ -92,6 +95,8 @@ def main():
     else:
         spec = TorchTD3(policy, critic_1, critic_2)
     gen = torch.Generator(device=dev).manual_seed(args.seed)
+    EPISODE_INFO_TAGS = tracking.episode_info_tags(LOG_KEYS)      # infos["episode"], as the reference's trainer tags it
+    tracker = tracking.from_args(args, n, EPISODE_INFO_TAGS, dev)     # --track: skrl's curves, kept on the device
     obs, _ = env.reset()
     collector = None
     if args.rollout == "fused":
@@ -123,6 +128,10 @@ def main():
             idx = memory.sample_indices(args.batch_size, gen) if learning else None
         lv = env.episode_log_vector
         ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
+        if tracker is not None:             # skrl's curves on the device: the raw reward, lv behind the env's own log reduction
+            tracker.step(rew, term, trunc)
+            tracker.track_vector(EPISODE_INFO_TAGS, lv)
+            tracker.post_interaction(step)
         if learning and fused is not None:
             smooth = collector.smooth_noise(args.batch_size, args.smooth_noise_std) if args.smooth_noise_std > 0 else None
             fused.update(memory, idx, smooth)

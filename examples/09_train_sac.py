@@ -31,6 +31,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from isaac_rover_orbit_amd.sac import HPARAMS, LOG_STD_MAX, LOG_STD_MIN, FusedSAC, TorchSAC  # noqa: E402
 from isaac_rover_orbit_amd.td3 import Critic, ReplayMemory  # noqa: E402
+from isaac_rover_orbit_amd import tracker as tracking  # noqa: E402
+from isaac_rover_orbit_amd.envs.rover_env import LOG_KEYS  # noqa: E402
 
 _spec = importlib.util.spec_from_file_location("train_ppo_example", os.path.join(ROOT, "examples", "04_train_ppo.py"))
 ppo_example = importlib.util.module_from_spec(_spec)
@@ -57,6 +59,7 @@ def build_parser() -> argparse.ArgumentParser:
                     help="env steps of uniform random actions before the actor acts (skrl random_timesteps)")
     ap.add_argument("--learning_starts", type=int, default=HPARAMS["learning_starts"],
                     help="collect without an update before this timestep (skrl learning_starts)")
+    tracking.add_arguments(ap)
     return ap
 
 
@@ -86,6 +89,8 @@ def main(argv=None):
         spec = TorchSAC(policy, critic_1, critic_2)
     gen = torch.Generator(device=dev).manual_seed(args.seed)
     eps = torch.empty(args.batch_size, 4, device=dev)
+    EPISODE_INFO_TAGS = tracking.episode_info_tags(LOG_KEYS)      # infos["episode"], as the reference's trainer tags it
+    tracker = tracking.from_args(args, n, EPISODE_INFO_TAGS, dev)     # --track: skrl's curves, kept on the device
     obs, _ = env.reset()
     col = None
     if args.rollout == "fused":
@@ -119,6 +124,10 @@ def main(argv=None):
             o = o_next
         lv = env.episode_log_vector
         ep_count += lv[13]; ep_stats += torch.where(lv[13] > 0, lv[7:11], torch.zeros_like(lv[7:11]))
+        if tracker is not None:             # skrl's curves on the device: the raw reward, lv behind the env's own log reduction
+            tracker.step(rew, term, trunc)
+            tracker.track_vector(EPISODE_INFO_TAGS, lv)
+            tracker.post_interaction(step)
         if col is None and step >= args.learning_starts:
             idx = memory.sample_indices(args.batch_size, gen)
             smooth_draw(args.seed, updates, 1.0, eps)

@@ -65,6 +65,8 @@ EXPORTS = [
     "rover_scaler_train", "rover_scaler_apply", "rover_scaler_train_gated",
     "rover_ppo_epoch_bytes", "rover_ppo_minibatch_gated", "rover_ppo_apply_gated", "rover_ppo_epoch_end",  # rover_train_gate.h
     "rover_rollout_record_shaped",  # rover_rollout.h
+    "rover_tracker_state_bytes", "rover_tracker_workspace_bytes", "rover_tracker_snapshot_words", "rover_tracker_init",  # rover_tracker.h
+    "rover_tracker_step", "rover_tracker_track", "rover_tracker_snapshot",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -521,6 +523,16 @@ def load():
     lib.rover_scaler_train.argtypes = [slh, vp, i32, vp, vp, i32, vp, C.c_size_t, vp]
     lib.rover_scaler_apply.argtypes = [slh, vp, i32, vp, vp, i32, i32, vp, vp, vp]
     lib.rover_scaler_train_gated.argtypes = [slh, vp, i32, vp, vp, i32, vp, C.c_size_t, vp, vp]
+    lib.rover_tracker_state_bytes.argtypes = [i32, i32]
+    lib.rover_tracker_state_bytes.restype = C.c_size_t
+    lib.rover_tracker_workspace_bytes.argtypes = [i32]
+    lib.rover_tracker_workspace_bytes.restype = C.c_size_t
+    lib.rover_tracker_snapshot_words.argtypes = [i32]
+    lib.rover_tracker_snapshot_words.restype = C.c_size_t
+    lib.rover_tracker_init.argtypes = [vp, i32, i32, vp]
+    lib.rover_tracker_step.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, C.c_size_t, vp]
+    lib.rover_tracker_track.argtypes = [vp, i32, i32, i32, vp, i32, vp]
+    lib.rover_tracker_snapshot.argtypes = [vp, i32, i32, vp, i32, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
