@@ -11,7 +11,9 @@
 //   lift_wgrad_kernel    one workgroup per 16 x 16 tile of a weight gradient (or of a bias gradient), dW = dZ^T A on the MFMA
 //                        with the rows as k, written in the packed layout;
 //   lift_mb_final_kernel one workgroup: log_std gradient, KL and loss terms from the partials; the epoch's early-stop word.
-// and per optimiser step lift_sumsq_kernel -> lift_adam_prep_kernel -> lift_adam_kernel (norm, clip, Adam, replica refresh).
+// and per optimiser step lift_sumsq_kernel -> lift_adam_prep_kernel -> lift_adam_kernel (norm, clip, Adam, replica refresh); their
+// arithmetic, the KL rate rule and the packed-layout helpers are train_shared.hpp's (the text rover_ppo_apply runs), device_of and
+// launched rover_internal.hpp's.
 // Every kernel of a minibatch / apply reads the device state first and returns at once while the epoch's stop word is set.
 //
 // All the lift layers have K and N multiples of 16 except K = 36 of the first layer and the outputs (8, 1), so every product
@@ -27,10 +29,9 @@
 #include "../../include/rover_policy.h"
 #include "rover_internal.hpp"
 #include "train_math.hpp"
+#include "train_shared.hpp"
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int OBS = 36, NACT = 8;
 constexpr int NL = 4;
@@ -50,8 +51,6 @@ enum { S_X = 0, S_Y1 = 36, S_Y2 = 292, S_Y3 = 420, S_D1 = 484, S_D2 = 740, S_D3 
 constexpr int PART = 16;
 constexpr int NORM_BLOCKS = 128;
 constexpr int MAX_SCALER_W = 64;
-
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 struct LiftNets {
     uint32_t net_off[2];          // start of the policy / value packed block
@@ -74,12 +73,6 @@ __device__ __forceinline__ float scaler_fwd(float x, double mean, double var, fl
 __device__ __forceinline__ float scaler_inv(float x, double mean, double var, float clip)
 {
     return __fadd_rn(__fmul_rn(sqrtf((float)var), clampf_nan(x, -clip, clip)), (float)mean);
-}
-
-// W[n][k] of a packed layer with G k groups (rover_policy.h "Packed weights")
-__device__ __forceinline__ float w_at(const float *Wp, int G, int n, int k)
-{
-    return Wp[((((size_t)(n >> 4) * G + (k >> 4)) * 64 + (n & 15) + 16 * (k & 3)) << 2) + ((k >> 2) & 3)];
 }
 
 // fixed halving tree over the FT threads of the block; returns the total in every thread
@@ -430,10 +423,7 @@ __global__ __launch_bounds__(FT) void lift_sumsq_kernel(const float *grad, int P
 {
     if (stopped(st)) return;
     __shared__ float red[FT];
-    const int chunk = cdiv(P, NORM_BLOCKS), e0 = blockIdx.x * chunk, e1 = min(e0 + chunk, P);
-    float s = 0.0f;
-    for (int e = e0 + threadIdx.x; e < e1; e += FT) s += grad[e] * grad[e];
-    const float tot = block_sum(s, red);
+    const float tot = block_sum(sumsq_partial(grad, P, NORM_BLOCKS, FT), red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(FT) void lift_adam_prep_kernel(const float *part, float max_norm, float beta1, float beta2,
@@ -444,13 +434,10 @@ __global__ __launch_bounds__(FT) void lift_adam_prep_kernel(const float *part, f
     const float tot = block_sum((int)threadIdx.x < NORM_BLOCKS ? part[threadIdx.x] : 0.0f, red);
     if (threadIdx.x == 0) {
         const float norm = sqrtf(tot);
-        const float coef = max_norm / (norm + 1e-6f);
         st->grad_norm = norm;
-        st->clip_coef = fminf(coef, 1.0f);
+        st->clip_coef = grad_clip_coef(norm, max_norm);
         st->step += 1;
-        const double bc1 = 1.0 - pow((double)beta1, (double)st->step), bc2 = 1.0 - pow((double)beta2, (double)st->step);
-        st->step_size = (float)(st->lr / bc1);
-        st->bc2_sqrt = (float)sqrt(bc2);
+        adam_scalars(st->step, beta1, beta2, st->lr, &st->step_size, &st->bc2_sqrt);
     }
 }
 __global__ __launch_bounds__(FT) void lift_adam_kernel(float *params, float *grad, float *m, float *v, const rover_lift_ppo_state *st,
@@ -460,16 +447,7 @@ __global__ __launch_bounds__(FT) void lift_adam_kernel(float *params, float *gra
     if (stopped(st)) return;
     const int e = blockIdx.x * FT + threadIdx.x;
     if (e >= P) return;
-    const float g = grad[e] * st->clip_coef;
-    grad[e] = g;
-    const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
-    const float mo = m[e], mn = mo + w1 * (g - mo);                     // exp_avg.lerp_(grad, 1 - beta1)
-    const float vn = v[e] * beta2 + w2 * (g * g);                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = sqrtf(vn) / st->bc2_sqrt + eps;                 // (exp_avg_sq.sqrt() / sqrt(bc2)).add_(eps)
-    const float p = params[e] + (-st->step_size) * (mn / denom);        // param.addcdiv_(exp_avg, denom, -lr / bc1)
-    m[e] = mn;
-    v[e] = vn;
-    params[e] = p;
+    const float p = adam_element_clipped(params, grad, m, v, e, &st->clip_coef, &st->step_size, &st->bc2_sqrt, beta1, beta2, eps);
     if ((uint32_t)e < Pa) {
         if (rep_a)
             for (int c = 0; c < n_copies; ++c) rep_a[(size_t)c * Pa + e] = p;
@@ -487,10 +465,7 @@ __global__ void lift_kl_kernel(const float *stats, int nmb, float thr, float fac
     for (int i = 0; i < nrec; ++i) s += stats[4 * i];
     if (nrec > 0) {
         const float kl = s / (float)nrec;
-        double lr = st->lr;
-        if ((double)kl > 2.0 * (double)thr) lr = fmax(lr / (double)factor, (double)lr_min);
-        else if ((double)kl < 0.5 * (double)thr) lr = fmin(lr * (double)factor, (double)lr_max);
-        st->lr = lr;
+        st->lr = kl_adaptive_lr(st->lr, kl, thr, factor, lr_min, lr_max);
         if (kl_out) *kl_out = kl;
     } else if (kl_out) {
         *kl_out = NAN;
@@ -502,9 +477,6 @@ __global__ void lift_kl_kernel(const float *stats, int nmb, float thr, float fac
 }
 
 // ---- host helpers
-size_t layer_weight_floats(const rover_policy_layer &l) { return (size_t)cdiv(l.N, 16) * cdiv(l.K, 16) * 64 * 4; }
-size_t layer_bias_floats(const rover_policy_layer &l) { return ((size_t)l.N + 3) & ~(size_t)3; }
-
 // rover_lift_policy_desc(nout) with the offsets rover_policy_pack sets
 bool is_lift(const rover_policy_desc *d, int nout)
 {
@@ -521,12 +493,6 @@ bool is_lift(const rover_policy_desc *d, int nout)
         off += layer_bias_floats(l);
     }
     return true;
-}
-size_t packed_floats(const rover_policy_desc *d)
-{
-    size_t n = 0;
-    for (int i = 0; i < d->n_enc + d->n_mlp; ++i) n += layer_weight_floats(d->layers[i]) + layer_bias_floats(d->layers[i]);
-    return n;
 }
 int check_pair(const rover_policy_desc *pa, const rover_policy_desc *pb)
 {
@@ -557,20 +523,6 @@ LiftHp hp_of(const rover_lift_ppo_hparams *h)
             h->scaler_clip};
 }
 size_t ws_floats(int n) { return WS_HEAD + (size_t)2 * S_ROW * n + (size_t)PART * cdiv(n, RB); }
-int device_of(const void *p, int *dev)
-{
-    hipPointerAttribute_t at;
-    hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_INVALID, "not a device pointer: %s", hipGetErrorString(e));
-    *dev = at.device;
-    return ROVER_OK;
-}
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, what, hipGetErrorString(e));
-    return ROVER_OK;
-}
 // statistics + merge of a scaler update (x rows gathered by idx when not NULL)
 int scaler_train(double *scaler, int width, const float *x, const int64_t *idx, int rows, const rover_lift_ppo_state *st, float *ws,
                  hipStream_t s)

@@ -21,10 +21,9 @@
 #include "../../include/rover_policy.h"
 #include "rover_internal.hpp"
 #include "train_math.hpp"
+#include "train_shared.hpp"   // cdiv, the packed sizes
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int OBS = 36;
 constexpr int NL = 4;
@@ -38,8 +37,6 @@ constexpr int PX = 40, P1 = 260, P2 = 132, P3 = 68;
 constexpr int NET_F = RB * (P1 + P2 + P3);
 constexpr int LDS_FLOATS = RB * PX + 2 * NET_F;      // 15360 floats = 61440 bytes
 constexpr uint32_t LRO_TAG = 0x4C524F00u;            // "LRO\0": word 3 of the Philox counter, | action pair
-
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 __device__ __forceinline__ float clampf_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }   // NaN passes
 // RunningStandardScaler forward / inverse (rover_lift_train.h), fp32 with explicit roundings: the text of lift_ppo_kernels.hip
@@ -218,9 +215,6 @@ __global__ __launch_bounds__(256) void lift_rollout_record_kernel(const float *_
         }
     }
 }
-
-size_t layer_weight_floats(const rover_policy_layer &l) { return (size_t)cdiv(l.N, 16) * cdiv(l.K, 16) * 64 * 4; }
-size_t layer_bias_floats(const rover_policy_layer &l) { return ((size_t)l.N + 3) & ~(size_t)3; }
 
 // rover_lift_policy_desc(nout) with the offsets rover_policy_pack sets
 bool is_lift(const rover_policy_desc *d, int nout)

@@ -10,7 +10,7 @@
 //                             in the packed layout;
 //   offpolicy_combine_kernel  the chunk partials added in chunk order;
 // plus the gather of the sampled rows from the observation ring, the fixed-order reductions the trainers' final kernels use,
-// Adam and Polyak, and the host side that lays the networks out and launches them.
+// Adam (train_shared.hpp's element and scalars) and Polyak, and the host side that lays the networks out and launches them.
 //
 // Both trainers include this one text; what differs between them (the heads, the final kernels, the workspace, the argument
 // checks, the entry points) stays in their files.  Every kernel is a template on the trainer's device state struct
@@ -28,10 +28,9 @@
 #include "../../include/rover_hip.h"
 #include "../../include/rover_policy.h"
 #include "rover_internal.hpp"
+#include "train_shared.hpp"
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int OBS = 965, PROP = 4, ENC_OFF = 3;
 constexpr int ACOL = 64;                                     // first action column of the critic's MLP input
@@ -48,9 +47,6 @@ constexpr int MAXJ = 2 * NL;                                 // layers per weigh
 constexpr int MW[NL] = {80, 68, 256, 160, 128, 4};
 constexpr int ROW_F = 80 + 68 + 256 + 160 + 128 + 4;        // 696
 constexpr int RP = 8;                                        // stride of a block's partials
-
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-__host__ __device__ inline size_t al4(size_t n) { return (n + 3) & ~(size_t)3; }
 
 // fixed halving tree over the 256 threads of the block; the total in every thread after the call
 __device__ __forceinline__ float block_sum(float v, float *red)
@@ -183,10 +179,6 @@ struct BackLaunch {
     int rows;
     float slope;
 };
-__device__ __forceinline__ float w_at(const float *Wp, int G, int n, int k)
-{
-    return Wp[((((size_t)(n >> 4) * G + (k >> 4)) * 64 + (n & 15) + 16 * (k & 3)) << 2) + ((k >> 2) & 3)];
-}
 template <class State>
 __global__ __launch_bounds__(FT) void offpolicy_back_kernel(BackLaunch L)
 {
@@ -306,37 +298,16 @@ __device__ void reduce_rows(const float *rowp, int nblk, int nterms, float *tot,
         tot[i] = block_sum(s, red);
     }
 }
-__device__ void adam_scalars(int step, float beta1, float beta2, float lr, float *step_size, float *bc2_sqrt)
-{
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    *step_size = (float)((double)lr / bc1);
-    *bc2_sqrt = (float)sqrt(bc2);
-}
 
-// ---- Adam (torch's single-tensor order) over P floats; sc = {step_size, bc2_sqrt} in the state; then the replicas
-__device__ __forceinline__ float adam_one(float *params, const float *grad, float *m, float *v, const float *sc, int e, float beta1,
-                                          float beta2, float eps)
-{
-    const float g = grad[e];
-    const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
-    const float mo = m[e], mn = mo + w1 * (g - mo);                     // exp_avg.lerp_(grad, 1 - beta1)
-    const float vn = v[e] * beta2 + w2 * (g * g);                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = sqrtf(vn) / sc[1] + eps;                        // (exp_avg_sq.sqrt() / sqrt(bc2)).add_(eps)
-    const float p = params[e] + (-sc[0]) * (mn / denom);                // param.addcdiv_(exp_avg, denom, -lr / bc1)
-    m[e] = mn;
-    v[e] = vn;
-    params[e] = p;
-    return p;
-}
+// ---- Adam (train_shared.hpp's element, no clipping) over P floats; sc = {step_size, bc2_sqrt} in the state; then the replicas
 template <class State>
 __global__ __launch_bounds__(FT) void offpolicy_adam_kernel(float *params, const float *grad, float *m, float *v, const float *sc, int P,
                                                             float beta1, float beta2, float eps, float *rep, int n_copies)
 {
     const int e = blockIdx.x * FT + threadIdx.x;
     if (e >= P) return;
-    const float p = adam_one(params, grad, m, v, sc, e, beta1, beta2, eps);
-    if (rep)
-        for (int c = 0; c < n_copies; ++c) rep[(size_t)c * P + e] = p;
+    const float p = adam_element(params, m, v, e, grad[e], sc, sc + 1, beta1, beta2, eps);
+    refresh_replicas(rep, n_copies, P, e, p);
 }
 
 // ---- Polyak: t.mul_(1 - tau); t.add_(tau * p) -- two fp32 roundings per product, one per sum (no contraction)
@@ -351,8 +322,6 @@ __global__ __launch_bounds__(FT) void offpolicy_polyak_kernel(float *t, const fl
 }
 
 // ---- host side
-size_t layer_weight_floats(int N, int K) { return (size_t)cdiv(N, 16) * cdiv(K, 16) * 64 * 4; }
-size_t layer_bias_floats(int N) { return al4((size_t)N); }
 int out_of(int l, bool critic) { return l < NL - 1 ? LN[l] : (critic ? 1 : 2); }
 int in_of(int l, bool critic) { return critic ? CK[l] : AK[l]; }
 size_t net_floats(bool critic)
@@ -404,21 +373,6 @@ struct Region {
 };
 size_t rowp_floats(int rows) { return al4((size_t)RP * cdiv(rows, FT)); }
 size_t part_floats(int rows) { return (size_t)cdiv(rows, CH) * (2 * net_floats(true)); }   // the chunk partials of both critics
-
-int device_of(const void *p, int *dev)
-{
-    hipPointerAttribute_t at;
-    hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_INVALID, "not a device pointer: %s", hipGetErrorString(e));
-    *dev = at.device;
-    return ROVER_OK;
-}
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, what, hipGetErrorString(e));
-    return ROVER_OK;
-}
 
 // the forward of up to MAXZ networks over `rows` rows; net z reads observation rows ro[z] and (critics) actions ain[z] (any
 // pitch aip) and writes its layer outputs to reg[z]->cache.  The last layer has no activation: a tanh actor's head applies it.

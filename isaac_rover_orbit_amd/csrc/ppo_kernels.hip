@@ -9,7 +9,9 @@
 //   ppo_wgrad_kernel     one workgroup per 16 x 16 tile of a weight gradient (or of a bias gradient), dW = dZ^T A on
 //                        v_mfma_f32_16x16x4_f32 with the rows as k, written in the packed layout;
 //   ppo_mb_final_kernel  one workgroup: log_std gradient, KL and loss terms from the partials.
-// and per optimiser step ppo_sumsq_kernel -> ppo_adam_prep_kernel -> ppo_adam_kernel (norm, clip, Adam, replica refresh).
+// and per optimiser step ppo_sumsq_kernel -> ppo_adam_prep_kernel -> ppo_adam_kernel (norm, clip, Adam, replica refresh); their
+// arithmetic, the KL rate rule, the packed-layout helpers and the reference-architecture check are train_shared.hpp's, device_of and
+// launched rover_internal.hpp's.
 // Each of the six has a gated twin for skrl's KL early stop (include/rover_train_gate.h): the same code behind one load of
 // rover_ppo_epoch.stop -- the rows and wgrad kernels as a second instantiation over a wider argument struct, the four small ones as
 // *_gated_kernel around a shared device function; ppo_epoch_end_kernel closes an epoch.
@@ -29,10 +31,9 @@
 #include "../../include/rover_train_gate.h"
 #include "rover_internal.hpp"
 #include "train_math.hpp"
+#include "train_shared.hpp"
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int OBS = 965, PROP = 4, ENC_OFF = 3;
 constexpr int NL = 6;
@@ -52,8 +53,6 @@ enum { S_A1 = 0, S_M = 80, S_A3 = 144, S_A4 = 400, S_A5 = 560, S_DZ1 = 688, S_DZ
        S_DZ6 = 1372, S_ROW = 1374 };
 constexpr int NORM_BLOCKS = 128;
 
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
 // where the parameters of each network and log_std sit in the flat vector (offsets in floats)
 struct PpoNets {
     uint32_t net_off[2];          // start of the policy / value packed block
@@ -66,13 +65,6 @@ struct PpoNets {
 struct PpoHp {
     float clip, vclip, vscale, ls_min, ls_max;
 };
-
-// W[n][k] of a packed layer with G k groups (rover_policy.h "Packed weights"): fragment (t = n / 16, g = k / 16), lane
-// (n & 15) + 16 (k & 3), element (k & 15) / 4
-__device__ __forceinline__ float w_at(const float *Wp, int G, int n, int k)
-{
-    return Wp[((((size_t)(n >> 4) * G + (k >> 4)) * 64 + (n & 15) + 16 * (k & 3)) << 2) + ((k >> 2) & 3)];
-}
 
 // acc[r] = chain_k fmaf(in[r][k], W[n][k], acc[r]) for k in [k0, k1) ascending, r < 16 (the MFMA's k-ordered chain)
 __device__ __forceinline__ void chain16(float (&acc)[RB], const float *in, int ip, const float *Wp, int G, int n, int k0, int k1)
@@ -456,10 +448,7 @@ __global__ __launch_bounds__(FT) void ppo_mb_final_gated_kernel(const float *par
 __device__ __forceinline__ void ppo_sumsq_body(const float *grad, int P, float *part)
 {
     __shared__ float red[FT];
-    const int chunk = cdiv(P, NORM_BLOCKS), e0 = blockIdx.x * chunk, e1 = min(e0 + chunk, P);
-    float s = 0.0f;
-    for (int e = e0 + threadIdx.x; e < e1; e += FT) s += grad[e] * grad[e];
-    const float tot = block_sum(s, red);
+    const float tot = block_sum(sumsq_partial(grad, P, NORM_BLOCKS, FT), red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(FT) void ppo_sumsq_kernel(const float *grad, int P, float *part) { ppo_sumsq_body(grad, P, part); }
@@ -474,13 +463,10 @@ __device__ __forceinline__ void ppo_adam_prep_body(const float *part, float max_
     const float tot = block_sum((int)threadIdx.x < NORM_BLOCKS ? part[threadIdx.x] : 0.0f, red);
     if (threadIdx.x == 0) {
         const float norm = sqrtf(tot);
-        const float coef = max_norm / (norm + 1e-6f);
         st->grad_norm = norm;
-        st->clip_coef = fminf(coef, 1.0f);
+        st->clip_coef = grad_clip_coef(norm, max_norm);
         st->step += 1;
-        const double bc1 = 1.0 - pow((double)beta1, (double)st->step), bc2 = 1.0 - pow((double)beta2, (double)st->step);
-        st->step_size = (float)(st->lr / bc1);
-        st->bc2_sqrt = (float)sqrt(bc2);
+        adam_scalars(st->step, beta1, beta2, st->lr, &st->step_size, &st->bc2_sqrt);
     }
 }
 __global__ __launch_bounds__(FT) void ppo_adam_prep_kernel(const float *part, float max_norm, float beta1, float beta2,
@@ -500,16 +486,7 @@ __device__ __forceinline__ void ppo_adam_body(float *params, float *grad, float 
 {
     const int e = blockIdx.x * FT + threadIdx.x;
     if (e >= P) return;
-    const float g = grad[e] * st->clip_coef;
-    grad[e] = g;
-    const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
-    const float mo = m[e], mn = mo + w1 * (g - mo);                     // exp_avg.lerp_(grad, 1 - beta1)
-    const float vn = v[e] * beta2 + w2 * (g * g);                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = sqrtf(vn) / st->bc2_sqrt + eps;                 // (exp_avg_sq.sqrt() / sqrt(bc2)).add_(eps)
-    const float p = params[e] + (-st->step_size) * (mn / denom);        // param.addcdiv_(exp_avg, denom, -lr / bc1)
-    m[e] = mn;
-    v[e] = vn;
-    params[e] = p;
+    const float p = adam_element_clipped(params, grad, m, v, e, &st->clip_coef, &st->step_size, &st->bc2_sqrt, beta1, beta2, eps);
     if ((uint32_t)e < Pa) {
         if (rep_a)
             for (int c = 0; c < n_copies; ++c) rep_a[(size_t)c * Pa + e] = p;
@@ -538,7 +515,7 @@ __global__ void ppo_kl_kernel(const float *stats, int nmb, float thr, float fact
     float s = 0.0f;
     for (int i = 0; i < nmb; ++i) s += stats[4 * i];
     const float kl = s / (float)nmb;
-    double lr = st->lr;
+    double lr = st->lr;   // kl_adaptive_lr written out: behind the call this kernel's last branch comes out inverted
     if ((double)kl > 2.0 * (double)thr) lr = fmax(lr / (double)factor, (double)lr_min);
     else if ((double)kl < 0.5 * (double)thr) lr = fmin(lr * (double)factor, (double)lr_max);
     st->lr = lr;
@@ -555,12 +532,7 @@ __global__ void ppo_epoch_end_kernel(const float *stats, int nmb, float thr, flo
         float s = 0.0f;
         for (int i = 0; i < rec; ++i) s += stats[4 * i];
         kl = s / (float)rec;
-        if (schedule) {
-            double lr = st->lr;
-            if ((double)kl > 2.0 * (double)thr) lr = fmax(lr / (double)factor, (double)lr_min);
-            else if ((double)kl < 0.5 * (double)thr) lr = fmin(lr * (double)factor, (double)lr_max);
-            st->lr = lr;
-        }
+        if (schedule) st->lr = kl_adaptive_lr(st->lr, kl, thr, factor, lr_min, lr_max);
     }
     if (kl_out) *kl_out = kl;
     const int32_t stopped = ep->stopped_epochs + (ep->stop != 0);
@@ -592,36 +564,6 @@ __global__ __launch_bounds__(FT) void ppo_gae_kernel(const float *rew, const flo
 }
 
 // ---- host helpers
-size_t layer_weight_floats(const rover_policy_layer &l) { return (size_t)cdiv(l.N, 16) * cdiv(l.K, 16) * 64 * 4; }
-size_t layer_bias_floats(const rover_policy_layer &l) { return ((size_t)l.N + 3) & ~(size_t)3; }
-
-// the reference architecture (rover_policy_default_desc), final tanh iff out_dim 2 (policy) / none iff 1 (value), with the
-// offsets rover_policy_pack sets
-bool is_reference(const rover_policy_desc *d, int nout, int final_act)
-{
-    if (!d) return false;
-    if (d->obs_dim != OBS || d->prop_dim != PROP || d->enc_offset != ENC_OFF || d->enc_dim != LK[0] || d->n_enc != 2 || d->n_mlp != 4)
-        return false;
-    if (d->leaky_slope != 0.01f) return false;
-    size_t off = 0;
-    for (int i = 0; i < NL; ++i) {
-        const rover_policy_layer &l = d->layers[i];
-        if (l.K != LK[i] || l.N != (i < NL - 1 ? LN[i] : nout)) return false;
-        if (l.act != (i < NL - 1 ? ROVER_ACT_LEAKY_RELU : final_act)) return false;
-        if ((l.split_k != 0) != (i == 0 || i == NL - 1)) return false;
-        if (l.w_off != off) return false;
-        off += layer_weight_floats(l);
-        if (l.b_off != off) return false;
-        off += layer_bias_floats(l);
-    }
-    return true;
-}
-size_t packed_floats(const rover_policy_desc *d)
-{
-    size_t n = 0;
-    for (int i = 0; i < d->n_enc + d->n_mlp; ++i) n += layer_weight_floats(d->layers[i]) + layer_bias_floats(d->layers[i]);
-    return n;
-}
 int check_pair(const rover_policy_desc *pa, const rover_policy_desc *pb)
 {
     if (!pa || !pb) return rover_internal_fail(ROVER_ERR_INVALID, "descriptor is NULL");
@@ -647,20 +589,6 @@ PpoNets nets_of(const rover_policy_desc *pa, const rover_policy_desc *pb)
     return s;
 }
 size_t ws_floats(int n) { return WS_HEAD + (size_t)2 * S_ROW * n + (size_t)8 * cdiv(n, RB); }
-int device_of(const void *p, int *dev)
-{
-    hipPointerAttribute_t at;
-    hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_INVALID, "not a device pointer: %s", hipGetErrorString(e));
-    *dev = at.device;
-    return ROVER_OK;
-}
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, what, hipGetErrorString(e));
-    return ROVER_OK;
-}
 
 }  // namespace
 

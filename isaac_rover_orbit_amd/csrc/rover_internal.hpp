@@ -9,6 +9,30 @@ __attribute__((visibility("hidden"))) int rover_internal_fail(int code, const ch
 
 #include <hip/hip_runtime_api.h>
 
+#include "../../include/rover_hip.h"
+
+// The HIP device `p` lives on, for the DeviceGuard of an entry point.  A failed query also stays on the runtime's record as the
+// thread's last error; with `clear_error` it is taken off, so that a later launched() does not report it (the scaler and the
+// tracker ask for that).
+inline int device_of(const void *p, int *dev, bool clear_error = false)
+{
+    hipPointerAttribute_t at;
+    hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) {
+        if (clear_error) (void)hipGetLastError();
+        return rover_internal_fail(ROVER_ERR_INVALID, "not a device pointer: %s", hipGetErrorString(e));
+    }
+    *dev = at.device;
+    return ROVER_OK;
+}
+// after a launch: the runtime's last error under the entry point's format string `what`, or ROVER_OK
+inline int launched(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, what, hipGetErrorString(e));
+    return ROVER_OK;
+}
+
 // Every entry point that launches work runs on the handle's device, whatever the calling thread's current device is.
 struct DeviceGuard {
     int prev = -1;

@@ -220,7 +220,8 @@ __global__ __launch_bounds__(64) void sac_tail_adam_kernel(float *params, const 
     const int e = threadIdx.x;
     if (e >= TAIL) return;
     if (e >= 4 && !learn_entropy) return;
-    adam_one(params, grad, m, v, e < 4 ? sc_actor : sc_entropy, e, beta1, beta2, eps);
+    const float *sc = e < 4 ? sc_actor : sc_entropy;
+    adam_element(params, m, v, e, grad[e], sc, sc + 1, beta1, beta2, eps);
 }
 
 // ---- host side

@@ -197,23 +197,6 @@ __global__ __launch_bounds__(TT) void scaler_apply_kernel(ApplyArgs A)
     }
 }
 
-int device_of(const void *p, int *dev)
-{
-    hipPointerAttribute_t at;
-    hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return rover_internal_fail(ROVER_ERR_INVALID, "not a device pointer: %s", hipGetErrorString(e));
-    }
-    *dev = at.device;
-    return ROVER_OK;
-}
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, what, hipGetErrorString(e));
-    return ROVER_OK;
-}
 bool width_ok(int32_t width) { return width >= 1 && width <= MAX_W; }
 size_t ws_doubles(int width, int rows) { return (size_t)width * (1 + (size_t)cdiv(rows, CH)); }
 
@@ -252,7 +235,7 @@ int train_impl(const rover_scaler_hparams *h, double *scaler, int32_t width, con
         return rover_internal_fail(ROVER_ERR_INVALID, "rover_scaler_train: scaler, ws and idx must be 8-byte aligned");
     if (reinterpret_cast<uintptr_t>(x) & 3) return rover_internal_fail(ROVER_ERR_INVALID, "rover_scaler_train: x must be 4-byte aligned");
     int dev;
-    if (int rc = device_of(scaler, &dev)) return rc;
+    if (int rc = device_of(scaler, &dev, true)) return rc;
     DeviceGuard guard(dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
     double *bmean = static_cast<double *>(ws), *part = bmean + width;
@@ -317,7 +300,7 @@ int rover_scaler_apply(const rover_scaler_hparams *h, const double *scaler, int3
     const uintptr_t px = reinterpret_cast<uintptr_t>(x), po = reinterpret_cast<uintptr_t>(out), pr = reinterpret_cast<uintptr_t>(raw_out);
     if ((px | po | pr) & 3) return rover_internal_fail(ROVER_ERR_INVALID, "rover_scaler_apply: x, out and raw_out must be 4-byte aligned");
     int dev;
-    if (int rc = device_of(scaler, &dev)) return rc;
+    if (int rc = device_of(scaler, &dev, true)) return rc;
     DeviceGuard guard(dev);
     ApplyArgs A;
     A.scaler = scaler; A.x = x; A.idx = idx; A.out = out; A.raw = raw_out;

@@ -303,13 +303,6 @@ int check_layout(const char *who, const int32_t *state, int32_t n, int32_t R, in
     return ROVER_OK;
 }
 
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, what, hipGetErrorString(e));
-    return ROVER_OK;
-}
-
 }  // namespace
 
 extern "C" {

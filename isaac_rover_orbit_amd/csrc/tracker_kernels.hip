@@ -267,23 +267,6 @@ __global__ __launch_bounds__(TT) void tracker_snapshot_kernel(int32_t *state, in
     }
 }
 
-int device_of(const void *p, int *dev)
-{
-    hipPointerAttribute_t at;
-    hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return rover_internal_fail(ROVER_ERR_INVALID, "not a device pointer: %s", hipGetErrorString(e));
-    }
-    *dev = at.device;
-    return ROVER_OK;
-}
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, what, hipGetErrorString(e));
-    return ROVER_OK;
-}
 bool slots_ok(int32_t slots) { return slots >= 0 && slots <= MAX_SLOTS; }
 int check_state(const char *who, const void *state, int32_t n, int32_t slots)
 {
@@ -310,7 +293,7 @@ int rover_tracker_init(void *state, int32_t n, int32_t slots, void *stream)
 {
     if (int rc = check_state("rover_tracker_init", state, n, slots)) return rc;
     int dev;
-    if (int rc = device_of(state, &dev)) return rc;
+    if (int rc = device_of(state, &dev, true)) return rc;
     DeviceGuard guard(dev);
     const size_t words = rover_tracker_state_bytes(n, slots) / 4;
     const size_t blocks = (words + TT - 1) / TT;
@@ -331,7 +314,7 @@ int rover_tracker_step(void *state, int32_t n, int32_t slots, const float *rew, 
         (flag_bytes == 4 && ((reinterpret_cast<uintptr_t>(terminated) | reinterpret_cast<uintptr_t>(truncated)) & 3)))
         return rover_internal_fail(ROVER_ERR_INVALID, "rover_tracker_step: rew and float32 flags must be 4-byte aligned");
     int dev;
-    if (int rc = device_of(state, &dev)) return rc;
+    if (int rc = device_of(state, &dev, true)) return rc;
     DeviceGuard guard(dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nb = cdiv(n, TT);
@@ -365,7 +348,7 @@ int rover_tracker_track(void *state, int32_t n, int32_t slots, int32_t first_slo
     if (first_slot < 0 || count < 1 || (long long)first_slot + count > slots)
         return rover_internal_fail(ROVER_ERR_INVALID, "rover_tracker_track: slot out of range");
     int dev;
-    if (int rc = device_of(state, &dev)) return rc;
+    if (int rc = device_of(state, &dev, true)) return rc;
     DeviceGuard guard(dev);
     hipLaunchKernelGGL(tracker_track_kernel, dim3((unsigned)cdiv(count, TT)), dim3(TT), 0, static_cast<hipStream_t>(stream),
                        static_cast<int32_t *>(state), (int)slots, (int)first_slot, values, (int)count);
@@ -378,7 +361,7 @@ int rover_tracker_snapshot(void *state, int32_t n, int32_t slots, void *out, int
     if (!out || (reinterpret_cast<uintptr_t>(out) & 7))
         return rover_internal_fail(ROVER_ERR_INVALID, "rover_tracker_snapshot: out must be an 8-byte aligned pointer");
     int dev;
-    if (int rc = device_of(state, &dev)) return rc;
+    if (int rc = device_of(state, &dev, true)) return rc;
     DeviceGuard guard(dev);
     hipLaunchKernelGGL(tracker_snapshot_kernel, dim3(1), dim3(TT), 0, static_cast<hipStream_t>(stream), static_cast<int32_t *>(state),
                        (int)slots, static_cast<int32_t *>(out), (int)(clear_window != 0));

@@ -9,7 +9,9 @@
 //   trpo_wgrad_kernel    dW = dZ^T A and db = sum dZ per (16 x 16 tile, 2048-row chunk), written in the packed layout;
 //   trpo_combine_kernel  the chunk partials added in chunk order (plus damping v for a Fisher-vector product);
 // plus one-thread-per-row heads (surrogate gradient, FVP scaling, line-search KL / surrogate, value MSE), fixed-order
-// reductions and the small CG / line-search / Adam kernels that read and write the device state.
+// reductions and the small CG / line-search / Adam kernels that read and write the device state.  The value step's clip and Adam
+// arithmetic, w_at, the packed sizes and the reference-architecture check are train_shared.hpp's, device_of and launched
+// rover_internal.hpp's; the network kernels are this file's own.
 //
 // The theta_old forward of rover_trpo_policy_grad caches every activation (690 floats per row), so a Fisher-vector product
 // is a JVP (6 dense launches), a head, a reverse pass (5 launches) and the weight gradients (1 launch + combine).
@@ -23,10 +25,9 @@
 #include "../../include/rover_policy.h"
 #include "../../include/rover_trpo.h"
 #include "rover_internal.hpp"
+#include "train_shared.hpp"
 
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int OBS = 965, PROP = 4, ENC_OFF = 3;
 constexpr int NL = 6;
@@ -40,9 +41,6 @@ constexpr int CH = 2048;                                     // rows per weight-
 constexpr int MW[NL] = {80, 64, 256, 160, 128, 2};
 constexpr int ROW_F = 80 + 64 + 256 + 160 + 128 + 2;        // 690
 constexpr int HEAD_F = 1024;                                 // reduction partials at the start of the workspace
-
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-__host__ __device__ inline size_t al4(size_t n) { return (n + 3) & ~(size_t)3; }
 
 struct Nets {
     uint32_t net_off[2];          // start of the policy / value packed block
@@ -166,10 +164,6 @@ struct BackArgs {
     float slope;
     const int32_t *skip;
 };
-__device__ __forceinline__ float w_at(const float *Wp, int G, int n, int k)
-{
-    return Wp[((((size_t)(n >> 4) * G + (k >> 4)) * 64 + (n & 15) + 16 * (k & 3)) << 2) + ((k >> 2) & 3)];
-}
 __global__ __launch_bounds__(FT) void trpo_back_kernel(BackArgs A)
 {
     if (skipped(A.skip)) return;
@@ -568,13 +562,10 @@ __global__ __launch_bounds__(FT) void trpo_adam_prep_kernel(const float *part, f
     const float tot = reduce_part(part, red);
     if (threadIdx.x == 0) {
         const float norm = sqrtf(tot);
-        const float coef = max_norm / (norm + 1e-6f);
         st->grad_norm = norm;
-        st->clip_coef = fminf(coef, 1.0f);
+        st->clip_coef = grad_clip_coef(norm, max_norm);
         st->value_step += 1;
-        const double bc1 = 1.0 - pow((double)beta1, (double)st->value_step), bc2 = 1.0 - pow((double)beta2, (double)st->value_step);
-        st->step_size = (float)((double)lr / bc1);
-        st->bc2_sqrt = (float)sqrt(bc2);
+        adam_scalars(st->value_step, beta1, beta2, lr, &st->step_size, &st->bc2_sqrt);
     }
 }
 __global__ __launch_bounds__(FT) void trpo_adam_kernel(float *params, float *grad, float *m, float *v, const rover_trpo_state *st, int P,
@@ -582,23 +573,11 @@ __global__ __launch_bounds__(FT) void trpo_adam_kernel(float *params, float *gra
 {
     const int e = blockIdx.x * FT + threadIdx.x;
     if (e >= P) return;
-    const float g = grad[e] * st->clip_coef;
-    grad[e] = g;
-    const float w1 = (float)(1.0 - (double)beta1), w2 = (float)(1.0 - (double)beta2);
-    const float mo = m[e], mn = mo + w1 * (g - mo);                     // exp_avg.lerp_(grad, 1 - beta1)
-    const float vn = v[e] * beta2 + w2 * (g * g);                       // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = sqrtf(vn) / st->bc2_sqrt + eps;                 // (exp_avg_sq.sqrt() / sqrt(bc2)).add_(eps)
-    const float p = params[e] + (-st->step_size) * (mn / denom);        // param.addcdiv_(exp_avg, denom, -lr / bc1)
-    m[e] = mn;
-    v[e] = vn;
-    params[e] = p;
-    if (rep)
-        for (int c = 0; c < n_copies; ++c) rep[(size_t)c * P + e] = p;
+    const float p = adam_element_clipped(params, grad, m, v, e, &st->clip_coef, &st->step_size, &st->bc2_sqrt, beta1, beta2, eps);
+    refresh_replicas(rep, n_copies, P, e, p);
 }
 
 // ---- host side
-size_t layer_weight_floats(int N, int K) { return (size_t)cdiv(N, 16) * cdiv(K, 16) * 64 * 4; }
-size_t layer_bias_floats(int N) { return al4((size_t)N); }
 size_t ref_net_floats(int nout)
 {
     size_t n = 0;
@@ -610,26 +589,6 @@ size_t ref_net_floats(int nout)
 }
 size_t ref_param_floats() { return ref_net_floats(2) + ref_net_floats(1) + 4; }
 
-bool is_reference(const rover_policy_desc *d, int nout, int final_act)
-{
-    if (!d) return false;
-    if (d->obs_dim != OBS || d->prop_dim != PROP || d->enc_offset != ENC_OFF || d->enc_dim != LK[0] || d->n_enc != 2 || d->n_mlp != 4)
-        return false;
-    if (d->leaky_slope != 0.01f) return false;
-    size_t off = 0;
-    for (int i = 0; i < NL; ++i) {
-        const rover_policy_layer &l = d->layers[i];
-        const int N = i < NL - 1 ? LN[i] : nout;
-        if (l.K != LK[i] || l.N != N) return false;
-        if (l.act != (i < NL - 1 ? ROVER_ACT_LEAKY_RELU : final_act)) return false;
-        if ((l.split_k != 0) != (i == 0 || i == NL - 1)) return false;
-        if (l.w_off != off) return false;
-        off += layer_weight_floats(N, LK[i]);
-        if (l.b_off != off) return false;
-        off += layer_bias_floats(N);
-    }
-    return true;
-}
 int check_pair(const rover_policy_desc *pa, const rover_policy_desc *pb)
 {
     if (!pa || !pb) return rover_internal_fail(ROVER_ERR_INVALID, "descriptor is NULL");
@@ -701,21 +660,6 @@ Ws ws_at(void *ws, int rows, int mb)
     w.pol = region_at(pol, rows, ref_net_floats(2));
     if (mb > 0) w.val = region_at(pol + region_floats(rows, ref_net_floats(2)), mb, ref_net_floats(1));
     return w;
-}
-
-int device_of(const void *p, int *dev)
-{
-    hipPointerAttribute_t at;
-    hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_INVALID, "not a device pointer: %s", hipGetErrorString(e));
-    *dev = at.device;
-    return ROVER_OK;
-}
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, what, hipGetErrorString(e));
-    return ROVER_OK;
 }
 
 // one network's forward over a region's rows: layer outputs into `dst` (cache or scratch)
