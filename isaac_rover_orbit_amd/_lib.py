@@ -312,6 +312,19 @@ def _hip_runtimes() -> set:
     return out
 
 
+# (rover_X_bytes entry, Python mirror of struct rover_X): load() refuses a library whose sizes differ
+_MIRRORS = [("rover_config_bytes", RoverConfig), ("rover_lift_config_bytes", LiftConfig), ("rover_camera_config_bytes", CameraConfig),
+            ("rover_viewer_config_bytes", ViewerConfig), ("rover_ppo_hparams_bytes", PpoHparams), ("rover_ppo_state_bytes", PpoState),
+            ("rover_ppo_epoch_bytes", PpoEpoch), ("rover_lift_ppo_hparams_bytes", LiftPpoHparams),
+            ("rover_lift_ppo_state_bytes", LiftPpoState), ("rover_trpo_hparams_bytes", TrpoHparams),
+            ("rover_trpo_state_bytes", TrpoState), ("rover_td3_hparams_bytes", Td3Hparams), ("rover_td3_state_bytes", Td3State),
+            ("rover_rollout_hparams_bytes", RolloutHparams), ("rover_lift_rollout_hparams_bytes", LiftRolloutHparams),
+            ("rover_td3_collect_hparams_bytes", Td3CollectHparams), ("rover_td3_explore_hparams_bytes", Td3ExploreHparams),
+            ("rover_sac_hparams_bytes", SacHparams), ("rover_sac_state_bytes", SacState),
+            ("rover_sac_collect_hparams_bytes", SacCollectHparams), ("rover_scaler_hparams_bytes", ScalerHparams),
+            ("rover_trace_stream_bytes", TraceStream)]
+
+
 def load():
     """Load ``librover_hip.so`` (built in-tree by ``__graft_entry__.build()`` / ``isaac_rover_orbit_amd.build``)."""
     global _lib
@@ -540,40 +553,11 @@ def load():
         if fn.restype is C.c_int:
             fn.restype = C.c_int
     lib.rover_config_bytes.restype = C.c_size_t
-    if lib.rover_config_bytes() != C.sizeof(RoverConfig):
-        raise RoverHipError("struct rover_config of librover_hip.so does not match the Python mirror")
-    if lib.rover_lift_config_bytes() != C.sizeof(LiftConfig) or lib.rover_lift_state_words() != LIFT_STATE_WORDS:
-        raise RoverHipError("struct lift_config / lift state layout of librover_hip.so does not match the Python mirror")
-    if lib.rover_camera_config_bytes() != C.sizeof(CameraConfig):
-        raise RoverHipError("struct rover_camera_config of librover_hip.so does not match the Python mirror")
-    if lib.rover_viewer_config_bytes() != C.sizeof(ViewerConfig):
-        raise RoverHipError("struct rover_viewer_config of librover_hip.so does not match the Python mirror")
-    if lib.rover_ppo_hparams_bytes() != C.sizeof(PpoHparams) or lib.rover_ppo_state_bytes() != C.sizeof(PpoState):
-        raise RoverHipError("struct rover_ppo_hparams / rover_ppo_state of librover_hip.so does not match the Python mirror")
-    if lib.rover_ppo_epoch_bytes() != C.sizeof(PpoEpoch):
-        raise RoverHipError("struct rover_ppo_epoch of librover_hip.so does not match the Python mirror")
-    if lib.rover_lift_ppo_hparams_bytes() != C.sizeof(LiftPpoHparams) or lib.rover_lift_ppo_state_bytes() != C.sizeof(LiftPpoState):
-        raise RoverHipError("struct rover_lift_ppo_hparams / rover_lift_ppo_state of librover_hip.so does not match the Python mirror")
-    if lib.rover_trpo_hparams_bytes() != C.sizeof(TrpoHparams) or lib.rover_trpo_state_bytes() != C.sizeof(TrpoState):
-        raise RoverHipError("struct rover_trpo_hparams / rover_trpo_state of librover_hip.so does not match the Python mirror")
-    if lib.rover_td3_hparams_bytes() != C.sizeof(Td3Hparams) or lib.rover_td3_state_bytes() != C.sizeof(Td3State):
-        raise RoverHipError("struct rover_td3_hparams / rover_td3_state of librover_hip.so does not match the Python mirror")
-    if lib.rover_rollout_hparams_bytes() != C.sizeof(RolloutHparams):
-        raise RoverHipError("struct rover_rollout_hparams of librover_hip.so does not match the Python mirror")
-    if lib.rover_lift_rollout_hparams_bytes() != C.sizeof(LiftRolloutHparams):
-        raise RoverHipError("struct rover_lift_rollout_hparams of librover_hip.so does not match the Python mirror")
-    if lib.rover_td3_collect_hparams_bytes() != C.sizeof(Td3CollectHparams):
-        raise RoverHipError("struct rover_td3_collect_hparams of librover_hip.so does not match the Python mirror")
-    if lib.rover_td3_explore_hparams_bytes() != C.sizeof(Td3ExploreHparams):
-        raise RoverHipError("struct rover_td3_explore_hparams of librover_hip.so does not match the Python mirror")
-    if lib.rover_sac_hparams_bytes() != C.sizeof(SacHparams) or lib.rover_sac_state_bytes() != C.sizeof(SacState):
-        raise RoverHipError("struct rover_sac_hparams / rover_sac_state of librover_hip.so does not match the Python mirror")
-    if lib.rover_sac_collect_hparams_bytes() != C.sizeof(SacCollectHparams):
-        raise RoverHipError("struct rover_sac_collect_hparams of librover_hip.so does not match the Python mirror")
-    if lib.rover_scaler_hparams_bytes() != C.sizeof(ScalerHparams):
-        raise RoverHipError("struct rover_scaler_hparams of librover_hip.so does not match the Python mirror")
-    if lib.rover_trace_stream_bytes() != C.sizeof(TraceStream):
-        raise RoverHipError("struct rover_trace_stream of librover_hip.so does not match the Python mirror")
+    for entry, mirror in _MIRRORS:              # rover_X_bytes() of the library against sizeof of the Python mirror of struct rover_X
+        if getattr(lib, entry)() != C.sizeof(mirror):
+            raise RoverHipError(f"struct {entry[:-len('_bytes')]} of librover_hip.so does not match the Python mirror")
+    if lib.rover_lift_state_words() != LIFT_STATE_WORDS:
+        raise RoverHipError("lift state layout of librover_hip.so does not match the Python mirror")
     if lib.rover_state_words() != STATE_WORDS:
         raise RoverHipError("librover_hip.so state layout does not match the Python binding")
     _lib = lib

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._fused import stream
 from ._logdict import LogDict
 from .rover_env import RLTaskEnv, _ptr, _spaces
 
@@ -157,7 +158,7 @@ class FrankaCubeLiftEnv(RLTaskEnv):
         return self
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream(self.device)
 
     # views used by user code / tests
     @property

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._fused import stream
 from ..cfg import OBS_ORDER, REWARD_ORDER, TERMINATION_ORDER, RoverEnvCfg
 from ..terrain import Terrain, make_flat_terrain, make_procedural_terrain
 from ._logdict import LogDict
@@ -463,7 +464,7 @@ class RoverEnv(RLTaskEnv):
         return self
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream(self.device)
 
     @property
     def call_counter(self) -> int:

@@ -13,11 +13,11 @@ from __future__ import annotations
 import ctypes as C
 from typing import Mapping
 
-import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _fused, _lib
+from ._fused import ptr
 from .policy import RoverNet, make_desc
 
 OBS_DIM, ACT_DIM = 36, 8
@@ -28,9 +28,7 @@ LOG_STD_KEY = "log_std_parameter"    # skrl GaussianMixin
 
 def default_hparams() -> "_lib.LiftPpoHparams":
     """skrl_ppo_cfg.yaml of the lift task (rover_lift_ppo_default_hparams)."""
-    h = _lib.LiftPpoHparams()
-    _lib.check(_lib.load().rover_lift_ppo_default_hparams(C.byref(h)), "rover_lift_ppo_default_hparams")
-    return h
+    return _fused.default_hparams(_lib.LiftPpoHparams, "rover_lift_ppo_default_hparams")
 
 
 # ---------------------------------------------------------------------------------------------------------------- torch spec
@@ -187,15 +185,9 @@ class TorchLiftPPO:
 
 # ---------------------------------------------------------------------------------------------------------------- HIP path
 def _layers(sd: Mapping[str, torch.Tensor]):
-    ws, bs = [], []
-    i = 0
-    while LIFT_KEY.format(2 * i, "weight") in sd:
-        ws.append(sd[LIFT_KEY.format(2 * i, "weight")]); bs.append(sd[LIFT_KEY.format(2 * i, "bias")])
-        i += 1
-    if i == 0:
+    ws, bs, (n,) = _fused.host_layers(sd, (LIFT_KEY,))
+    if n == 0:
         raise ValueError("state_dict has no net.<i>.weight entries")
-    ws = [np.ascontiguousarray(torch.as_tensor(w).detach().cpu().numpy(), dtype=np.float32) for w in ws]
-    bs = [np.ascontiguousarray(torch.as_tensor(b).detach().cpu().numpy(), dtype=np.float32) for b in bs]
     return ws, bs
 
 
@@ -208,28 +200,14 @@ def pack(sd: Mapping[str, torch.Tensor]):
     """(descriptor, packed host array) of a lift state_dict (``net.<2i>.*`` keys)."""
     ws, bs = _layers(sd)
     desc = lift_desc([w.shape for w in ws])
-    lib = _lib.load()
-    packed = np.empty(int(lib.rover_policy_packed_floats(C.byref(desc))), dtype=np.float32)
-    nl = len(ws)
-    wp = (C.c_void_p * nl)(*[w.ctypes.data for w in ws])
-    bp = (C.c_void_p * nl)(*[b.ctypes.data for b in bs])
-    _lib.check(lib.rover_policy_pack(C.byref(desc), wp, bp, packed.ctypes.data), "rover_policy_pack")
-    return desc, packed
+    return desc, _fused.pack_layers(desc, ws, bs)
 
 
 def unpack(desc: "_lib.PolicyDesc", packed) -> dict:
     """Packed buffer (one replica) -> ``net.<2i>.*`` state_dict entries (rover_policy_unpack), float32 CPU tensors."""
-    packed = np.ascontiguousarray(torch.as_tensor(packed).detach().cpu().numpy(), dtype=np.float32)
-    nl = desc.n_enc + desc.n_mlp
-    ws = [np.empty((desc.layers[i].N, desc.layers[i].K), np.float32) for i in range(nl)]
-    bs = [np.empty(desc.layers[i].N, np.float32) for i in range(nl)]
-    wp = (C.c_void_p * nl)(*[w.ctypes.data for w in ws])
-    bp = (C.c_void_p * nl)(*[b.ctypes.data for b in bs])
-    _lib.check(_lib.load().rover_policy_unpack(C.byref(desc), packed.ctypes.data, wp, bp), "rover_policy_unpack")
     sd = {}
-    for i in range(nl):
-        sd[LIFT_KEY.format(2 * i, "weight")] = torch.from_numpy(ws[i])
-        sd[LIFT_KEY.format(2 * i, "bias")] = torch.from_numpy(bs[i])
+    for i, (w, b) in enumerate(zip(*_fused.unpack_layers(desc, packed))):
+        sd[LIFT_KEY.format(2 * i, "weight")], sd[LIFT_KEY.format(2 * i, "bias")] = w, b
     return sd
 
 
@@ -250,58 +228,32 @@ def _scaler_sd(blk: torch.Tensor, width: int) -> dict:
     return {"running_mean": b[:width].clone(), "running_variance": b[width:2 * width].clone(), "current_count": b[2 * width].clone()}
 
 
-class FusedLiftPPO:
+class FusedLiftPPO(_fused.FusedActorCritic):
     """Lift PPO trainer state on the GPU: parameters, Adam moments, both scalers, learning rate, step count and the epoch's
     early-stop word all in device memory.  ``.actor`` / ``.critic`` alias the trainer's parameters (replicas refreshed by every
     optimiser step) and read STANDARDISED states (``standardize``).  ``update`` synchronises with the host once, at its end."""
 
+    OBS_DIM, ACT_DIM = OBS_DIM, ACT_DIM
+    _STATE, _WORKSPACE, _PARAM_FLOATS = _lib.LiftPpoState, "rover_lift_ppo_workspace_bytes", "rover_lift_ppo_param_floats"
+    _RUNS = "the lift networks only (rover_lift_train.h)"
+    _unpack = staticmethod(unpack)
+
     def __init__(self, policy_sd: Mapping[str, torch.Tensor], value_sd: Mapping[str, torch.Tensor], lr: float = 1e-4,
                  epochs: int = 8, minibatches: int = 24, device="cuda", n_copies: int = 4, **hparams):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("FusedLiftPPO needs a ROCm GPU (no CPU fallback)")
-        self._lib = _lib.load()
-        self.device = torch.device(device)
-        self.hp = default_hparams()
-        for k, v in hparams.items():
-            if not hasattr(self.hp, k):
-                raise TypeError(f"unknown hyper-parameter {k!r}")
-            setattr(self.hp, k, v)
-        self.epochs, self.minibatches, self.n_copies = int(epochs), int(minibatches), int(n_copies)
-        self.desc_p, pa = pack(policy_sd)
-        self.desc_v, pv = pack(value_sd)
-        P = int(self._lib.rover_lift_ppo_param_floats(C.byref(self.desc_p), C.byref(self.desc_v)))
-        if P == 0:
-            raise _lib.RoverHipError("FusedLiftPPO runs the lift networks only (rover_lift_train.h)")
-        self.n_p, self.n_v = pa.size, pv.size
-        ls = torch.as_tensor(policy_sd[LOG_STD_KEY]).detach().float().cpu().reshape(-1)
-        if ls.numel() != ACT_DIM:
-            raise ValueError(f"log_std_parameter must hold {ACT_DIM} values")
-        flat = np.concatenate([pa, pv, ls.numpy()])
-        assert flat.size == P
-        self.params = torch.from_numpy(flat).to(self.device)
-        self.grad = torch.zeros_like(self.params)
-        self.adam_m = torch.zeros_like(self.params)
-        self.adam_v = torch.zeros_like(self.params)
+        super().__init__(default_hparams, hparams, device, n_copies)
+        self.epochs, self.minibatches = int(epochs), int(minibatches)
+        self._networks(pack(policy_sd), pack(value_sd), policy_sd[LOG_STD_KEY])
         self.state = torch.zeros(C.sizeof(_lib.LiftPpoState) // 8, dtype=torch.float64, device=self.device)
         self.state[0] = float(lr)
         self.state_scaler = _scaler_block(OBS_DIM, self.device)
         self.value_scaler = _scaler_block(1, self.device)
-        self.rep_p = self.params[:self.n_p].repeat(self.n_copies)
-        self.rep_v = self.params[self.n_p:self.n_p + self.n_v].repeat(self.n_copies)
-        self.actor = RoverNet.from_packed(self.desc_p, self.rep_p, self.n_copies)
-        self.critic = RoverNet.from_packed(self.desc_v, self.rep_v, self.n_copies)
-        self.ws = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._ensure_ws(1)
-        self._gae_hp = _lib.PpoHparams()
-        _lib.check(self._lib.rover_ppo_default_hparams(C.byref(self._gae_hp)), "rover_ppo_default_hparams")
-        self._gae_hp.gamma, self._gae_hp.lam = self.hp.gamma, self.hp.lam
 
     @classmethod
     def from_checkpoint(cls, ck, **kw) -> "FusedLiftPPO":
         """skrl-style checkpoint ``{"policy", "value"[, "state_preprocessor", "value_preprocessor"]}`` (a path or the dict)."""
-        if isinstance(ck, str):
-            ck = torch.load(ck, map_location="cpu", weights_only=False)
-        t = cls(ck["policy"], ck["value"], **kw)
+        ck = _fused.load_checkpoint(ck)
+        t = super().from_checkpoint(ck, **kw)
         for key, blk, w in (("state_preprocessor", t.state_scaler, OBS_DIM), ("value_preprocessor", t.value_scaler, 1)):
             if key in ck:
                 sd = ck[key]
@@ -311,10 +263,6 @@ class FusedLiftPPO:
         return t
 
     # ---- views
-    @property
-    def log_std(self) -> torch.Tensor:
-        return self.params[self.n_p + self.n_v:self.n_p + self.n_v + ACT_DIM]
-
     @property
     def lr(self) -> float:
         return float(self.state[0].item())
@@ -332,26 +280,10 @@ class FusedLiftPPO:
 
     def state_dict(self) -> dict:
         """skrl-style checkpoint: ``policy`` / ``value`` state_dicts (``net.<2i>.*``, ``log_std_parameter``) and both scalers."""
-        p = self.params.cpu()
-        pol = unpack(self.desc_p, p[:self.n_p])
-        pol[LOG_STD_KEY] = p[self.n_p + self.n_v:].clone()
-        return {"policy": pol, "value": unpack(self.desc_v, p[self.n_p:self.n_p + self.n_v]),
-                "state_preprocessor": _scaler_sd(self.state_scaler, OBS_DIM), "value_preprocessor": _scaler_sd(self.value_scaler, 1)}
+        return {**super().state_dict(), "state_preprocessor": _scaler_sd(self.state_scaler, OBS_DIM),
+                "value_preprocessor": _scaler_sd(self.value_scaler, 1)}
 
     # ---- kernels
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _ensure_ws(self, rows: int):
-        need = int(self._lib.rover_lift_ppo_workspace_bytes(int(rows)))
-        if self.ws.numel() < need:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-
-    @staticmethod
-    def _check(t: torch.Tensor, name: str, dtype=torch.float32):
-        if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dtype} cuda tensor")
-
     def standardize(self, x: torch.Tensor, which: str = "state", train: bool = False, inverse: bool = False,
                     out: torch.Tensor | None = None) -> torch.Tensor:
         """The state (36-wide) or value (1-wide) RunningStandardScaler on the device (rover_lift_ppo_standardize)."""
@@ -365,16 +297,6 @@ class FusedLiftPPO:
                                                         self._stream()), "rover_lift_ppo_standardize")
         return out.reshape(shape)
 
-    def gae(self, rew, done, val, last_v):
-        """(adv, ret) of (T, n_envs) rollouts in rover_ppo_gae's order; adv is not normalised."""
-        for t, nm in ((rew, "rew"), (done, "done"), (val, "val"), (last_v, "last_v")):
-            self._check(t, nm)
-        T, n = rew.shape
-        adv, ret = torch.empty_like(rew), torch.empty_like(rew)
-        _lib.check(self._lib.rover_ppo_gae(C.byref(self._gae_hp), rew.data_ptr(), done.data_ptr(), val.data_ptr(), last_v.data_ptr(),
-                                           T, n, adv.data_ptr(), ret.data_ptr(), self._stream()), "rover_ppo_gae")
-        return adv, ret
-
     def minibatch(self, obs, act, logp, val, ret, adv, idx, train_scaler=False, stats=None, mean_out=None, value_out=None):
         """Gradient of one minibatch into ``self.grad`` (nothing while the epoch's stop word is set); ``stats`` (4 floats)."""
         self._check(idx, "idx", torch.int64)
@@ -382,7 +304,6 @@ class FusedLiftPPO:
         self._ensure_ws(max(n, 1))
         if stats is None:
             stats = torch.zeros(4, device=self.device)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         _lib.check(self._lib.rover_lift_ppo_minibatch(C.byref(self.desc_p), C.byref(self.desc_v), C.byref(self.hp),
                                                       self.params.data_ptr(), self.state_scaler.data_ptr(), obs.data_ptr(),
                                                       act.data_ptr(), logp.data_ptr(), val.data_ptr(), ret.data_ptr(), adv.data_ptr(),
@@ -410,22 +331,11 @@ class FusedLiftPPO:
         or (T, n_envs, ...).  Returns (epoch KL means, learning rate)."""
         epochs = self.epochs if epochs is None else int(epochs)
         mbs = self.minibatches if minibatches is None else int(minibatches)
-        obs = obs.reshape(-1, obs.shape[-1])
-        B = obs.shape[0]
-        act = act.reshape(B, -1)
-        logp, val, ret, adv = (x.reshape(B) for x in (logp, val, ret, adv))
-        for t, nm in ((obs, "obs"), (act, "act"), (logp, "logp"), (val, "val"), (ret, "ret"), (adv, "adv")):
-            self._check(t, nm)
-        if obs.shape[1] != OBS_DIM or act.shape[1] != ACT_DIM:
-            raise ValueError(f"obs must be (B, {OBS_DIM}) and act (B, {ACT_DIM})")
+        obs, act, logp, val, ret, adv, B = self._flat_rollout(obs, act, logp=logp, val=val, ret=ret, adv=adv)
         stats = torch.zeros(epochs, mbs, 4, device=self.device)
         kls = torch.empty(epochs, device=self.device)
         for e in range(epochs):
-            perm = perms[e] if perms is not None else torch.randperm(B, device=self.device)
-            chunks = perm.chunk(mbs)
-            if len(chunks) != mbs:
-                raise ValueError(f"{B} rows do not make {mbs} minibatches")
-            for j, mb in enumerate(chunks):
+            for j, mb in enumerate(self._minibatches(perms, e, B, mbs)):
                 self.minibatch(obs, act, logp, val, ret, adv, mb.contiguous(), train_scaler=(e == 0), stats=stats[e, j])
                 self.apply()
             self.kl_schedule(stats[e], kls[e:e + 1])

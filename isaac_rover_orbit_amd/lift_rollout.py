@@ -21,9 +21,10 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _fused, _lib
+from ._fused import f32_cuda, holds, launch, ptr
 from .lift_ppo import OBS_DIM
-from .rollout import _MASK, standard_normals
+from .rollout import _FLAG, _transition, standard_normals
 
 LIFT_ROLLOUT_TAG = 0x4C524F00     # "LRO\0": word 3 of the Philox counter, | action pair (the lift env's draws have word 3 in {0, 1})
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
@@ -129,9 +130,7 @@ class TorchLiftRollout(_LiftRolloutBase):
 
 # ---------------------------------------------------------------------------------------------------------------- the kernels
 def default_hparams() -> "_lib.LiftRolloutHparams":
-    hp = _lib.LiftRolloutHparams()
-    _lib.check(_lib.load().rover_lift_rollout_default_hparams(C.byref(hp)), "rover_lift_rollout_default_hparams")
-    return hp
+    return _fused.default_hparams(_lib.LiftRolloutHparams, "rover_lift_rollout_default_hparams")
 
 
 def lift_rollout_act(actor, critic, log_std: torch.Tensor, obs: torch.Tensor, counter: int, hp: "_lib.LiftRolloutHparams",
@@ -140,7 +139,6 @@ def lift_rollout_act(actor, critic, log_std: torch.Tensor, obs: torch.Tensor, co
     """One ``rover_lift_rollout_act`` launch on the current stream; ``mean_out`` / ``val_out`` are allocated when not given, every
     other output left ``None`` is passed as NULL (not computed), ``value_scaler=None`` leaves the value raw.  Returns
     ``(mean_out, val_out)``."""
-    lib = _lib.load()
     if obs.dim() != 2 or obs.shape[1] != OBS_DIM:
         raise ValueError(f"obs must be (n, {OBS_DIM})")
     n = int(obs.shape[0])
@@ -152,29 +150,20 @@ def lift_rollout_act(actor, critic, log_std: torch.Tensor, obs: torch.Tensor, co
     if actor.n_copies != critic.n_copies:
         raise ValueError("actor and critic must hold the same number of packed replicas")
     A = actor.out_dim
-    want = {"obs": (n, OBS_DIM), "log_std": (A,), "obs_out": (n, OBS_DIM), "mean_out": (n, A), "val_out": (n, 1), "act_out": (n, A),
-            "env_act_out": (n, A), "logp_out": (n,), "eps_out": (n, A)}
-    for name, t in (("obs", obs), ("log_std", log_std), ("obs_out", obs_out), ("mean_out", mean_out), ("val_out", val_out),
-                    ("act_out", act_out), ("env_act_out", env_act_out), ("logp_out", logp_out), ("eps_out", eps_out)):
-        if t is None:
-            continue
-        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.device != actor.packed.device:
-            raise ValueError(f"{name} must be a contiguous float32 cuda tensor on the networks' device")
-        if t.numel() != int(np.prod(want[name])):
-            raise ValueError(f"{name} must hold {want[name]} values")
+    for name, t, shape in (("obs", obs, (n, OBS_DIM)), ("log_std", log_std, (A,)), ("obs_out", obs_out, (n, OBS_DIM)),
+                           ("mean_out", mean_out, (n, A)), ("val_out", val_out, (n, 1)), ("act_out", act_out, (n, A)),
+                           ("env_act_out", env_act_out, (n, A)), ("logp_out", logp_out, (n,)), ("eps_out", eps_out, (n, A))):
+        f32_cuda(name, t, actor.packed.device, "the networks' device")
+        holds(name, t, shape)
     for name, t, w in (("state_scaler", state_scaler, OBS_DIM), ("value_scaler", value_scaler, 1)):
         if t is None:
             continue
         if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != 2 * w + 1 or t.device != obs.device:
             raise ValueError(f"{name} must be a contiguous float64 cuda tensor of {2 * w + 1} values (mean, var, count)")
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-    with torch.cuda.device(obs.device):
-        _lib.check(lib.rover_lift_rollout_act(C.byref(actor.desc), actor.packed.data_ptr(), C.byref(critic.desc),
-                                              critic.packed.data_ptr(), actor.n_copies, C.byref(hp), C.c_uint64(int(counter)),
-                                              obs.data_ptr(), n, log_std.data_ptr(), state_scaler.data_ptr(), ptr(value_scaler),
-                                              ptr(obs_out), mean_out.data_ptr(), val_out.data_ptr(), ptr(act_out), ptr(env_act_out),
-                                              ptr(logp_out), ptr(eps_out), stream), "rover_lift_rollout_act")
+    launch("rover_lift_rollout_act", obs.device, C.byref(actor.desc), actor.packed.data_ptr(), C.byref(critic.desc),
+           critic.packed.data_ptr(), actor.n_copies, C.byref(hp), C.c_uint64(int(counter)), obs.data_ptr(), n, log_std.data_ptr(),
+           state_scaler.data_ptr(), ptr(value_scaler), ptr(obs_out), mean_out.data_ptr(), val_out.data_ptr(), ptr(act_out),
+           ptr(env_act_out), ptr(logp_out), ptr(eps_out))
     return mean_out, val_out
 
 
@@ -183,23 +172,15 @@ def lift_rollout_record(rew: torch.Tensor, terminated: torch.Tensor, truncated: 
     """One ``rover_lift_rollout_record`` launch on the current stream (``log=None``: no tally)."""
     n = int(rew.numel())
     dev = rew.device
-    for name, x, dts in (("rew", rew, (torch.float32,)), ("terminated", terminated, (torch.bool, torch.uint8)),
-                         ("truncated", truncated, (torch.bool, torch.uint8)), ("rew_out", rew_out, (torch.float32,)),
-                         ("done_out", done_out, (torch.float32,))):
-        if not x.is_cuda or x.dtype not in dts or not x.is_contiguous() or x.numel() != n or x.device != dev:
-            raise ValueError(f"{name} must be a contiguous {dts[0]} cuda tensor of {n} elements")
+    _transition(n, dev, ("rew", rew, (torch.float32,)), ("terminated", terminated, _FLAG), ("truncated", truncated, _FLAG),
+                ("rew_out", rew_out, (torch.float32,)), ("done_out", done_out, (torch.float32,)))
     if log is not None:
         for name, x, m in (("log", log, LOG_WORDS), ("ep_sum", ep_sum, 8), ("ep_count", ep_count, 1)):
             if x is None or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() < m or x.device != dev:
                 raise ValueError(f"{name} must be a contiguous float32 cuda tensor of at least {m} elements")
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().rover_lift_rollout_record(rew.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), n,
-                                                         C.c_float(float(reward_scale)), ptr(log), rew_out.data_ptr(),
-                                                         done_out.data_ptr(), ptr(ep_sum) if log is not None else None,
-                                                         ptr(ep_count) if log is not None else None, stream),
-                   "rover_lift_rollout_record")
+    launch("rover_lift_rollout_record", dev, rew.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), n,
+           C.c_float(float(reward_scale)), ptr(log), rew_out.data_ptr(), done_out.data_ptr(), ptr(ep_sum) if log is not None else None,
+           ptr(ep_count) if log is not None else None)
 
 
 class LiftRolloutCollector(_LiftRolloutBase):
@@ -212,8 +193,7 @@ class LiftRolloutCollector(_LiftRolloutBase):
     """
 
     def __init__(self, trainer, num_envs: int, horizon: int, seed: int = 42, env_id_offset: int = 0, clip_actions: bool = False):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("LiftRolloutCollector needs a ROCm GPU (no CPU fallback; TorchLiftRollout is the CPU specification)")
+        _fused.require_gpu("LiftRolloutCollector", "TorchLiftRollout is the CPU specification")
         super().__init__(trainer.log_std, num_envs, horizon, seed, env_id_offset, clip_actions, trainer.actor.packed.device)
         self._lib = _lib.load()
         self.trainer = trainer
@@ -230,9 +210,8 @@ class LiftRolloutCollector(_LiftRolloutBase):
         return float(self.trainer.hp.reward_scale)
 
     def hparams(self) -> "_lib.LiftRolloutHparams":
-        hp, th = default_hparams(), self.trainer.hp
-        hp.seed_lo, hp.seed_hi = self.seed & _MASK, (self.seed >> 32) & _MASK
-        hp.env_id_offset, hp.clip_actions = self.env_id_offset, int(self.clip_actions)
+        hp, th = _fused.seeded(default_hparams(), self.seed, self.env_id_offset), self.trainer.hp
+        hp.clip_actions = int(self.clip_actions)
         hp.log_std_min, hp.log_std_max = th.log_std_min, th.log_std_max
         hp.scaler_eps, hp.scaler_clip, hp.reward_scale = th.scaler_eps, th.scaler_clip, th.reward_scale
         return hp

@@ -16,7 +16,7 @@ from typing import Mapping, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _fused, _lib
 
 ENCODER_KEY = "dense_encoder.encoder_layers.{}.{}"   # models.py:28-30: Linear at even indices, activation at odd ones
 MLP_KEY = "mlp.{}.{}"                                 # models.py:76-86
@@ -31,8 +31,7 @@ class RoverNet:
 
     def __init__(self, weights: Sequence, biases: Sequence, n_enc: int = 2, final_act: str = "tanh", obs_dim: int = 965,
                  prop_dim: int = 4, leaky_slope: float = 0.01, device="cuda", n_copies: int = 4, hidden_act: str = "leaky_relu"):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("RoverNet needs a ROCm GPU (no CPU fallback)")
+        _fused.require_gpu("RoverNet")
         self._lib = _lib.load()
         self.device = torch.device(device)
         ws = [np.ascontiguousarray(torch.as_tensor(w).detach().cpu().numpy(), dtype=np.float32) for w in weights]
@@ -104,7 +103,7 @@ class RoverNet:
             out = torch.empty((n, self.out_dim), dtype=torch.float32, device=obs.device)
         if obs.device != self.packed.device or out.device != obs.device:
             raise ValueError(f"obs / out must live on the network's device {self.packed.device}")
-        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        stream = _fused.stream(obs.device)
         with torch.cuda.device(obs.device):     # the entry point launches on the thread's current device
             _lib.check(self._lib.rover_policy_forward(C.byref(self.desc), self.packed.data_ptr(), self.n_copies, obs.data_ptr(),
                                                       n, out.data_ptr(), stream), "rover_policy_forward")
@@ -137,7 +136,7 @@ def forward_pair(net_a: RoverNet, net_b: RoverNet, obs: torch.Tensor, out_a: tor
         out_b = torch.empty((n, net_b.out_dim), dtype=torch.float32, device=obs.device)
     if net_a.n_copies != net_b.n_copies or obs.device != net_a.packed.device or obs.device != net_b.packed.device:
         return net_a(obs, out_a), net_b(obs, out_b)
-    stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+    stream = _fused.stream(obs.device)
     with torch.cuda.device(obs.device):
         rc = net_a._lib.rover_policy_forward_pair(C.byref(net_a.desc), net_a.packed.data_ptr(), C.byref(net_b.desc), net_b.packed.data_ptr(),
                                                   net_a.n_copies, obs.data_ptr(), n, out_a.data_ptr(), out_b.data_ptr(), stream)

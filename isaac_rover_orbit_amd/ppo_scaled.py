@@ -23,7 +23,7 @@ from typing import Mapping
 import torch
 import torch.nn as nn
 
-from . import _lib
+from ._fused import load_checkpoint, require_gpu
 from .lift_ppo import RunningStandardScaler, kl_adaptive
 from .ppo import FusedPPO
 from .scaler import DeviceScaler
@@ -113,8 +113,7 @@ class FusedScaledPPO:
     scale (``value_scaler.inverse`` gives values).  ``rollout_scaled.ScaledRolloutCollector`` does both per env step."""
 
     def __init__(self, policy_sd: Mapping[str, torch.Tensor], value_sd: Mapping[str, torch.Tensor], device="cuda", **kw):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("FusedScaledPPO needs a ROCm GPU (no CPU fallback; TorchScaledPPO is the specification)")
+        require_gpu("FusedScaledPPO", "TorchScaledPPO is the specification")
         self.inner = FusedPPO(policy_sd, value_sd, device=device, **kw)
         self.device = self.inner.device
         self.state_scaler = DeviceScaler(OBS_DIM, self.device)
@@ -124,8 +123,7 @@ class FusedScaledPPO:
     @classmethod
     def from_checkpoint(cls, ck, **kw) -> "FusedScaledPPO":
         """skrl checkpoint ``{"policy", "value"[, "state_preprocessor", "value_preprocessor"]}`` (a path or the loaded dict)."""
-        if isinstance(ck, str):
-            ck = torch.load(ck, map_location="cpu", weights_only=False)
+        ck = load_checkpoint(ck)
         t = cls(ck["policy"], ck["value"], **kw)
         for key, sc in ((STATE_KEY, t.state_scaler), (VALUE_KEY, t.value_scaler)):
             if key in ck:
@@ -191,50 +189,20 @@ class FusedScaledPPO:
         gated = tr._gated(kl_early_stop, scheduler)
         epochs = tr.epochs if epochs is None else int(epochs)
         mbs = tr.minibatches if minibatches is None else int(minibatches)
-        obs = obs.reshape(-1, obs.shape[-1])
-        B = obs.shape[0]
-        act = act.reshape(B, -1)
-        logp, val, ret, adv = (x.reshape(B) for x in (logp, val, ret, adv))
-        for t, nm in ((obs, "obs"), (act, "act"), (logp, "logp"), (val, "val"), (ret, "ret"), (adv, "adv")):
-            tr._check(t, nm)
-        if obs.shape[1] != OBS_DIM or act.shape[1] != 2:
-            raise ValueError("obs must be (B, 965) and act (B, 2)")
+        obs, act, logp, val, ret, adv, B = tr._flat_rollout(obs, act, logp=logp, val=val, ret=ret, adv=adv)
         if self._image.shape[0] < B:
             self._image = torch.empty(B, OBS_DIM, dtype=torch.float32, device=self.device)
         image = self._image[:B]
-        kls = torch.empty(epochs, device=self.device)
-        if gated:
-            stats = torch.full((epochs, mbs, 4), float("nan"), device=self.device)
-            tr.epoch_state.zero_()
-            snaps = torch.empty(epochs, 8, dtype=torch.int32, device=self.device)
-        else:
-            stats = torch.empty(epochs, mbs, 4, device=self.device)
-        tr.last_stats = stats
-        for e in range(epochs):
-            perm = perms[e] if perms is not None else torch.randperm(B, device=self.device)
-            chunks = perm.chunk(mbs)
-            if len(chunks) != mbs:
-                raise ValueError(f"{B} rows do not make {mbs} minibatches")
-            for j, mb in enumerate(chunks):
-                mb = mb.contiguous()
-                if e == 0:                      # skrl: state_preprocessor(states, train=not epoch)
-                    if train_state_scaler:
-                        self.state_scaler.train(obs, mb, gate=tr.epoch_state if gated else None)
-                    self.state_scaler.forward(obs, mb, out=image)
-                if gated:
-                    tr.minibatch_gated(image, act, logp, val, ret, adv, mb, stats[e, j], kl_early_stop)
-                    tr.apply_gated()
-                else:
-                    tr.minibatch(image, act, logp, val, ret, adv, mb, stats=stats[e, j])
-                    tr.apply()
-            if e == 0 and epochs > 1:           # the statistics are final: one pass, then no scaler work in the later epochs
+        gate = tr.epoch_state if gated else None
+
+        def before(e, mb):
+            if e == 0:                          # skrl: state_preprocessor(states, train=not epoch)
+                if train_state_scaler:
+                    self.state_scaler.train(obs, mb, gate=gate)
+                self.state_scaler.forward(obs, mb, out=image)
+
+        def after_first():                      # the statistics are final: one pass, then no scaler work in the later epochs
+            if epochs > 1:
                 self.state_scaler.forward(obs, out=image)
-            if gated:
-                snaps[e].copy_(tr.epoch_state)
-                tr.epoch_end(stats[e], scheduler is not None, kls[e:e + 1])
-            else:
-                tr.kl_schedule(stats[e], kls[e:e + 1])
-        if gated:
-            return tr._finish_gated(kls, snaps)
-        tr.last_update = None
-        return kls.cpu().tolist(), tr.lr
+
+        return tr._epochs(image, act, logp, val, ret, adv, perms, epochs, mbs, gated, kl_early_stop, scheduler, before, after_first)

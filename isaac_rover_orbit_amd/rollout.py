@@ -21,7 +21,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _fused, _lib
+from ._fused import f32_cuda, holds, launch, ptr
 
 ROLLOUT_TAG = 0x524F4C00          # "ROL\0": word 3 of the Philox counter, | action pair (the env's draws have word 3 in {0, 1, 2})
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
@@ -152,7 +153,6 @@ def rollout_act(actor, critic, log_std: torch.Tensor, raw_obs: torch.Tensor, cou
                 obs_out=None, mean_out=None, val_out=None, act_out=None, env_act_out=None, logp_out=None, eps_out=None):
     """One ``rover_rollout_act`` launch on the current stream; ``mean_out`` / ``val_out`` are allocated when not given, every other
     output left ``None`` is passed as NULL (not computed).  Returns ``(mean_out, val_out)``."""
-    lib = _lib.load()
     n = int(raw_obs.shape[0])
     f = dict(dtype=torch.float32, device=raw_obs.device)
     if mean_out is None:
@@ -161,26 +161,30 @@ def rollout_act(actor, critic, log_std: torch.Tensor, raw_obs: torch.Tensor, cou
         val_out = torch.empty(n, critic.out_dim, **f)
     if actor.n_copies != critic.n_copies:
         raise ValueError("actor and critic must hold the same number of packed replicas")
-    for name, t in (("raw_obs", raw_obs), ("log_std", log_std), ("obs_out", obs_out), ("mean_out", mean_out), ("val_out", val_out),
-                    ("act_out", act_out), ("env_act_out", env_act_out), ("logp_out", logp_out), ("eps_out", eps_out)):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.device != actor.packed.device):
-            raise ValueError(f"{name} must be a contiguous float32 cuda tensor on the networks' device")
-    if log_std.numel() != actor.out_dim:
-        raise ValueError(f"log_std must hold {actor.out_dim} values")
-    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    stream = C.c_void_p(torch.cuda.current_stream(raw_obs.device).cuda_stream)
-    with torch.cuda.device(raw_obs.device):
-        _lib.check(lib.rover_rollout_act(C.byref(actor.desc), actor.packed.data_ptr(), C.byref(critic.desc), critic.packed.data_ptr(),
-                                         actor.n_copies, C.byref(hp), C.c_uint64(int(counter)), raw_obs.data_ptr(), n, log_std.data_ptr(),
-                                         ptr(obs_out), mean_out.data_ptr(), val_out.data_ptr(), ptr(act_out), ptr(env_act_out),
-                                         ptr(logp_out), ptr(eps_out), stream), "rover_rollout_act")
+    A = actor.out_dim
+    for name, t, shape in (("raw_obs", raw_obs, (n, 965)), ("log_std", log_std, A), ("obs_out", obs_out, (n, 965)),
+                           ("mean_out", mean_out, (n, A)), ("val_out", val_out, (n, critic.out_dim)), ("act_out", act_out, (n, A)),
+                           ("env_act_out", env_act_out, (n, A)), ("logp_out", logp_out, (n,)), ("eps_out", eps_out, (n, A))):
+        f32_cuda(name, t, actor.packed.device, "the networks' device")
+        holds(name, t, shape)
+    launch("rover_rollout_act", raw_obs.device, C.byref(actor.desc), actor.packed.data_ptr(), C.byref(critic.desc),
+           critic.packed.data_ptr(), actor.n_copies, C.byref(hp), C.c_uint64(int(counter)), raw_obs.data_ptr(), n, log_std.data_ptr(),
+           ptr(obs_out), mean_out.data_ptr(), val_out.data_ptr(), ptr(act_out), ptr(env_act_out), ptr(logp_out), ptr(eps_out))
     return mean_out, val_out
 
 
 def default_hparams() -> "_lib.RolloutHparams":
-    hp = _lib.RolloutHparams()
-    _lib.check(_lib.load().rover_rollout_default_hparams(C.byref(hp)), "rover_rollout_default_hparams")
-    return hp
+    return _fused.default_hparams(_lib.RolloutHparams, "rover_rollout_default_hparams")
+
+
+def _transition(n: int, device, *named) -> None:
+    """Refuses a reward / flag / output tensor, given as (name, tensor, dtypes), that is not ``n`` contiguous values on ``device``."""
+    for name, x, dts in named:
+        if not x.is_cuda or x.dtype not in dts or not x.is_contiguous() or x.numel() != n or x.device != device:
+            raise ValueError(f"{name} must be a contiguous {dts[0]} cuda tensor of {n} elements")
+
+
+_FLAG = (torch.bool, torch.uint8)
 
 
 class RolloutCollector(_RolloutBase):
@@ -194,8 +198,7 @@ class RolloutCollector(_RolloutBase):
 
     def __init__(self, actor, critic, log_std: torch.Tensor, num_envs: int, horizon: int, seed: int = 42, env_id_offset: int = 0,
                  clip_actions: bool = True):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("RolloutCollector needs a ROCm GPU (no CPU fallback; TorchRollout is the CPU specification)")
+        _fused.require_gpu("RolloutCollector", "TorchRollout is the CPU specification")
         if not log_std.is_cuda or log_std.dtype != torch.float32:
             raise ValueError("log_std must be a float32 cuda tensor (a view into the trainer's parameters works as it is)")
         super().__init__(log_std, num_envs, horizon, seed, env_id_offset, clip_actions, actor.packed.device)
@@ -210,9 +213,8 @@ class RolloutCollector(_RolloutBase):
             raise ValueError("the critic must have one output")
 
     def hparams(self) -> "_lib.RolloutHparams":
-        hp = default_hparams()
-        hp.seed_lo, hp.seed_hi = self.seed & _MASK, (self.seed >> 32) & _MASK
-        hp.env_id_offset, hp.clip_actions = self.env_id_offset, int(self.clip_actions)
+        hp = _fused.seeded(default_hparams(), self.seed, self.env_id_offset)
+        hp.clip_actions = int(self.clip_actions)
         return hp
 
     @torch.no_grad()
@@ -232,21 +234,15 @@ class RolloutCollector(_RolloutBase):
         """Slot ``t`` of ``rew`` / ``done``.  ``rewards_shaper_scale`` (a float; the reference's ``reward_shaper_function``) and
         ``time_limit_bootstrap`` (skrl: ``rewards += discount * values * truncated``, with slot ``t`` of ``val``, the value of the
         pre-step states) take ``rover_rollout_record_shaped``; both at their defaults: the plain launch."""
-        for name, x, dts in (("rew", rew, (torch.float32,)), ("terminated", terminated, (torch.bool, torch.uint8)),
-                             ("truncated", truncated, (torch.bool, torch.uint8))):
-            if not x.is_cuda or x.dtype not in dts or not x.is_contiguous() or x.numel() != self.n or x.device != self.device:
-                raise ValueError(f"{name} must be a contiguous {dts[0]} cuda tensor of {self.n} elements")
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            if rewards_shaper_scale is not None or time_limit_bootstrap:
-                scale = 1.0 if rewards_shaper_scale is None else float(rewards_shaper_scale)
-                _lib.check(self._lib.rover_rollout_record_shaped(rew.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
-                                                                 self.val[t].data_ptr(), self.n, scale, float(discount),
-                                                                 int(bool(time_limit_bootstrap)), self.rew[t].data_ptr(),
-                                                                 self.done[t].data_ptr(), stream), "rover_rollout_record_shaped")
-                return
-            _lib.check(self._lib.rover_rollout_record(rew.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self.n,
-                                                      self.rew[t].data_ptr(), self.done[t].data_ptr(), stream), "rover_rollout_record")
+        _transition(self.n, self.device, ("rew", rew, (torch.float32,)), ("terminated", terminated, _FLAG), ("truncated", truncated, _FLAG))
+        if rewards_shaper_scale is not None or time_limit_bootstrap:
+            scale = 1.0 if rewards_shaper_scale is None else float(rewards_shaper_scale)
+            launch("rover_rollout_record_shaped", self.device, rew.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
+                   self.val[t].data_ptr(), self.n, scale, float(discount), int(bool(time_limit_bootstrap)), self.rew[t].data_ptr(),
+                   self.done[t].data_ptr())
+            return
+        launch("rover_rollout_record", self.device, rew.data_ptr(), terminated.data_ptr(), truncated.data_ptr(), self.n,
+               self.rew[t].data_ptr(), self.done[t].data_ptr())
 
     @torch.no_grad()
     def last_value(self, raw_obs) -> torch.Tensor:

@@ -29,10 +29,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
-from .policy import RoverNet
+from . import _fused, _lib
 from .ppo import pack, unpack
-from .td3 import ACT_DIM, OBS_DIM, ReplayMemory, pack_critic, update_parameters
+from .td3 import ACT_DIM, ReplayMemory, pack_critic, update_parameters
 
 # skrl SAC_DEFAULT_CONFIG with rover_sac.yaml (batch 4096, actor / critic lr 1e-4).  skrl's defaults stated from memory:
 # gradient_steps 1, discount 0.99, polyak 0.005, entropy_learning_rate 5e-3 (rover_sac.yaml), learn_entropy True,
@@ -195,7 +194,7 @@ class TorchSAC:
     @classmethod
     def from_checkpoint(cls, ck, policy: nn.Module, critic_1: nn.Module, critic_2: nn.Module, **hparams) -> "TorchSAC":
         """Loads a checkpoint (a path or the dict) into fresh modules; missing target entries start as copies."""
-        if isinstance(ck, str):
+        if isinstance(ck, str):                 # the specification keeps its own loading
             ck = torch.load(ck, map_location="cpu", weights_only=False)
         policy.load_state_dict(ck["policy"]); critic_1.load_state_dict(ck["critic_1"]); critic_2.load_state_dict(ck["critic_2"])
         spec = cls(policy, critic_1, critic_2, log_entropy_coefficient=ck.get("log_entropy_coefficient"), **hparams)
@@ -207,9 +206,7 @@ class TorchSAC:
 
 # ---------------------------------------------------------------------------------------------------------------- fused
 def default_hparams() -> "_lib.SacHparams":
-    h = _lib.SacHparams()
-    _lib.check(_lib.load().rover_sac_default_hparams(C.byref(h)), "rover_sac_default_hparams")
-    return h
+    return _fused.default_hparams(_lib.SacHparams, "rover_sac_default_hparams")
 
 
 STAT_KEYS = ("critic_loss", "q1_mean", "q2_mean", "y_mean", "policy_loss", "entropy_loss", "logp_mean", "alpha", "critic_step",
@@ -217,7 +214,7 @@ STAT_KEYS = ("critic_loss", "q1_mean", "q2_mean", "y_mean", "policy_loss", "entr
 TAIL = 8             # log_std (2 + 2 pad), log_alpha (1 + 3 pad)
 
 
-class FusedSAC:
+class FusedSAC(_fused.FusedOffPolicy):
     """SAC trainer state on the GPU: parameters, target critics, Adam moments and the device state struct (rover_sac_state).
 
     ``update`` runs one gradient step without a host synchronisation; ``stats`` reads the state (one synchronisation).  The
@@ -227,28 +224,17 @@ class FusedSAC:
     ``beta2``, ``eps``, ``target_entropy``, ``learn_entropy``).  ``polyak`` follows ``td3.FusedTD3``'s note on float32 taus.
     """
 
+    _STATE, _WORKSPACE, _PARAM_FLOATS = _lib.SacState, "rover_sac_workspace_bytes", "rover_sac_param_floats"
+    _RUNS = "the reference's Gaussian actor (Net(2, True)) and td3.Critic only (rover_sac.h)"
+    _unpack = staticmethod(unpack)
+
     def __init__(self, policy_sd: Mapping[str, torch.Tensor], critic_1_sd: Mapping[str, torch.Tensor],
                  critic_2_sd: Mapping[str, torch.Tensor], target_critic_1_sd=None, target_critic_2_sd=None,
                  log_entropy_coefficient=None, device="cuda", n_copies: int = 4, **hparams):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("FusedSAC needs a ROCm GPU (no CPU fallback)")
-        self._lib = _lib.load()
-        self.device = torch.device(device)
-        self.hp = default_hparams()
-        for k, v in hparams.items():
-            if not hasattr(self.hp, k):
-                raise TypeError(f"unknown hyper-parameter {k!r}")
-            setattr(self.hp, k, int(bool(v)) if k == "learn_entropy" else v)
+        super().__init__(default_hparams, hparams, device, n_copies, convert={"learn_entropy": lambda v: int(bool(v))})
         if "log_std_parameter" not in policy_sd:
             raise ValueError("the policy state_dict has no log_std_parameter (SAC trains the Gaussian actor, Net(2, True))")
-        self.n_copies = int(n_copies)
-        self.desc_a, pa = pack(policy_sd, "tanh")
-        self.desc_c, pc1 = pack_critic(critic_1_sd)
-        _, pc2 = pack_critic(critic_2_sd)
-        P = int(self._lib.rover_sac_param_floats(C.byref(self.desc_a), C.byref(self.desc_c)))
-        if P == 0:
-            raise _lib.RoverHipError("FusedSAC runs the reference's Gaussian actor (Net(2, True)) and td3.Critic only (rover_sac.h)")
-        self.n_a, self.n_c, self.P = pa.size, pc1.size, P
+        pa, pc1, pc2 = self._networks(pack(policy_sd, "tanh"), pack_critic(critic_1_sd), pack_critic(critic_2_sd))
         self.tail = self.n_a + 2 * self.n_c
         log_std = torch.as_tensor(policy_sd["log_std_parameter"]).detach().cpu().numpy().astype(np.float32).reshape(-1)
         if log_std.size != ACT_DIM:
@@ -257,30 +243,22 @@ class FusedSAC:
             la = np.float32(initial_log_alpha().item())
         else:
             la = np.float32(torch.as_tensor(log_entropy_coefficient).detach().cpu().reshape(-1)[0].item())
-        tail = np.zeros(P - self.tail, np.float32)
+        tail = np.zeros(self.P - self.tail, np.float32)
         tail[0:2], tail[4] = log_std, la
-        self.params = torch.from_numpy(np.concatenate([pa, pc1, pc2, tail])).to(self.device)
+        self._alloc(np.concatenate([pa, pc1, pc2, tail]))
         t1 = pack_critic(target_critic_1_sd)[1] if target_critic_1_sd is not None else pc1
         t2 = pack_critic(target_critic_2_sd)[1] if target_critic_2_sd is not None else pc2
         self.target = torch.from_numpy(np.concatenate([t1, t2])).to(self.device)
-        self.grad = torch.zeros_like(self.params)
-        self.adam_m = torch.zeros_like(self.params)
-        self.adam_v = torch.zeros_like(self.params)
         self.state = torch.zeros(C.sizeof(_lib.SacState) // 4, dtype=torch.int32, device=self.device)
-        self.rep_a = self.params[:self.n_a].repeat(self.n_copies)
-        self.actor = RoverNet.from_packed(self.desc_a, self.rep_a, self.n_copies)
         self.log_std = self.params[self.tail:self.tail + ACT_DIM]
         self.log_alpha = self.params[self.tail + 4:self.tail + 5]
-        self.ws = torch.empty(0, dtype=torch.uint8, device=self.device)
 
-    @classmethod
-    def from_checkpoint(cls, ck, **kw) -> "FusedSAC":
-        """A checkpoint with ``CHECKPOINT_KEYS`` (a path or the loaded dict); missing target entries start as copies, a
-        missing ``log_entropy_coefficient`` as log(initial_entropy_value)."""
-        if isinstance(ck, str):
-            ck = torch.load(ck, map_location="cpu", weights_only=False)
-        return cls(ck["policy"], ck["critic_1"], ck["critic_2"], ck.get("target_critic_1"), ck.get("target_critic_2"),
-                   ck.get("log_entropy_coefficient"), **kw)
+    @staticmethod
+    def _checkpoint_args(ck):
+        """A checkpoint with ``CHECKPOINT_KEYS``; missing target entries start as copies, a missing ``log_entropy_coefficient`` as
+        log(initial_entropy_value)."""
+        return (ck["policy"], ck["critic_1"], ck["critic_2"], ck.get("target_critic_1"), ck.get("target_critic_2"),
+                ck.get("log_entropy_coefficient"))
 
     # ---- views
     def blocks(self, vec: torch.Tensor) -> dict:
@@ -288,18 +266,16 @@ class FusedSAC:
         a, c = self.n_a, self.n_c
         if vec.numel() == 2 * c:
             return {"critic_1": vec[:c], "critic_2": vec[c:2 * c]}
-        return {"policy": vec[:a], "critic_1": vec[a:a + c], "critic_2": vec[a + c:a + 2 * c],
-                "log_std": vec[self.tail:self.tail + ACT_DIM], "log_alpha": vec[self.tail + 4:self.tail + 5]}
+        return {**super().blocks(vec), "log_std": vec[self.tail:self.tail + ACT_DIM], "log_alpha": vec[self.tail + 4:self.tail + 5]}
 
     def unvector(self, vec: torch.Tensor) -> dict:
         """state_dict-shaped float32 CPU tensors of each block of a vector in either layout; the policy's entry holds
         ``log_std_parameter``, ``log_entropy_coefficient`` is a 1-element tensor."""
-        b = {k: v.detach().cpu() for k, v in self.blocks(vec).items()}
-        out = {"critic_1": unpack(self.desc_c, b["critic_1"]), "critic_2": unpack(self.desc_c, b["critic_2"])}
-        if "policy" in b:
-            out["policy"] = unpack(self.desc_a, b["policy"])
-            out["policy"]["log_std_parameter"] = b["log_std"].clone()
-            out["log_entropy_coefficient"] = b["log_alpha"].clone()
+        out = super().unvector(vec)
+        if "policy" in out:
+            b = self.blocks(vec)
+            out["policy"]["log_std_parameter"] = b["log_std"].detach().cpu().clone()
+            out["log_entropy_coefficient"] = b["log_alpha"].detach().cpu().clone()
         return out
 
     def state_dict(self) -> dict:
@@ -308,41 +284,13 @@ class FusedSAC:
         return {"policy": p["policy"], "critic_1": p["critic_1"], "critic_2": p["critic_2"], "target_critic_1": t["critic_1"],
                 "target_critic_2": t["critic_2"], "log_entropy_coefficient": p["log_entropy_coefficient"]}
 
-    def stats(self) -> dict:
-        """The device state struct (one host synchronisation)."""
-        st = _lib.SacState.from_buffer_copy(self.state.cpu().numpy().tobytes())
-        return {f: getattr(st, f) for f, _ in _lib.SacState._fields_ if f != "reserved"}
-
     # ---- kernels
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _ensure_ws(self, rows: int):
-        need = int(self._lib.rover_sac_workspace_bytes(rows))
-        if self.ws.numel() < need:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-
-    def _sample(self, memory: ReplayMemory, idx: torch.Tensor, eps: torch.Tensor):
-        if memory.obs.device != self.params.device or not idx.is_cuda or idx.dtype != torch.int64 or not idx.is_contiguous():
-            raise ValueError("idx must be a contiguous int64 cuda tensor on the memory's device")
-        if memory.obs.shape[-1] != OBS_DIM or memory.actions.shape[-1] != ACT_DIM:
-            raise ValueError("the memory must hold 965-wide observations and 2-wide actions")
-        if len(memory) == 0:
-            raise ValueError("the memory is empty")
-        n = int(idx.numel())
+    def _sample(self, memory: ReplayMemory, idx: torch.Tensor, eps: torch.Tensor) -> int:
+        n = super()._sample(memory, idx)
         if (not torch.is_tensor(eps) or eps.device != self.params.device or eps.dtype != torch.float32 or not eps.is_contiguous()
                 or eps.dim() != 2 or tuple(eps.shape) != (n, 4)):
             raise ValueError("eps must be a contiguous float32 cuda tensor of (n, 4) on the memory's device")
-        self._ensure_ws(n)
         return n
-
-    @staticmethod
-    def _out(t, numel, name):
-        if t is None:
-            return None
-        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
-            raise ValueError(f"{name} must be a contiguous float32 cuda tensor of {numel} floats")
-        return t.data_ptr()
 
     def critic_step(self, memory: ReplayMemory, idx: torch.Tensor, eps: torch.Tensor, y_out: torch.Tensor | None = None):
         n = self._sample(memory, idx, eps)

@@ -31,10 +31,11 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _fused, _lib
+from ._fused import f32_cuda, launch, ptr
 from .rollout import _MASK, philox4x32, standard_normals, unit_uniform
 from .td3 import ACT_DIM, ReplayMemory
-from .td3_collect import TorchTD3Collector, _f32_cuda, _FusedCollector, _launch, _launch_act, _ptr
+from .td3_collect import TorchTD3Collector, _FusedCollector, _launch_act
 from .td3_explore import SAC_ACTION_TAG as ACTION_TAG  # "SAC\0": word 3 of the Philox counter of the action draws, | action pair
 from .td3_explore import SAC_RANDOM_TAG as RANDOM_TAG  # "SAR\0": ... of the random steps' uniforms, | action quad
 from .td3_explore import smooth_normals
@@ -186,9 +187,7 @@ class TorchSACCollector(_SacModeMixin, TorchTD3Collector):
 
 # ---------------------------------------------------------------------------------------------------------------- the kernels
 def default_hparams() -> "_lib.SacCollectHparams":
-    hp = _lib.SacCollectHparams()
-    _lib.check(_lib.load().rover_sac_collect_default_hparams(C.byref(hp)), "rover_sac_collect_default_hparams")
-    return hp
+    return _fused.default_hparams(_lib.SacCollectHparams, "rover_sac_collect_default_hparams")
 
 
 def collect_act(actor, log_std, rows: torch.Tensor, counter: int, hp: "_lib.SacCollectHparams", act_out: torch.Tensor,
@@ -199,8 +198,8 @@ def collect_act(actor, log_std, rows: torch.Tensor, counter: int, hp: "_lib.SacC
     wide = (("act_out", act_out), ("env_act_out", env_act_out), ("mean_out", mean_out), ("eps_out", eps_out))
     narrow = (("log_std", log_std, ACT_DIM), ("logp_out", logp_out, n), ("sigma_out", sigma_out, ACT_DIM))
     _launch_act("rover_sac_collect_act", actor, rows, ACT_DIM, wide, narrow, C.byref(actor.desc), actor.packed.data_ptr(),
-                actor.n_copies, _ptr(log_std), C.byref(hp), C.c_uint64(int(counter)), rows.data_ptr(), n, _ptr(mean_out),
-                act_out.data_ptr(), env_act_out.data_ptr(), _ptr(eps_out), _ptr(logp_out), _ptr(sigma_out))
+                actor.n_copies, ptr(log_std), C.byref(hp), C.c_uint64(int(counter)), rows.data_ptr(), n, ptr(mean_out),
+                act_out.data_ptr(), env_act_out.data_ptr(), ptr(eps_out), ptr(logp_out), ptr(sigma_out))
 
 
 def collect_record(raw: torch.Tensor, ring_slot: torch.Tensor, hp: "_lib.SacCollectHparams", counter: int = 0, *, rew=None,
@@ -218,9 +217,9 @@ def collect_record(raw: torch.Tensor, ring_slot: torch.Tensor, hp: "_lib.SacColl
         if idx_out is not None and int(eps_out.shape[0]) != batch:
             raise ValueError("idx_out and eps_out must hold the same batch")
         batch = int(eps_out.shape[0])
-    _launch("rover_sac_collect_record", raw.device, raw.data_ptr(), n, ring_slot.data_ptr(), _ptr(rew), _ptr(terminated), _ptr(rew_out),
-            _ptr(term_out), _ptr(ring_pos_entry), int(ring_pos_value), _ptr(idx_out), batch, int(mem_rows), _ptr(eps_out), C.byref(hp),
-            C.c_uint64(int(counter)))
+    launch("rover_sac_collect_record", raw.device, raw.data_ptr(), n, ring_slot.data_ptr(), ptr(rew), ptr(terminated), ptr(rew_out),
+           ptr(term_out), ptr(ring_pos_entry), int(ring_pos_value), ptr(idx_out), batch, int(mem_rows), ptr(eps_out), C.byref(hp),
+           C.c_uint64(int(counter)))
 
 
 class SACCollector(_SacModeMixin, _FusedCollector):
@@ -242,7 +241,7 @@ class SACCollector(_SacModeMixin, _FusedCollector):
         self.log_std = log_std
         if actor.out_dim != ACT_DIM:
             raise ValueError("the actor must have 2 outputs")
-        _f32_cuda("log_std", log_std, actor.packed.device)
+        f32_cuda("log_std", log_std, actor.packed.device)
         if log_std.numel() != ACT_DIM:
             raise ValueError("log_std must hold 2 floats")
 

@@ -12,13 +12,11 @@ from typing import Mapping
 
 import torch
 
-from . import _lib
+from . import _fused, _lib
 
 
 def default_hparams() -> "_lib.ScalerHparams":
-    h = _lib.ScalerHparams()
-    _lib.check(_lib.load().rover_scaler_default_hparams(C.byref(h)), "rover_scaler_default_hparams")
-    return h
+    return _fused.default_hparams(_lib.ScalerHparams, "rover_scaler_default_hparams")
 
 
 class DeviceScaler:
@@ -26,8 +24,7 @@ class DeviceScaler:
     holds the scaler (a trainer and a rollout collector, say) sees every update at once."""
 
     def __init__(self, width: int, device="cuda", epsilon: float = 1e-8, clip_threshold: float = 5.0):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("DeviceScaler needs a ROCm GPU (no CPU fallback; lift_ppo.RunningStandardScaler is the specification)")
+        _fused.require_gpu("DeviceScaler", "lift_ppo.RunningStandardScaler is the specification")
         self._lib = _lib.load()
         self.width = int(width)
         n = int(self._lib.rover_scaler_doubles(self.width))
@@ -71,7 +68,7 @@ class DeviceScaler:
 
     # ---- kernels
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _fused.stream(self.device)
 
     def _rows(self, x: torch.Tensor, name: str) -> torch.Tensor:
         if not x.is_cuda or x.dtype != torch.float32 or x.device != self.block.device:

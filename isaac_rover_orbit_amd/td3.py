@@ -30,8 +30,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
-from .policy import RoverNet
+from . import _fused, _lib
+from ._fused import ptr
 from .ppo import _layers, pack, unpack
 
 # skrl TD3_DEFAULT_CONFIG with rover_td3.yaml (batch 4096, actor / critic lr 1e-4).  skrl's defaults stated from memory:
@@ -266,9 +266,7 @@ class TorchTD3:
 
 # ---------------------------------------------------------------------------------------------------------------- fused
 def default_hparams() -> "_lib.Td3Hparams":
-    h = _lib.Td3Hparams()
-    _lib.check(_lib.load().rover_td3_default_hparams(C.byref(h)), "rover_td3_default_hparams")
-    return h
+    return _fused.default_hparams(_lib.Td3Hparams, "rover_td3_default_hparams")
 
 
 def critic_desc() -> "_lib.PolicyDesc":
@@ -282,19 +280,14 @@ def pack_critic(sd: Mapping[str, torch.Tensor]):
     ws, bs, n_enc = _layers(sd)
     if n_enc != 2 or len(ws) != 6:
         raise ValueError("not a Critic state_dict (2 encoder and 4 MLP layers)")
-    lib = _lib.load()
     desc = critic_desc()
-    packed = np.empty(int(lib.rover_policy_packed_floats(C.byref(desc))), dtype=np.float32)
-    wp = (C.c_void_p * 6)(*[w.ctypes.data for w in ws])
-    bp = (C.c_void_p * 6)(*[b.ctypes.data for b in bs])
-    _lib.check(lib.rover_td3_critic_pack(C.byref(desc), wp, bp, packed.ctypes.data), "rover_td3_critic_pack")
-    return desc, packed
+    return desc, _fused.pack_layers(desc, ws, bs, "rover_td3_critic_pack")
 
 
 STAT_KEYS = ("critic_loss", "q1_mean", "q2_mean", "y_mean", "policy_loss", "critic_step", "actor_step", "bad_index")
 
 
-class FusedTD3:
+class FusedTD3(_fused.FusedOffPolicy):
     """TD3 trainer state on the GPU: parameters, targets, Adam moments and the device state struct (rover_td3_state).
 
     ``update`` runs one gradient step without a host synchronisation; ``stats`` reads the state (one synchronisation).  The
@@ -306,117 +299,61 @@ class FusedTD3:
     ``rover_td3_polyak`` in rover_td3.h).  ``polyak = 1`` copies the parameters.
     """
 
+    _STATE, _WORKSPACE, _PARAM_FLOATS = _lib.Td3State, "rover_td3_workspace_bytes", "rover_td3_param_floats"
+    _RUNS = "the reference actor (Net(2, False)) and td3.Critic only (rover_td3.h)"
+    _unpack = staticmethod(unpack)
+
     def __init__(self, policy_sd: Mapping[str, torch.Tensor], critic_1_sd: Mapping[str, torch.Tensor],
                  critic_2_sd: Mapping[str, torch.Tensor], target_policy_sd=None, target_critic_1_sd=None, target_critic_2_sd=None,
                  policy_delay: int = 2, device="cuda", n_copies: int = 4, **hparams):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("FusedTD3 needs a ROCm GPU (no CPU fallback)")
-        self._lib = _lib.load()
-        self.device = torch.device(device)
-        self.hp = default_hparams()
-        for k, v in hparams.items():
-            if not hasattr(self.hp, k):
-                raise TypeError(f"unknown hyper-parameter {k!r}")
-            setattr(self.hp, k, v)
-        self.policy_delay, self.n_copies, self.critic_updates = int(policy_delay), int(n_copies), 0
-        self.desc_a, pa = pack(policy_sd, "none")
-        self.desc_c, pc1 = pack_critic(critic_1_sd)
-        _, pc2 = pack_critic(critic_2_sd)
-        P = int(self._lib.rover_td3_param_floats(C.byref(self.desc_a), C.byref(self.desc_c)))
-        if P == 0:
-            raise _lib.RoverHipError("FusedTD3 runs the reference actor (Net(2, False)) and td3.Critic only (rover_td3.h)")
-        self.n_a, self.n_c, self.P = pa.size, pc1.size, P
-        self.params = self._vector(pa, pc1, pc2)
+        super().__init__(default_hparams, hparams, device, n_copies)
+        self.policy_delay, self.critic_updates = int(policy_delay), 0
+        pa, pc1, pc2 = self._networks(pack(policy_sd, "none"), pack_critic(critic_1_sd), pack_critic(critic_2_sd))
         tp = pack(target_policy_sd, "none")[1] if target_policy_sd is not None else pa
         t1 = pack_critic(target_critic_1_sd)[1] if target_critic_1_sd is not None else pc1
         t2 = pack_critic(target_critic_2_sd)[1] if target_critic_2_sd is not None else pc2
-        self.target = self._vector(tp, t1, t2)
-        self.grad = torch.zeros_like(self.params)
-        self.adam_m = torch.zeros_like(self.params)
-        self.adam_v = torch.zeros_like(self.params)
+        self._alloc(self._vector(pa, pc1, pc2))
+        self.target = torch.from_numpy(self._vector(tp, t1, t2)).to(self.device)
         self.state = torch.zeros(C.sizeof(_lib.Td3State) // 4, dtype=torch.int32, device=self.device)
-        self.rep_a = self.params[:self.n_a].repeat(self.n_copies)
-        self.actor = RoverNet.from_packed(self.desc_a, self.rep_a, self.n_copies)
-        self.ws = torch.empty(0, dtype=torch.uint8, device=self.device)
 
-    def _vector(self, pa, pc1, pc2) -> torch.Tensor:
-        flat = np.concatenate([pa, pc1, pc2, np.zeros(self.P - pa.size - pc1.size - pc2.size, np.float32)])
-        return torch.from_numpy(flat).to(self.device)
+    def _vector(self, pa, pc1, pc2) -> np.ndarray:
+        return np.concatenate([pa, pc1, pc2, np.zeros(self.P - pa.size - pc1.size - pc2.size, np.float32)])
 
-    @classmethod
-    def from_checkpoint(cls, ck, **kw) -> "FusedTD3":
-        """skrl TD3 checkpoint ``{"policy", "target_policy", "critic_1", "critic_2", "target_critic_1", "target_critic_2"}`` (a
-        path or the loaded dict); missing target entries start as copies."""
-        if isinstance(ck, str):
-            ck = torch.load(ck, map_location="cpu", weights_only=False)
-        return cls(ck["policy"], ck["critic_1"], ck["critic_2"], ck.get("target_policy"), ck.get("target_critic_1"),
-                   ck.get("target_critic_2"), **kw)
+    @staticmethod
+    def _checkpoint_args(ck):
+        """skrl TD3 checkpoint ``{"policy", "target_policy", "critic_1", "critic_2", "target_critic_1", "target_critic_2"}``;
+        missing target entries start as copies."""
+        return (ck["policy"], ck["critic_1"], ck["critic_2"], ck.get("target_policy"), ck.get("target_critic_1"),
+                ck.get("target_critic_2"))
 
     # ---- views
-    def blocks(self, vec: torch.Tensor) -> dict:
-        """The actor / critic_1 / critic_2 slices of a vector in this layout."""
-        a, c = self.n_a, self.n_c
-        return {"policy": vec[:a], "critic_1": vec[a:a + c], "critic_2": vec[a + c:a + 2 * c]}
-
-    def unvector(self, vec: torch.Tensor) -> dict:
-        """state_dict-shaped float32 CPU tensors of each network block of a vector in this layout."""
-        b = {k: v.detach().cpu() for k, v in self.blocks(vec).items()}
-        return {"policy": unpack(self.desc_a, b["policy"]), "critic_1": unpack(self.desc_c, b["critic_1"]),
-                "critic_2": unpack(self.desc_c, b["critic_2"])}
-
     def state_dict(self) -> dict:
         """skrl TD3 checkpoint keys; state dicts that ``Net(2, False)`` / ``Critic`` load (float32 CPU tensors)."""
         p, t = self.unvector(self.params), self.unvector(self.target)
         return {"policy": p["policy"], "target_policy": t["policy"], "critic_1": p["critic_1"], "critic_2": p["critic_2"],
                 "target_critic_1": t["critic_1"], "target_critic_2": t["critic_2"]}
 
-    def stats(self) -> dict:
-        """The device state struct (one host synchronisation)."""
-        st = _lib.Td3State.from_buffer_copy(self.state.cpu().numpy().tobytes())
-        return {f: getattr(st, f) for f, _ in _lib.Td3State._fields_ if f != "reserved"}
-
     # ---- kernels
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _ensure_ws(self, rows: int):
-        need = int(self._lib.rover_td3_workspace_bytes(rows))
-        if self.ws.numel() < need:
-            self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-
-    def _sample(self, memory: ReplayMemory, idx: torch.Tensor):
-        if memory.obs.device != self.params.device or not idx.is_cuda or idx.dtype != torch.int64 or not idx.is_contiguous():
-            raise ValueError("idx must be a contiguous int64 cuda tensor on the memory's device")
-        if memory.obs.shape[-1] != OBS_DIM or memory.actions.shape[-1] != ACT_DIM:
-            raise ValueError("the memory must hold 965-wide observations and 2-wide actions")
-        if len(memory) == 0:
-            raise ValueError("the memory is empty")
-        n = int(idx.numel())
-        self._ensure_ws(n)
-        return n
-
     def critic_step(self, memory: ReplayMemory, idx: torch.Tensor, noise: torch.Tensor | None = None, y_out: torch.Tensor | None = None):
         n = self._sample(memory, idx)
         if noise is not None and (not noise.is_cuda or noise.dtype != torch.float32 or not noise.is_contiguous()
                                   or noise.numel() != 2 * n):
             raise ValueError("noise must be a contiguous float32 cuda tensor of (n, 2)")
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         _lib.check(self._lib.rover_td3_critic_step(
             C.byref(self.desc_a), C.byref(self.desc_c), C.byref(self.hp), self.params.data_ptr(), self.target.data_ptr(),
             self.grad.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(), memory.obs.data_ptr(), memory.slots, memory.num_envs,
             memory.ring_pos.data_ptr(), memory.actions.data_ptr(), memory.rewards.data_ptr(), memory.terminated.data_ptr(),
-            idx.data_ptr(), n, len(memory), ptr(noise), self.ws.data_ptr(), self.ws.numel(), self.state.data_ptr(), ptr(y_out),
-            self._stream()), "rover_td3_critic_step")
+            idx.data_ptr(), n, len(memory), ptr(noise), self.ws.data_ptr(), self.ws.numel(), self.state.data_ptr(),
+            self._out(y_out, n, "y_out"), self._stream()), "rover_td3_critic_step")
         self.critic_updates += 1
 
     def actor_step(self, memory: ReplayMemory, idx: torch.Tensor, dact_out: torch.Tensor | None = None):
         n = self._sample(memory, idx)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         _lib.check(self._lib.rover_td3_actor_step(
             C.byref(self.desc_a), C.byref(self.desc_c), C.byref(self.hp), self.params.data_ptr(), self.grad.data_ptr(),
             self.adam_m.data_ptr(), self.adam_v.data_ptr(), memory.obs.data_ptr(), memory.slots, memory.num_envs,
             memory.ring_pos.data_ptr(), idx.data_ptr(), n, len(memory), self.ws.data_ptr(), self.ws.numel(), self.state.data_ptr(),
-            self.rep_a.data_ptr(), self.n_copies, ptr(dact_out), self._stream()), "rover_td3_actor_step")
+            self.rep_a.data_ptr(), self.n_copies, self._out(dact_out, 2 * n, "dact_out"), self._stream()), "rover_td3_actor_step")
 
     def polyak(self):
         _lib.check(self._lib.rover_td3_polyak(C.byref(self.hp), self.target.data_ptr(), self.params.data_ptr(), self.P, self._stream()),

@@ -27,7 +27,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _fused, _lib
+from ._fused import f32_cuda, holds, launch, ptr
 from .rollout import FLT_MAX, _MASK, philox4x32, standard_normals
 from .td3 import OBS_DIM, ReplayMemory, explore
 
@@ -153,46 +154,26 @@ class TorchTD3Collector(_CollectorBase):
 
 # ---------------------------------------------------------------------------------------------------------------- the kernels
 def default_hparams() -> "_lib.Td3CollectHparams":
-    hp = _lib.Td3CollectHparams()
-    _lib.check(_lib.load().rover_td3_collect_default_hparams(C.byref(hp)), "rover_td3_collect_default_hparams")
-    return hp
-
-
-def _f32_cuda(name: str, t, device) -> None:
-    if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.device != device):
-        raise ValueError(f"{name} must be a contiguous float32 cuda tensor on the actor's device")
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _launch(fn: str, device, *args) -> None:
-    """One call of the library's ``fn`` on the current stream of ``device``, the stream as its last argument."""
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    with torch.cuda.device(device):
-        _lib.check(getattr(_lib.load(), fn)(*args, stream), fn)
+    return _fused.default_hparams(_lib.Td3CollectHparams, "rover_td3_collect_default_hparams")
 
 
 def _launch_act(fn: str, actor, rows: torch.Tensor, width: int, wide, narrow, *args) -> None:
-    """The checks of an act wrapper, then ``_launch(fn, rows.device, *args)``: ``rows`` (n, 965); ``wide`` pairs (name, tensor of
+    """The checks of an act wrapper, then ``launch(fn, rows.device, *args)``: ``rows`` (n, 965); ``wide`` pairs (name, tensor of
     (n, width) values); ``narrow`` triples (name, tensor, number of values).  Every tensor may be ``None``."""
     device = actor.packed.device
-    _f32_cuda("rows", rows, device)
+    f32_cuda("rows", rows, device)
     for name, t, _ in narrow:
-        _f32_cuda(name, t, device)
+        f32_cuda(name, t, device)
     for name, t in wide:
-        _f32_cuda(name, t, device)
+        f32_cuda(name, t, device)
     n = int(rows.shape[0])
     if rows.dim() != 2 or rows.shape[1] != OBS_DIM:
         raise ValueError(f"rows must have shape (n, {OBS_DIM})")
     for name, t in wide:
-        if t is not None and t.numel() != n * width:
-            raise ValueError(f"{name} must hold ({n}, {width}) values")
+        holds(name, t, (n, width))
     for name, t, numel in narrow:
-        if t is not None and t.numel() != numel:
-            raise ValueError(f"{name} must hold {numel} values")
-    _launch(fn, rows.device, *args)
+        holds(name, t, numel)
+    launch(fn, rows.device, *args)
 
 
 def collect_act(actor, rows: torch.Tensor, counter: int, hp: "_lib.Td3CollectHparams", act_out: torch.Tensor,
@@ -201,17 +182,17 @@ def collect_act(actor, rows: torch.Tensor, counter: int, hp: "_lib.Td3CollectHpa
     ``eps_out`` left ``None`` are passed as NULL."""
     wide = (("act_out", act_out), ("env_act_out", env_act_out), ("mean_out", mean_out), ("eps_out", eps_out))
     _launch_act("rover_td3_collect_act", actor, rows, actor.out_dim, wide, (), C.byref(actor.desc), actor.packed.data_ptr(),
-                actor.n_copies, C.byref(hp), C.c_uint64(int(counter)), rows.data_ptr(), int(rows.shape[0]), _ptr(mean_out),
-                act_out.data_ptr(), env_act_out.data_ptr(), _ptr(eps_out))
+                actor.n_copies, C.byref(hp), C.c_uint64(int(counter)), rows.data_ptr(), int(rows.shape[0]), ptr(mean_out),
+                act_out.data_ptr(), env_act_out.data_ptr(), ptr(eps_out))
 
 
 def collect_record(raw: torch.Tensor, ring_slot: torch.Tensor, hp: "_lib.Td3CollectHparams", counter: int = 0, *, rew=None,
                    terminated=None, rew_out=None, term_out=None, ring_pos_entry=None, ring_pos_value: int = 0, idx_out=None,
                    mem_rows: int = 0) -> None:
     """One ``rover_td3_collect_record`` launch on the current stream; every argument left ``None`` is passed as NULL."""
-    _launch("rover_td3_collect_record", raw.device, raw.data_ptr(), int(raw.shape[0]), ring_slot.data_ptr(), _ptr(rew), _ptr(terminated),
-            _ptr(rew_out), _ptr(term_out), _ptr(ring_pos_entry), int(ring_pos_value), _ptr(idx_out),
-            0 if idx_out is None else int(idx_out.numel()), int(mem_rows), C.byref(hp), C.c_uint64(int(counter)))
+    launch("rover_td3_collect_record", raw.device, raw.data_ptr(), int(raw.shape[0]), ring_slot.data_ptr(), ptr(rew), ptr(terminated),
+           ptr(rew_out), ptr(term_out), ptr(ring_pos_entry), int(ring_pos_value), ptr(idx_out),
+           0 if idx_out is None else int(idx_out.numel()), int(mem_rows), C.byref(hp), C.c_uint64(int(counter)))
 
 
 class _FusedCollector(_CollectorBase):
@@ -223,8 +204,7 @@ class _FusedCollector(_CollectorBase):
     _DRAWS = False
 
     def __init__(self, memory: ReplayMemory, seed: int, env_id_offset: int, noise_std: float, clip):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError(f"{self._NAME} needs a ROCm GPU (no CPU fallback; Torch{self._NAME} is the CPU specification)")
+        _fused.require_gpu(self._NAME, f"Torch{self._NAME} is the CPU specification")
         super().__init__(memory, seed, env_id_offset, noise_std, clip)
 
     def _bind(self, actor) -> None:
@@ -236,9 +216,7 @@ class _FusedCollector(_CollectorBase):
         self._bufs: dict = {}
 
     def _seeded(self, hp):
-        hp.seed_lo, hp.seed_hi = self.seed & _MASK, (self.seed >> 32) & _MASK
-        hp.env_id_offset = self.env_id_offset
-        return hp
+        return _fused.seeded(hp, self.seed, self.env_id_offset)
 
     def _record(self, raw, ring_slot, counter=0, idx=None, eps=None, **transition) -> None:
         raise NotImplementedError

@@ -30,11 +30,12 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _fused, _lib
+from ._fused import launch, ptr
 from .lift_rollout import LIFT_ROLLOUT_TAG
 from .rollout import ROLLOUT_TAG, _MASK, philox4x32, standard_normals, unit_uniform
 from .td3 import HPARAMS, ReplayMemory, exploration_scale
-from .td3_collect import INDEX_TAG, NOISE_TAG, TD3Collector, TorchTD3Collector, _launch, _launch_act, _ptr
+from .td3_collect import INDEX_TAG, NOISE_TAG, TD3Collector, TorchTD3Collector, _launch_act
 
 RANDOM_TAG = 0x54335200           # "T3R\0": word 3 of the Philox counter of the random actions, | action quad
 SMOOTH_TAG = 0x54334E00           # "T3N\0": ... of the smoothing noise, | action pair
@@ -176,9 +177,7 @@ class TorchTD3Explorer(_ExplorerMixin, TorchTD3Collector):
 
 # ---------------------------------------------------------------------------------------------------------------- the kernels
 def default_hparams() -> "_lib.Td3ExploreHparams":
-    hp = _lib.Td3ExploreHparams()
-    _lib.check(_lib.load().rover_td3_explore_default_hparams(C.byref(hp)), "rover_td3_explore_default_hparams")
-    return hp
+    return _fused.default_hparams(_lib.Td3ExploreHparams, "rover_td3_explore_default_hparams")
 
 
 def explore_act(actor, rows: torch.Tensor, counter: int, hp: "_lib.Td3ExploreHparams", act_out: torch.Tensor,
@@ -187,16 +186,16 @@ def explore_act(actor, rows: torch.Tensor, counter: int, hp: "_lib.Td3ExploreHpa
     ``mean_out`` / ``eps_out`` left ``None`` are passed as NULL."""
     wide = (("act_out", act_out), ("env_act_out", env_act_out), ("ou_state", ou_state), ("mean_out", mean_out), ("eps_out", eps_out))
     _launch_act("rover_td3_explore_act", actor, rows, actor.out_dim, wide, (), C.byref(actor.desc), actor.packed.data_ptr(),
-                actor.n_copies, C.byref(hp), C.c_uint64(int(counter)), rows.data_ptr(), int(rows.shape[0]), _ptr(ou_state),
-                _ptr(mean_out), act_out.data_ptr(), env_act_out.data_ptr(), _ptr(eps_out))
+                actor.n_copies, C.byref(hp), C.c_uint64(int(counter)), rows.data_ptr(), int(rows.shape[0]), ptr(ou_state),
+                ptr(mean_out), act_out.data_ptr(), env_act_out.data_ptr(), ptr(eps_out))
 
 
 def smooth_draw(seed: int, counter: int, std: float, out: torch.Tensor) -> torch.Tensor:
     """One ``rover_td3_smooth_draw`` launch on the current stream into ``out`` (n, A), a contiguous float32 cuda tensor."""
     if not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 2:
         raise ValueError("out must be a contiguous float32 cuda tensor of shape (n, A)")
-    _launch("rover_td3_smooth_draw", out.device, int(seed) & _MASK, (int(seed) >> 32) & _MASK, C.c_uint64(int(counter)), float(std),
-            out.data_ptr(), int(out.shape[0]), int(out.shape[1]))
+    launch("rover_td3_smooth_draw", out.device, int(seed) & _MASK, (int(seed) >> 32) & _MASK, C.c_uint64(int(counter)), float(std),
+           out.data_ptr(), int(out.shape[0]), int(out.shape[1]))
     return out
 
 

@@ -9,22 +9,16 @@ HIP library or a GPU these functions raise.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._fused import require_gpu, stream as _stream
 from .terrain import GRADIENT_THRESHOLD, RESOLUTION, mesh_bounding_boxes, mesh_node_boxes
 
 
-def _stream(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _device(device) -> torch.device:
-    if not torch.cuda.is_available():
-        raise _lib.RoverHipError("terrain_hip needs a ROCm GPU (no CPU fallback)")
+    require_gpu("terrain_hip")
     return torch.device(device)
 
 

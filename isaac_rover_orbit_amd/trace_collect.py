@@ -32,12 +32,10 @@ re-applied on the host at the drain).
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import _lib
+from . import _fused, _lib
 from .trace import EpisodeRecorder
 
 HEADER_WORDS = 16                 # include/rover_trace.h
@@ -364,8 +362,7 @@ class TraceCollector(_TraceBase):
     number of kernel launches."""
 
     def __init__(self, *args, device=None, **kw):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("TraceCollector needs a ROCm GPU (no CPU fallback; TorchTraceCollector is the CPU model)")
+        _fused.require_gpu("TraceCollector", "TorchTraceCollector is the CPU model")
         self._lib = _lib.load()
         device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if device.type != "cuda":
@@ -386,9 +383,7 @@ class TraceCollector(_TraceBase):
         self._call("rover_trace_init", 0, self.state.data_ptr(), self.n, self.desc_cap)
 
     def _call(self, name: str, launches: int, *args) -> None:
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            _lib.check(getattr(self._lib, name)(*args, stream), name)
+        _fused.launch(name, self.device, *args)
         self.calls.append((name, launches))
 
     def _append(self, src, done) -> None:

@@ -19,14 +19,13 @@ be declared before it is tracked (its slot lives in device memory).
 from __future__ import annotations
 
 import collections
-import ctypes as C
 import json
 from typing import Callable, Iterable, Mapping, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _fused, _lib
 
 WINDOW, CHUNK, HDR_WORDS, ACC_WORDS, MAX_SLOTS = 100, 256, 220, 20, 4096
 W_N, W_SLOTS, W_HEAD, W_LEN, W_STEPS, W_WSTEPS, W_SUM, W_MAX, W_MIN, W_RING_R, W_RING_T = 0, 1, 2, 3, 4, 5, 8, 14, 17, 20, 120
@@ -401,8 +400,7 @@ class EpisodeTracker(_TrackerBase):
     def __init__(self, num_envs: int, tags: Sequence[str] = (), write_interval: int = 40, clear_window_on_write: bool = True,
                  device="cuda", writer=None, callback=None):
         super().__init__(num_envs, tags, write_interval, clear_window_on_write, writer, callback)
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("EpisodeTracker needs a ROCm GPU (no CPU fallback; tracker.TorchEpisodeTracker is the specification)")
+        _fused.require_gpu("EpisodeTracker", "tracker.TorchEpisodeTracker is the specification")
         self._lib = _lib.load()
         nbytes = int(self._lib.rover_tracker_state_bytes(self.num_envs, self.slots))
         if nbytes != 4 * state_words(self.num_envs, self.slots):
@@ -414,7 +412,7 @@ class EpisodeTracker(_TrackerBase):
         _lib.check(self._lib.rover_tracker_init(self.state.data_ptr(), self.num_envs, self.slots, self._stream()), "rover_tracker_init")
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _fused.stream(self.device)
 
     def _vec(self, x: torch.Tensor, name: str, dtypes, numel: int | None = None) -> torch.Tensor:
         if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != self.device or x.dtype not in dtypes:

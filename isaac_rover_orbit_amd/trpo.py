@@ -18,8 +18,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
-from .policy import RoverNet
+from . import _fused, _lib
+from ._fused import ptr
 from .ppo import LOG_STD_KEY, pack, unpack
 
 # skrl TRPO_DEFAULT_CONFIG with rover_trpo.yaml.  The yaml's learning_rate (1e-4) is not a TRPO key: skrl's TRPO reads
@@ -201,75 +201,33 @@ class TorchTRPO:
 
 # ---------------------------------------------------------------------------------------------------------------- fused
 def default_hparams() -> "_lib.TrpoHparams":
-    h = _lib.TrpoHparams()
-    _lib.check(_lib.load().rover_trpo_default_hparams(C.byref(h)), "rover_trpo_default_hparams")
-    return h
+    return _fused.default_hparams(_lib.TrpoHparams, "rover_trpo_default_hparams")
 
 
 STAT_KEYS = ("loss_old", "cg_iters", "cg_rr", "xhx", "step", "accepted", "kl", "value_loss")
 
 
-class FusedTRPO:
+class FusedTRPO(_fused.FusedActorCritic):
     """TRPO trainer state on the GPU: parameters, value Adam moments and the device state struct (rover_trpo_state).
 
-    ``update`` synchronises with the host once, at its end, to return the statistics.
+    ``update`` synchronises with the host once, at its end, to return the statistics.  ``from_checkpoint`` takes a skrl checkpoint
+    ``{"policy": state_dict, "value": state_dict, ...}`` (a path or the loaded dict).
     """
+
+    _STATE, _WORKSPACE, _PARAM_FLOATS = _lib.TrpoState, "rover_trpo_workspace_bytes", "rover_trpo_param_floats"
+    _RUNS = "the reference architecture only (rover_trpo.h)"
+    _PAD = 2
+    _unpack = staticmethod(unpack)
 
     def __init__(self, policy_sd: Mapping[str, torch.Tensor], value_sd: Mapping[str, torch.Tensor], epochs: int = 4,
                  minibatches: int = 60, device="cuda", n_copies: int = 4, **hparams):
-        if not torch.cuda.is_available():
-            raise _lib.RoverHipError("FusedTRPO needs a ROCm GPU (no CPU fallback)")
-        self._lib = _lib.load()
-        self.device = torch.device(device)
-        self.hp = default_hparams()
-        for k, v in hparams.items():
-            if not hasattr(self.hp, k):
-                raise TypeError(f"unknown hyper-parameter {k!r}")
-            setattr(self.hp, k, v)
-        self.epochs, self.minibatches, self.n_copies = int(epochs), int(minibatches), int(n_copies)
-        self.desc_p, pa = pack(policy_sd, "tanh")
-        self.desc_v, pv = pack(value_sd, "none")
-        P = int(self._lib.rover_trpo_param_floats(C.byref(self.desc_p), C.byref(self.desc_v)))
-        if P == 0:
-            raise _lib.RoverHipError("FusedTRPO runs the reference architecture only (rover_trpo.h)")
-        self.n_p, self.n_v, self.P = pa.size, pv.size, P
-        ls = torch.as_tensor(policy_sd[LOG_STD_KEY]).detach().float().cpu().reshape(-1)
-        if ls.numel() != 2:
-            raise ValueError("log_std_parameter must hold 2 values")
-        flat = np.concatenate([pa, pv, ls.numpy(), np.zeros(2, np.float32)])
-        assert flat.size == P
-        self.params = torch.from_numpy(flat).to(self.device)
-        self.grad = torch.zeros_like(self.params)
-        self.adam_m = torch.zeros_like(self.params)
-        self.adam_v = torch.zeros_like(self.params)
+        super().__init__(default_hparams, hparams, device, n_copies)
+        self.epochs, self.minibatches = int(epochs), int(minibatches)
+        self._networks(pack(policy_sd, "tanh"), pack(value_sd, "none"), policy_sd[LOG_STD_KEY])
         self.state = torch.zeros(C.sizeof(_lib.TrpoState) // 4, dtype=torch.int32, device=self.device)
-        self.rep_p = self.params[:self.n_p].repeat(self.n_copies)
-        self.rep_v = self.params[self.n_p:self.n_p + self.n_v].repeat(self.n_copies)
-        self.actor = RoverNet.from_packed(self.desc_p, self.rep_p, self.n_copies)
-        self.critic = RoverNet.from_packed(self.desc_v, self.rep_v, self.n_copies)
-        self.ws = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._ws_shape = (0, 0)
 
-    @classmethod
-    def from_checkpoint(cls, ck, **kw) -> "FusedTRPO":
-        """skrl checkpoint ``{"policy": state_dict, "value": state_dict, ...}`` (a path or the loaded dict)."""
-        if isinstance(ck, str):
-            ck = torch.load(ck, map_location="cpu", weights_only=False)
-        return cls(ck["policy"], ck["value"], **kw)
-
     # ---- views
-    @property
-    def log_std(self) -> torch.Tensor:
-        """The raw (unclamped) log_std parameter, a view of the device vector."""
-        return self.params[self.n_p + self.n_v:self.n_p + self.n_v + 2]
-
-    def state_dict(self) -> dict:
-        """``{"policy": ..., "value": ...}`` in the skrl / example layout (float32 CPU tensors)."""
-        p = self.params.cpu()
-        pol = unpack(self.desc_p, p[:self.n_p])
-        pol[LOG_STD_KEY] = p[self.n_p + self.n_v:self.n_p + self.n_v + 2].clone()
-        return {"policy": pol, "value": unpack(self.desc_v, p[self.n_p:self.n_p + self.n_v])}
-
     def vector(self, policy_sd: Mapping[str, torch.Tensor]) -> torch.Tensor:
         """A policy-side device vector (this class's layout, value block and padding zero) from state_dict-shaped tensors."""
         _, pa = pack(policy_sd, "tanh")
@@ -283,54 +241,21 @@ class FusedTRPO:
         sd[LOG_STD_KEY] = v[self.n_p + self.n_v:self.n_p + self.n_v + 2].clone()
         return sd
 
-    def stats(self) -> dict:
-        """The device state struct (one host synchronisation)."""
-        st = _lib.TrpoState.from_buffer_copy(self.state.cpu().numpy().tobytes())
-        return {f: getattr(st, f) for f, _ in _lib.TrpoState._fields_ if not f.startswith("reserved")}
-
     # ---- kernels
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _ensure_ws(self, rows: int, mb: int = 1):
         """Grow the workspace to (rows, mb).  The old bytes are carried over (on the stream of the kernels): the policy region
         sits at a fixed offset and its layout depends on the caller's B only, so the theta_old cache ``fvp`` reads survives a
         growth by ``value_minibatch`` between ``policy_grad`` and ``fvp``."""
         rows, mb = max(rows, self._ws_shape[0]), max(mb, self._ws_shape[1])
         if (rows, mb) != self._ws_shape:
-            need = int(self._lib.rover_trpo_workspace_bytes(rows, mb))
+            need = int(self._ws_bytes(rows, mb))
             ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             ws[:self.ws.numel()].copy_(self.ws)
             self.ws = ws
             self._ws_shape = (rows, mb)
 
-    @staticmethod
-    def _check(t: torch.Tensor, name: str, dtype=torch.float32):
-        if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dtype} cuda tensor")
-
     def _rollout(self, obs, act, logp, adv):
-        obs = obs.reshape(-1, obs.shape[-1])
-        B = obs.shape[0]
-        act, logp, adv = act.reshape(B, -1), logp.reshape(B), adv.reshape(B)
-        for t, nm in ((obs, "obs"), (act, "act"), (logp, "logp"), (adv, "adv")):
-            self._check(t, nm)
-        if obs.shape[1] != 965 or act.shape[1] != 2:
-            raise ValueError("obs must be (B, 965) and act (B, 2)")
-        return obs, act, logp, adv, B
-
-    def gae(self, rew, done, val, last_v):
-        """(adv, ret) of (T, n_envs) rollouts: rover_ppo_gae (the example's exact loop); adv is not normalised."""
-        from .ppo import default_hparams as ppo_hparams
-        for t, nm in ((rew, "rew"), (done, "done"), (val, "val"), (last_v, "last_v")):
-            self._check(t, nm)
-        h = ppo_hparams()
-        h.gamma, h.lam = self.hp.gamma, self.hp.lam
-        T, n = rew.shape
-        adv, ret = torch.empty_like(rew), torch.empty_like(rew)
-        _lib.check(self._lib.rover_ppo_gae(C.byref(h), rew.data_ptr(), done.data_ptr(), val.data_ptr(), last_v.data_ptr(), T, n,
-                                           adv.data_ptr(), ret.data_ptr(), self._stream()), "rover_ppo_gae")
-        return adv, ret
+        return self._flat_rollout(obs, act, logp=logp, adv=adv)
 
     def policy_grad(self, obs, act, logp, adv) -> torch.Tensor:
         """Step 1 at the current parameters: g into ``self.grad`` (value block zero); caches theta_old for ``fvp``."""
@@ -361,7 +286,6 @@ class FusedTRPO:
         obs, act, logp, adv, B = self._rollout(obs, act, logp, adv)
         self._ensure_ws(B)
         self._B = B
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         _lib.check(self._lib.rover_trpo_policy_step(C.byref(self.desc_p), C.byref(self.desc_v), C.byref(self.hp), self.params.data_ptr(),
                                                     obs.data_ptr(), act.data_ptr(), logp.data_ptr(), adv.data_ptr(), B, self.ws.data_ptr(),
                                                     self.ws.numel(), self.state.data_ptr(), self.rep_p.data_ptr(), self.n_copies,
@@ -397,11 +321,7 @@ class FusedTRPO:
         self._ensure_ws(B, -(-B // self.minibatches))
         self.policy_step(obs, act, logp, adv)
         for e in range(self.epochs):
-            perm = perms[e] if perms is not None else torch.randperm(B, device=self.device)
-            chunks = perm.chunk(self.minibatches)
-            if len(chunks) != self.minibatches:
-                raise ValueError(f"{B} rows do not make {self.minibatches} minibatches")
-            for mb in chunks:
+            for mb in self._minibatches(perms, e, B, self.minibatches):
                 self.value_minibatch(obs, ret, mb.contiguous())
                 self.value_apply()
         s = self.stats()

@@ -293,6 +293,10 @@ def test_collector_against_the_spec_and_into_the_update():
         col.begin(raw.double())
     with pytest.raises(ValueError):
         TC.TD3Collector(_actor(3), mem)
+    with pytest.raises(ValueError):                 # the trainer's optional outputs hold exactly what the kernels write
+        fused.critic_step(mem, i, y_out=torch.empty(B - 1, device="cuda"))
+    with pytest.raises(ValueError):
+        fused.actor_step(mem, i, dact_out=torch.empty(B, device="cuda"))
 
 
 def test_side_stream_matches_the_default_stream(actor, clean):
