@@ -222,6 +222,54 @@ def test_unknown_hyper_parameter_is_refused():
         _spec(policy_delay=2)
 
 
+# ---- the tests' own hyper-parameter mapping (sac_helpers.hparams / set_adam)
+def test_helper_maps_every_field_of_the_hparams_struct():
+    """A field added to rover_sac_hparams later has to be given to sac_helpers.hparams too, or the GPU tests could not move it."""
+    from isaac_rover_orbit_amd import _lib
+    from isaac_rover_orbit_amd.sac import HPARAMS
+    from sac_helpers import ADAM_NAMES, TORCH_NAMES, hparams
+    fields = [f for f, *_ in _lib.SacHparams._fields_]
+    assert set(fields) == set(TORCH_NAMES) | set(ADAM_NAMES) and not set(TORCH_NAMES) & set(ADAM_NAMES)
+    assert set(TORCH_NAMES.values()) <= set(HPARAMS) and len(set(TORCH_NAMES.values())) == len(TORCH_NAMES)
+    moved = {f: (False if f == "learn_entropy" else 0.1 + 0.01 * i) for i, f in enumerate(fields)}
+    fused_kw, torch_kw, adam = hparams(**moved)
+    assert set(fused_kw) == set(fields) and set(adam) == set(ADAM_NAMES) and set(torch_kw) == set(TORCH_NAMES.values())
+    h = _lib.SacHparams()
+    for k, v in fused_kw.items():
+        setattr(h, k, v)
+        # the struct holds exactly the number both paths get
+        assert getattr(h, k) == v and (k == "learn_entropy" or v == float(np.float32(moved[k]))), k
+        assert k in ADAM_NAMES or torch_kw[TORCH_NAMES[k]] == v
+    assert fused_kw["learn_entropy"] is False and torch_kw["learn_entropy"] is False
+    with pytest.raises(AssertionError):
+        hparams(policy_delay=2)
+
+
+def test_moved_adam_settings_reach_all_three_optimizers_of_the_spec():
+    from sac_helpers import hparams, specs_of
+    _, torch_kw, adam = hparams(beta1=0.8, beta2=0.99, eps=1e-4, entropy_lr=5e-2)
+    b1, b2, eps = (float(np.float32(v)) for v in (0.8, 0.99, 1e-4))
+    assert adam == dict(beta1=b1, beta2=b2, eps=eps)
+    for dt, spec in specs_of(nets(0), adam=adam, **torch_kw).items():
+        opts = (spec.policy_optimizer, spec.critic_optimizer, spec.entropy_optimizer)
+        for opt in opts:
+            assert len(opt.param_groups) == 1
+            assert opt.param_groups[0]["betas"] == (b1, b2) and opt.param_groups[0]["eps"] == eps
+        assert [o.param_groups[0]["lr"] for o in opts] == [1e-4, 1e-4, float(np.float32(5e-2))]
+    # ... and a step really runs with them: log_alpha's first Adam step is lr * g / (|g| + eps), so eps = 1e-4 shows at 1e-4 / |g|
+    mem = _memory()
+    idx, e = mem.sample_indices(16, torch.Generator().manual_seed(12)), draws(16, 13)
+    spec = specs_of(nets(0), adam=adam, **torch_kw)[F64]
+    la0 = float(spec.log_entropy_coefficient.detach())
+    st = spec.update(mem, idx, e)
+    g = -(st["logp_mean"] + spec.target_entropy)
+    assert float(spec.log_entropy_coefficient.detach()) - la0 == pytest.approx(-float(np.float32(5e-2)) * g / (abs(g) + eps), rel=1e-9)
+    assert abs(eps / abs(g)) > 1e-6                           # far above the comparison's 1e-9: torch's 1e-8 would fail it
+    # only one setting given: the others stay torch's
+    spec = specs_of(nets(0), adam=dict(beta2=b2))[F64]
+    assert spec.entropy_optimizer.param_groups[0]["betas"] == (0.9, b2) and spec.entropy_optimizer.param_groups[0]["eps"] == 1e-8
+
+
 # ---- host-only ABI checks
 def _descs():
     from isaac_rover_orbit_amd import td3
