@@ -13,8 +13,15 @@ HIP launches per env step, counter-based noise and batch indices.  That path als
 action's smoothing noise, drawn on the device).  ``--learning_starts`` collects without updating before that timestep, on either
 path.  At their defaults the run is what it was without them.
 
+``--preprocess running`` is rover_td3.yaml's ``state_preprocessor: RunningStandardScaler``: the policy acts on standardised rows,
+the memory keeps the raw ones, and every update standardises (and trains the statistics on) its sampled ``s`` and ``s'``
+(``offpolicy_scaled.FusedScaledTD3`` / ``TorchScaledTD3``; the collector takes the trainer's scaler).  ``--save`` then writes skrl's
+``state_preprocessor`` entry beside the networks and ``--resume`` reads it back.
+
     python examples/07_train_td3.py --num_envs 4096 --timesteps 2000 --update fused --out td3.jsonl
     python examples/07_train_td3.py --num_envs 4096 --timesteps 2000 --update fused --rollout fused --out td3.jsonl
+    python examples/07_train_td3.py --preprocess running --update fused --rollout fused --save td3.pt
+    python examples/07_train_td3.py --preprocess running --update fused --rollout fused --resume td3.pt
 """
 import argparse
 import importlib.util
@@ -33,6 +40,7 @@ from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
 from isaac_rover_orbit_amd.td3 import (HPARAMS, Critic, FusedTD3, ReplayMemory, TorchTD3, exploration_scale,  # noqa: E402
                                        explore)
 from isaac_rover_orbit_amd.td3_explore import TD3Explorer  # noqa: E402
+from isaac_rover_orbit_amd.offpolicy_scaled import FusedScaledTD3, TorchScaledTD3  # noqa: E402
 from isaac_rover_orbit_amd import tracker as tracking  # noqa: E402
 from isaac_rover_orbit_amd.envs.rover_env import LOG_KEYS  # noqa: E402
 
@@ -66,13 +74,17 @@ def build_parser() -> argparse.ArgumentParser:
                     help="collect without an update before this timestep (skrl learning_starts)")
     ap.add_argument("--smooth_noise_std", type=float, default=0.0,
                     help="std of the target action's smoothing noise (skrl smooth_regularization_noise; 0: none; needs --rollout fused)")
+    ap.add_argument("--preprocess", choices=("none", "running"), default="none",
+                    help="state_preprocessor of rover_td3.yaml: none, or skrl's RunningStandardScaler on the 965-wide states")
+    ap.add_argument("--resume", default=None, help="start from a checkpoint written by --save (with --preprocess running: its "
+                                                   "state_preprocessor entry too)")
     tracking.add_arguments(ap)
     return ap
 
 
-def main():
+def main(argv=None):
     ap = build_parser()
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.rollout == "fused" and args.update != "fused":
         ap.error("--rollout fused needs --update fused (the collector runs FusedTD3's actor)")
     if args.rollout != "fused" and (args.noise == "ou" or args.random_timesteps > 0 or args.smooth_noise_std > 0):
@@ -89,11 +101,24 @@ def main():
     env = RoverEnv(cfg, terrain=terrain)
     policy, critic_1, critic_2 = ppo_example.Net(2, False).to(dev), Critic().to(dev), Critic().to(dev)
     memory = ReplayMemory(M, n, device=dev)
-    fused = spec = None
+    fused = spec = scaled = None
+    ck = torch.load(args.resume, map_location="cpu", weights_only=False) if args.resume else None
     if args.update == "fused":
-        fused = FusedTD3(policy.state_dict(), critic_1.state_dict(), critic_2.state_dict())
+        fused = FusedTD3.from_checkpoint(ck) if ck else FusedTD3(policy.state_dict(), critic_1.state_dict(), critic_2.state_dict())
     else:
+        if ck:
+            for m, k in ((policy, "policy"), (critic_1, "critic_1"), (critic_2, "critic_2")):
+                m.load_state_dict(ck[k])
         spec = TorchTD3(policy, critic_1, critic_2)
+        for k in ("target_policy", "target_critic_1", "target_critic_2"):
+            if ck and ck.get(k) is not None:
+                getattr(spec, k).load_state_dict(ck[k])
+    if args.preprocess == "running":        # the trainer behind skrl's state scaler; ``upd`` is what updates, reports and saves
+        scaled = FusedScaledTD3(fused) if fused is not None else TorchScaledTD3(spec)
+        if ck:
+            scaled.load_state_preprocessor(ck)
+    upd = scaled if scaled is not None else (fused if fused is not None else spec)
+    pre = (lambda x: x) if scaled is None else (scaled.state_scaler.forward if fused is not None else scaled.state_preprocessor)
     gen = torch.Generator(device=dev).manual_seed(args.seed)
     EPISODE_INFO_TAGS = tracking.episode_info_tags(LOG_KEYS)      # infos["episode"], as the reference's trainer tags it
     tracker = tracking.from_args(args, n, EPISODE_INFO_TAGS, dev)     # --track: skrl's curves, kept on the device
@@ -101,7 +126,8 @@ def main():
     collector = None
     if args.rollout == "fused":
         collector = TD3Explorer(fused.actor, memory, seed=args.seed, env_id_offset=cfg.env_id_offset, noise=noise,
-                                noise_std=args.exploration_noise, random_timesteps=args.random_timesteps)
+                                noise_std=args.exploration_noise, random_timesteps=args.random_timesteps,
+                                state_scaler=None if scaled is None else scaled.state_scaler)
         collector.begin(obs)
     else:
         o = torch.nan_to_num(obs["policy"], neginf=0.0)
@@ -118,7 +144,7 @@ def main():
             idx = collector.record(obs, rew, term, args.batch_size if learning else None)   # indices over the rows filled so far
         else:
             with torch.no_grad():
-                a = fused.actor(o) if fused is not None else spec.act(o)
+                a = fused.actor(pre(o)) if fused is not None else spec.act(pre(o))
             if args.exploration_noise > 0:
                 a = explore(a, args.exploration_noise * torch.randn(a.shape, device=dev, generator=gen), scale)
             obs, rew, term, trunc, info = env.step(a)
@@ -134,13 +160,13 @@ def main():
             tracker.post_interaction(step)
         if learning and fused is not None:
             smooth = collector.smooth_noise(args.batch_size, args.smooth_noise_std) if args.smooth_noise_std > 0 else None
-            fused.update(memory, idx, smooth)
+            upd.update(memory, idx, smooth)
         elif learning:
-            last = spec.update(memory, idx)
+            last = upd.update(memory, idx)
         steps_log += 1
         if (step + 1) % args.log_every == 0 or step + 1 == args.timesteps:
             if fused is not None:
-                s = fused.stats()
+                s = upd.stats()
                 last = {k: s[k] for k in ("critic_loss", "q1_mean", "q2_mean", "y_mean", "policy_loss", "critic_step", "actor_step")}
             torch.cuda.synchronize()
             dt = time.perf_counter() - t_log
@@ -152,7 +178,7 @@ def main():
                 out.write(json.dumps(st) + "\n"); out.flush()
             t_log, steps_log = time.perf_counter(), 0
     if args.save:
-        torch.save(fused.state_dict() if fused is not None else spec.checkpoint(), args.save)
+        torch.save(upd.state_dict() if fused is not None else upd.checkpoint(), args.save)
     env.close()
 
 

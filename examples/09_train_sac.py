@@ -15,8 +15,15 @@ that timestep (skrl's switches of those names).
 launches per env step that act from the trainer's current actor and log_std, write the transition straight into the memory and
 return the batch's indices and the update's draws; every draw is counter-based (Philox keyed by ``--seed``).
 
+``--preprocess running`` is rover_sac.yaml's ``state_preprocessor: RunningStandardScaler``: the policy acts on standardised rows,
+the memory keeps the raw ones, and every update standardises (and trains the statistics on) its sampled ``s`` and ``s'``
+(``offpolicy_scaled.FusedScaledSAC`` / ``TorchScaledSAC``; the collector takes the trainer's scaler).  ``--save`` then writes skrl's
+``state_preprocessor`` entry beside the networks and ``--resume`` reads it back.
+
     python examples/09_train_sac.py --num_envs 4096 --timesteps 2000 --update fused --out sac.jsonl
     python examples/09_train_sac.py --num_envs 4096 --timesteps 2000 --update fused --rollout fused
+    python examples/09_train_sac.py --preprocess running --update fused --rollout fused --save sac.pt
+    python examples/09_train_sac.py --preprocess running --update fused --rollout fused --resume sac.pt
 """
 import argparse
 import importlib.util
@@ -30,6 +37,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from isaac_rover_orbit_amd.sac import HPARAMS, LOG_STD_MAX, LOG_STD_MIN, FusedSAC, TorchSAC  # noqa: E402
+from isaac_rover_orbit_amd.offpolicy_scaled import FusedScaledSAC, TorchScaledSAC  # noqa: E402
 from isaac_rover_orbit_amd.td3 import Critic, ReplayMemory  # noqa: E402
 from isaac_rover_orbit_amd import tracker as tracking  # noqa: E402
 from isaac_rover_orbit_amd.envs.rover_env import LOG_KEYS  # noqa: E402
@@ -59,6 +67,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="env steps of uniform random actions before the actor acts (skrl random_timesteps)")
     ap.add_argument("--learning_starts", type=int, default=HPARAMS["learning_starts"],
                     help="collect without an update before this timestep (skrl learning_starts)")
+    ap.add_argument("--preprocess", choices=("none", "running"), default="none",
+                    help="state_preprocessor of rover_sac.yaml: none, or skrl's RunningStandardScaler on the 965-wide states")
+    ap.add_argument("--resume", default=None, help="start from a checkpoint written by --save (with --preprocess running: its "
+                                                   "state_preprocessor entry too)")
     tracking.add_arguments(ap)
     return ap
 
@@ -82,11 +94,18 @@ def main(argv=None):
     env = RoverEnv(cfg, terrain=terrain)
     policy, critic_1, critic_2 = ppo_example.Net(2, True).to(dev), Critic().to(dev), Critic().to(dev)
     memory = ReplayMemory(M, n, device=dev)
-    fused = spec = None
+    fused = spec = scaled = None
+    ck = torch.load(args.resume, map_location="cpu", weights_only=False) if args.resume else None
     if args.update == "fused":
-        fused = FusedSAC(policy.state_dict(), critic_1.state_dict(), critic_2.state_dict())
+        fused = FusedSAC.from_checkpoint(ck) if ck else FusedSAC(policy.state_dict(), critic_1.state_dict(), critic_2.state_dict())
     else:
-        spec = TorchSAC(policy, critic_1, critic_2)
+        spec = TorchSAC.from_checkpoint(ck, policy, critic_1, critic_2) if ck else TorchSAC(policy, critic_1, critic_2)
+    if args.preprocess == "running":        # the trainer behind skrl's state scaler; ``upd`` is what updates, reports and saves
+        scaled = FusedScaledSAC(fused) if fused is not None else TorchScaledSAC(spec)
+        if ck:
+            scaled.load_state_preprocessor(ck)
+    upd = scaled if scaled is not None else (fused if fused is not None else spec)
+    pre = (lambda x: x) if scaled is None else (scaled.state_scaler.forward if fused is not None else scaled.state_preprocessor)
     gen = torch.Generator(device=dev).manual_seed(args.seed)
     eps = torch.empty(args.batch_size, 4, device=dev)
     EPISODE_INFO_TAGS = tracking.episode_info_tags(LOG_KEYS)      # infos["episode"], as the reference's trainer tags it
@@ -95,7 +114,8 @@ def main(argv=None):
     col = None
     if args.rollout == "fused":
         from isaac_rover_orbit_amd.sac_collect import SACCollector
-        col = SACCollector(fused.actor, fused.log_std, memory, seed=args.seed, random_timesteps=args.random_timesteps)
+        col = SACCollector(fused.actor, fused.log_std, memory, seed=args.seed, random_timesteps=args.random_timesteps,
+                           state_scaler=None if scaled is None else scaled.state_scaler)
         col.begin(obs)
     else:
         o = torch.nan_to_num(obs["policy"], neginf=0.0)
@@ -107,14 +127,14 @@ def main(argv=None):
             obs, rew, term, trunc, info = env.step(col.act(step))
             batch = col.record(obs, rew, term, args.batch_size if step >= args.learning_starts else None)
             if batch is not None:
-                fused.update(memory, *batch)
+                upd.update(memory, *batch)
                 updates += 1
         else:
             with torch.no_grad():
                 if step < args.random_timesteps:
                     a = torch.rand(n, 2, device=dev, generator=gen) * 2.0 - 1.0
                 else:
-                    mu = fused.actor(o) if fused is not None else policy(o)
+                    mu = fused.actor(pre(o)) if fused is not None else policy(pre(o))
                     log_std = fused.log_std if fused is not None else policy.log_std_parameter
                     sigma = log_std.clamp(LOG_STD_MIN, LOG_STD_MAX).exp()
                     a = (mu + sigma * torch.randn(n, 2, device=dev, generator=gen)).clamp(-1.0, 1.0)
@@ -132,14 +152,14 @@ def main(argv=None):
             idx = memory.sample_indices(args.batch_size, gen)
             smooth_draw(args.seed, updates, 1.0, eps)
             if fused is not None:
-                fused.update(memory, idx, eps)
+                upd.update(memory, idx, eps)
             else:
-                last = spec.update(memory, idx, eps)
+                last = upd.update(memory, idx, eps)
             updates += 1
         steps_log += 1
         if (step + 1) % args.log_every == 0 or step + 1 == args.timesteps:
             if fused is not None and updates:
-                s = fused.stats()
+                s = upd.stats()
                 last = {k: s[k] for k in LOGGED + ("critic_step", "actor_step", "entropy_step", "bad_index")}
             torch.cuda.synchronize()
             dt = time.perf_counter() - t_log
@@ -153,7 +173,7 @@ def main(argv=None):
     if out:
         out.close()
     if args.save:
-        torch.save(fused.state_dict() if fused is not None else spec.checkpoint(), args.save)
+        torch.save(upd.state_dict() if fused is not None else upd.checkpoint(), args.save)
     env.close()
     return last
 

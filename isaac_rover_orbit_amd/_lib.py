@@ -67,6 +67,7 @@ EXPORTS = [
     "rover_rollout_record_shaped",  # rover_rollout.h
     "rover_tracker_state_bytes", "rover_tracker_workspace_bytes", "rover_tracker_snapshot_words", "rover_tracker_init",  # rover_tracker.h
     "rover_tracker_step", "rover_tracker_track", "rover_tracker_snapshot",
+    "rover_offpolicy_stage_resolve", "rover_offpolicy_stage_rows",  # rover_offpolicy_scaled.h
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -546,6 +547,8 @@ def load():
     lib.rover_tracker_step.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, C.c_size_t, vp]
     lib.rover_tracker_track.argtypes = [vp, i32, i32, i32, vp, i32, vp]
     lib.rover_tracker_snapshot.argtypes = [vp, i32, i32, vp, i32, vp]
+    lib.rover_offpolicy_stage_resolve.argtypes = [vp, i32, C.c_int64, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rover_offpolicy_stage_rows.argtypes = [slh, vp, i32, vp, C.c_int64, vp, i32, vp, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:

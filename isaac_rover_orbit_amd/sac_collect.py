@@ -138,8 +138,9 @@ class TorchSACCollector(_SacModeMixin, TorchTD3Collector):
     """The specification, in torch / numpy.  ``actor``: any callable (n, 965) -> (n, 2) returning the tanh mean; ``log_std``: a
     tensor of 2 floats, read at every ``act``.  ``begin`` is ``TorchTD3Collector``'s."""
 
-    def __init__(self, actor, log_std, memory: ReplayMemory, seed: int = 42, env_id_offset: int = 0, random_timesteps: int = 0):
-        super().__init__(actor, memory, seed, env_id_offset, 0.0, (-1.0, 1.0))
+    def __init__(self, actor, log_std, memory: ReplayMemory, seed: int = 42, env_id_offset: int = 0, random_timesteps: int = 0,
+                 state_scaler=None):
+        super().__init__(actor, memory, seed, env_id_offset, 0.0, (-1.0, 1.0), state_scaler)
         self._init_sac(random_timesteps)
         self.log_std = log_std
         self.last: dict = {}
@@ -162,7 +163,7 @@ class TorchSACCollector(_SacModeMixin, TorchTD3Collector):
             a = torch.from_numpy(random_actions(self.seed, ids, self.counter)).to(dev)
             self.last = {}
         else:
-            mean = self.actor(m.obs[m.cursor])
+            mean = self.actor(self._states())
             a, self.last = mean, {"mean": mean}
             if mode == SAMPLE:
                 e = self.draws().astype(_F) if eps is None else eps.detach().cpu().numpy().astype(_F)
@@ -227,15 +228,16 @@ class SACCollector(_SacModeMixin, _FusedCollector):
     of 2 floats and ``memory`` a ``ReplayMemory`` on the same device, all held BY REFERENCE -- with ``FusedSAC.actor`` and
     ``FusedSAC.log_std`` the collector always sees the trainer's current parameters.  ``act`` returns a buffer the next call
     overwrites, ``record`` likewise (one index / draw buffer pair per batch size): ``begin`` and ``record`` are the fused base
-    class's, ``record`` returning ``(idx, eps)``.
+    class's, ``record`` returning ``(idx, eps)``.  ``state_scaler`` as ``TD3Collector``'s: the actor reads ``scaler.forward`` of the
+    cursor slot (one more launch, in every mode), the ring keeps the raw rows.
     """
 
     _NAME = "SACCollector"
     _DRAWS = True
 
     def __init__(self, actor, log_std: torch.Tensor, memory: ReplayMemory, seed: int = 42, env_id_offset: int = 0,
-                 random_timesteps: int = 0):
-        super().__init__(memory, seed, env_id_offset, 0.0, (-1.0, 1.0))
+                 random_timesteps: int = 0, state_scaler=None):
+        super().__init__(memory, seed, env_id_offset, 0.0, (-1.0, 1.0), state_scaler)
         self._init_sac(random_timesteps)
         self._bind(actor)
         self.log_std = log_std
@@ -259,7 +261,7 @@ class SACCollector(_SacModeMixin, _FusedCollector):
         """One launch in the mode of ``timestep`` on the ring's cursor slot.  Fills the memory's action slot and returns the actions
         for ``env.step``.  Advances the counter by one."""
         m = self.memory
-        collect_act(self.actor, self.log_std, m.obs[m.cursor], self.counter, self.hparams(self.mode(timestep, deterministic)),
+        collect_act(self.actor, self.log_std, self._states(), self.counter, self.hparams(self.mode(timestep, deterministic)),
                     m.actions[m.memory_index], self._env_act, mean_out=mean_out, eps_out=eps_out, logp_out=logp_out,
                     sigma_out=sigma_out)
         self.counter += 1

@@ -54,7 +54,7 @@ def sample_indices(seed: int, counter: int, batch_size: int, mem_rows: int) -> n
 class _CollectorBase:
     """Counter, checkpoint, argument checks and the memory's bookkeeping shared by the two implementations."""
 
-    def __init__(self, memory: ReplayMemory, seed: int, env_id_offset: int, noise_std: float, clip):
+    def __init__(self, memory: ReplayMemory, seed: int, env_id_offset: int, noise_std: float, clip, state_scaler=None):
         if memory.obs.shape[-1] != OBS_DIM:
             raise ValueError(f"the memory must hold {OBS_DIM}-wide observations")
         self.memory = memory
@@ -65,6 +65,13 @@ class _CollectorBase:
             raise ValueError("noise_std must be >= 0 and clip = (low, high) with low <= high")
         self.counter = 0
         self.device = memory.device
+        # skrl's state_preprocessor (offpolicy_scaled.py): the actor reads scaler(rows), untrained; the ring keeps the raw rows
+        self.state_scaler = state_scaler
+
+    def _states(self) -> torch.Tensor:
+        """The rows the actor reads: the ring's cursor slot, through ``state_scaler`` (no training) when one was given."""
+        rows = self.memory.obs[self.memory.cursor]
+        return rows if self.state_scaler is None else self.state_scaler(rows)
 
     def state_dict(self) -> dict:
         """The checkpoint of the noise and of the batch indices: the counter, not a generator state."""
@@ -104,8 +111,10 @@ class _CollectorBase:
 class TorchTD3Collector(_CollectorBase):
     """The specification, in plain torch / numpy.  ``actor``: any callable (n, 965) -> (n, A)."""
 
-    def __init__(self, actor, memory: ReplayMemory, seed: int = 42, env_id_offset: int = 0, noise_std: float = 0.0, clip=(-1.0, 1.0)):
-        super().__init__(memory, seed, env_id_offset, noise_std, clip)
+    def __init__(self, actor, memory: ReplayMemory, seed: int = 42, env_id_offset: int = 0, noise_std: float = 0.0, clip=(-1.0, 1.0),
+                 state_scaler=None):
+        """``state_scaler``: a callable rows -> standardised rows (``lift_ppo.RunningStandardScaler``) or ``None``."""
+        super().__init__(memory, seed, env_id_offset, noise_std, clip, state_scaler)
         self.actor = actor
 
     @staticmethod
@@ -126,7 +135,7 @@ class TorchTD3Collector(_CollectorBase):
     @torch.no_grad()
     def act(self, scale: float | None = None) -> torch.Tensor:
         m = self.memory
-        a = self.actor(m.obs[m.cursor])
+        a = self.actor(self._states())
         if self._exploring(scale):
             eps = torch.from_numpy(self.draws().astype(np.float32)).to(a.device)
             a = explore(a, self.noise_std * eps, float(scale), *self.clip)
@@ -203,9 +212,10 @@ class _FusedCollector(_CollectorBase):
     _NAME = ""
     _DRAWS = False
 
-    def __init__(self, memory: ReplayMemory, seed: int, env_id_offset: int, noise_std: float, clip):
+    def __init__(self, memory: ReplayMemory, seed: int, env_id_offset: int, noise_std: float, clip, state_scaler=None):
         _fused.require_gpu(self._NAME, f"Torch{self._NAME} is the CPU specification")
-        super().__init__(memory, seed, env_id_offset, noise_std, clip)
+        super().__init__(memory, seed, env_id_offset, noise_std, clip, state_scaler)
+        self._scaled = None
 
     def _bind(self, actor) -> None:
         self._lib = _lib.load()
@@ -217,6 +227,16 @@ class _FusedCollector(_CollectorBase):
 
     def _seeded(self, hp):
         return _fused.seeded(hp, self.seed, self.env_id_offset)
+
+    def _states(self) -> torch.Tensor:
+        """The rows the act kernel reads: the ring's cursor slot, or with a ``state_scaler`` (a ``scaler.DeviceScaler``) a scratch
+        image that one ``rover_scaler_apply`` fills from it.  The slot itself is never written."""
+        rows = self.memory.obs[self.memory.cursor]
+        if self.state_scaler is None:
+            return rows
+        if self._scaled is None:
+            self._scaled = torch.empty_like(rows)
+        return self.state_scaler.forward(rows, out=self._scaled)
 
     def _record(self, raw, ring_slot, counter=0, idx=None, eps=None, **transition) -> None:
         raise NotImplementedError
@@ -260,12 +280,15 @@ class TD3Collector(_FusedCollector):
     """The fused collector: ``actor`` is a ``RoverNet`` (reference architecture, no final activation) and ``memory`` a
     ``ReplayMemory`` on the same device, both held BY REFERENCE -- with ``FusedTD3.actor`` the collector always sees the trainer's
     current parameters.  ``act`` returns a buffer the next call overwrites, ``record`` likewise (one index buffer per batch size).
+    ``state_scaler``: a ``scaler.DeviceScaler`` (skrl's ``state_preprocessor``, ``offpolicy_scaled``): ``act`` then runs the actor on
+    ``scaler.forward`` of the cursor slot, one more launch, and the ring keeps the raw rows; ``None``: the launches as they were.
     """
 
     _NAME = "TD3Collector"
 
-    def __init__(self, actor, memory: ReplayMemory, seed: int = 42, env_id_offset: int = 0, noise_std: float = 0.0, clip=(-1.0, 1.0)):
-        super().__init__(memory, seed, env_id_offset, noise_std, clip)
+    def __init__(self, actor, memory: ReplayMemory, seed: int = 42, env_id_offset: int = 0, noise_std: float = 0.0, clip=(-1.0, 1.0),
+                 state_scaler=None):
+        super().__init__(memory, seed, env_id_offset, noise_std, clip, state_scaler)
         self._bind(actor)
         if actor.out_dim != self.A or actor.out_dim > 16:
             raise ValueError("the memory's action width must be the actor's output width (at most 16)")
@@ -286,7 +309,7 @@ class TD3Collector(_FusedCollector):
         the actor's output, not clamped).  Fills the memory's action slot and returns the actions for ``env.step``.  Advances the
         counter by one."""
         m = self.memory
-        collect_act(self.actor, m.obs[m.cursor], self.counter, self.hparams(scale), m.actions[m.memory_index], self._env_act,
+        collect_act(self.actor, self._states(), self.counter, self.hparams(scale), m.actions[m.memory_index], self._env_act,
                     mean_out=mean_out, eps_out=eps_out)
         self.counter += 1
         return self._env_act

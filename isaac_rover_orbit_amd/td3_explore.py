@@ -142,8 +142,8 @@ class TorchTD3Explorer(_ExplorerMixin, TorchTD3Collector):
                  clip=(-1.0, 1.0), random_timesteps: int = HPARAMS["random_timesteps"],
                  initial_scale: float = HPARAMS["exploration_initial_scale"], final_scale: float = HPARAMS["exploration_final_scale"],
                  exploration_timesteps=HPARAMS["exploration_timesteps"], ou_theta: float = OU_DEFAULTS["theta"],
-                 ou_sigma: float = OU_DEFAULTS["sigma"], ou_base_scale: float = OU_DEFAULTS["base_scale"]):
-        super().__init__(actor, memory, seed, env_id_offset, noise_std, clip)
+                 ou_sigma: float = OU_DEFAULTS["sigma"], ou_base_scale: float = OU_DEFAULTS["base_scale"], state_scaler=None):
+        super().__init__(actor, memory, seed, env_id_offset, noise_std, clip, state_scaler)
         self._init_explorer(noise, random_timesteps, initial_scale, final_scale, exploration_timesteps, ou_theta, ou_sigma, ou_base_scale)
 
     @torch.no_grad()
@@ -158,7 +158,7 @@ class TorchTD3Explorer(_ExplorerMixin, TorchTD3Collector):
         if mode == RANDOM:
             a = torch.from_numpy(random_actions(self.seed, ids, self.counter, self.A, *self.clip)).to(m.actions.device)
         else:
-            mean = self.actor(m.obs[m.cursor])
+            mean = self.actor(self._states())
             e = self.draws().astype(np.float32) if eps is None else eps.detach().cpu().numpy().astype(np.float32)
             xn, noise = ou_step(self.ou_state.cpu().numpy(), e, *self.ou)
             self.ou_state.copy_(torch.from_numpy(xn))
@@ -207,8 +207,8 @@ class TD3Explorer(_ExplorerMixin, TD3Collector):
                  clip=(-1.0, 1.0), random_timesteps: int = HPARAMS["random_timesteps"],
                  initial_scale: float = HPARAMS["exploration_initial_scale"], final_scale: float = HPARAMS["exploration_final_scale"],
                  exploration_timesteps=HPARAMS["exploration_timesteps"], ou_theta: float = OU_DEFAULTS["theta"],
-                 ou_sigma: float = OU_DEFAULTS["sigma"], ou_base_scale: float = OU_DEFAULTS["base_scale"]):
-        super().__init__(actor, memory, seed, env_id_offset, noise_std, clip)
+                 ou_sigma: float = OU_DEFAULTS["sigma"], ou_base_scale: float = OU_DEFAULTS["base_scale"], state_scaler=None):
+        super().__init__(actor, memory, seed, env_id_offset, noise_std, clip, state_scaler)
         self._init_explorer(noise, random_timesteps, initial_scale, final_scale, exploration_timesteps, ou_theta, ou_sigma, ou_base_scale)
         self._smooth: dict = {}
 
@@ -226,7 +226,7 @@ class TD3Explorer(_ExplorerMixin, TD3Collector):
         Advances the counter by one."""
         m = self.memory
         mode, scale = self.mode(timestep, timesteps)
-        explore_act(self.actor, m.obs[m.cursor], self.counter, self.explore_hparams(mode, scale), m.actions[m.memory_index],
+        explore_act(self.actor, self._states(), self.counter, self.explore_hparams(mode, scale), m.actions[m.memory_index],
                     self._env_act, ou_state=self.ou_state if mode == OU else None, mean_out=mean_out, eps_out=eps_out)
         self.counter += 1
         return self._env_act
