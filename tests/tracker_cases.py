@@ -128,3 +128,40 @@ def same_writes(wa, wb) -> bool:
             if not same(da[k], db[k]):
                 return False
     return True
+
+
+# ---------------------------------------------------------------------------------------------------------------- edge scripts
+# More than 65 536 envs: tracker_commit_kernel's 256 threads take the chunks t, t + 256, ... so chunks 256 and 257 belong to a second
+# pass.  Twelve steps at most, so that the CPU specification stays in seconds.
+BIG_SIZES = (65537, 65536 + 257)
+MANY_TAGS = (300, 4096)
+
+
+@functools.lru_cache(maxsize=None)
+def big_script(n: int):
+    """(steps, write_interval = 4) for n in BIG_SIZES.
+    Interval 1: the step maximum (50) and minimum (-60) lie in the last chunk; at step 3 envs of chunk 0, of chunk 255 and of the
+    last chunks (256, and 257 where n has one) finish together.
+    Interval 2: a NaN reward in the last env at step 5; at step 6 more than 100 envs finish, the last env among them and, at
+    n = 65 793, all of them beyond env 65 536, so only the 100 highest reach the rings.
+    Interval 3: a +inf reward in the last chunk at step 9, finishers in chunks 0 and 256 at step 10."""
+    assert n in BIG_SIZES
+    rew, term, trunc = _blank(n, 12, 12)
+    rew[0, n - 1], rew[2, 65536] = 50.0, -60.0
+    first = [5, 200, 255 * 256 + 17, 65536, n - 1]
+    term[3, first[:3]] = 1
+    trunc[3, first[3:]] = 1
+    rew[5, n - 1] = np.nan
+    many = np.arange(65537, n, 2)[:130] if n > 65536 + 200 else np.arange(65400, 65536, 1)
+    many = np.union1d(many, [n - 1])
+    assert len(many) > 100 and (n <= 65536 + 200 or many.min() > 65536)
+    term[6, many] = 1
+    rew[9, 65536] = np.inf
+    term[10, [3, 65536]] = 1
+    trunc[10, 70] = 1
+    return [(rew[t], term[t], trunc[t]) for t in range(12)], 4
+
+
+def many_tags(count: int):
+    """``count`` distinct tags: every third a (max), every third a (min), the others means."""
+    return tuple(f"Stat / s{i}" + (" (max)", " (min)", "")[i % 3] for i in range(count))
