@@ -68,6 +68,8 @@ EXPORTS = [
     "rover_tracker_state_bytes", "rover_tracker_workspace_bytes", "rover_tracker_snapshot_words", "rover_tracker_init",  # rover_tracker.h
     "rover_tracker_step", "rover_tracker_track", "rover_tracker_snapshot",
     "rover_offpolicy_stage_resolve", "rover_offpolicy_stage_rows",  # rover_offpolicy_scaled.h
+    "rover_lift_viewer_default_config", "rover_lift_viewer_config_bytes", "rover_lift_viewer_workspace_bytes",  # rover_lift_viewer.h
+    "rover_lift_viewer_constants", "rover_lift_viewer_env_origins", "rover_lift_viewer_render",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -298,6 +300,11 @@ class ViewerConfig(C.Structure):
                 ("near_clip", C.c_float), ("far_clip", C.c_float), ("draw_targets", C.c_int32)]
 
 
+class LiftViewerConfig(C.Structure):
+    """Mirror of ``struct rover_lift_viewer_config`` (include/rover_lift_viewer.h)."""
+    _fields_ = ViewerConfig._fields_ + [("env_spacing", C.c_float), ("ee_offset_z", C.c_float)]
+
+
 _lib = None
 
 
@@ -323,7 +330,7 @@ _MIRRORS = [("rover_config_bytes", RoverConfig), ("rover_lift_config_bytes", Lif
             ("rover_td3_collect_hparams_bytes", Td3CollectHparams), ("rover_td3_explore_hparams_bytes", Td3ExploreHparams),
             ("rover_sac_hparams_bytes", SacHparams), ("rover_sac_state_bytes", SacState),
             ("rover_sac_collect_hparams_bytes", SacCollectHparams), ("rover_scaler_hparams_bytes", ScalerHparams),
-            ("rover_trace_stream_bytes", TraceStream)]
+            ("rover_trace_stream_bytes", TraceStream), ("rover_lift_viewer_config_bytes", LiftViewerConfig)]
 
 
 def load():
@@ -413,6 +420,13 @@ def load():
     lib.rover_viewer_workspace_bytes.restype = C.c_size_t
     lib.rover_viewer_prepare.argtypes = [vp, C.POINTER(ViewerConfig), vp, C.c_size_t, vp]
     lib.rover_viewer_render.argtypes = [vp, C.POINTER(ViewerConfig), vp, vp, vp, vp, vp]
+    lib.rover_lift_viewer_default_config.argtypes = [C.POINTER(LiftViewerConfig)]
+    lib.rover_lift_viewer_config_bytes.restype = C.c_size_t
+    lib.rover_lift_viewer_workspace_bytes.argtypes = [i32, C.POINTER(LiftViewerConfig)]
+    lib.rover_lift_viewer_workspace_bytes.restype = C.c_size_t
+    lib.rover_lift_viewer_constants.argtypes = [vp, i32]
+    lib.rover_lift_viewer_env_origins.argtypes = [i32, f32, vp]
+    lib.rover_lift_viewer_render.argtypes = [vp, i32, C.POINTER(LiftViewerConfig), vp, C.c_size_t, vp, vp, vp, vp]
     lib.rover_ppo_default_hparams.argtypes = [C.POINTER(PpoHparams)]
     lib.rover_ppo_hparams_bytes.restype = C.c_size_t
     lib.rover_ppo_state_bytes.restype = C.c_size_t

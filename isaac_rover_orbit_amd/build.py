@@ -16,12 +16,13 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("rover_kernels.hip", "terrain
                                                             "td3_kernels.hip", "rollout_kernels.hip", "lift_rollout_kernels.hip",
                                                             "td3_collect_kernels.hip", "td3_explore_kernels.hip", "trace_kernels.hip",
                                                             "sac_kernels.hip", "sac_collect_kernels.hip", "scaler_kernels.hip",
-                                                            "tracker_kernels.hip", "offpolicy_scaled_kernels.hip")]
+                                                            "tracker_kernels.hip", "offpolicy_scaled_kernels.hip",
+                                                            "lift_viewer_kernels.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "rover_model.hpp"), os.path.join(_PKG, "csrc", "rover_internal.hpp"),
            os.path.join(_PKG, "csrc", "terrain_march.hpp"), os.path.join(_PKG, "csrc", "rover_render.hpp"),
            os.path.join(_PKG, "csrc", "td3_actor_tile.hpp"), os.path.join(_PKG, "csrc", "offpolicy_net.hpp"),
            os.path.join(_PKG, "csrc", "train_math.hpp"), os.path.join(_PKG, "csrc", "offpolicy_collect.hpp"),
-           os.path.join(_PKG, "csrc", "train_shared.hpp"),
+           os.path.join(_PKG, "csrc", "train_shared.hpp"), os.path.join(_PKG, "csrc", "lift_render.hpp"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_lift.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_hip.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_terrain.h"),
@@ -43,7 +44,8 @@ HEADERS = [os.path.join(_PKG, "csrc", "rover_model.hpp"), os.path.join(_PKG, "cs
            os.path.join(os.path.dirname(_PKG), "include", "rover_scaler.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_train_gate.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_tracker.h"),
-           os.path.join(os.path.dirname(_PKG), "include", "rover_offpolicy_scaled.h")]
+           os.path.join(os.path.dirname(_PKG), "include", "rover_offpolicy_scaled.h"),
+           os.path.join(os.path.dirname(_PKG), "include", "rover_lift_viewer.h")]
 OBJ_DIR = os.path.join(os.path.dirname(_PKG), "build", "obj")
 OUTPUT = os.path.join(_PKG, "librover_hip.so")
 # fp32 parity with the CPU oracle: no contraction, no fast-math (correctly rounded div / sqrt are hipcc defaults)
