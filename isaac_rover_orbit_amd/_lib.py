@@ -70,6 +70,8 @@ EXPORTS = [
     "rover_offpolicy_stage_resolve", "rover_offpolicy_stage_rows",  # rover_offpolicy_scaled.h
     "rover_lift_viewer_default_config", "rover_lift_viewer_config_bytes", "rover_lift_viewer_workspace_bytes",  # rover_lift_viewer.h
     "rover_lift_viewer_constants", "rover_lift_viewer_env_origins", "rover_lift_viewer_render",
+    "rover_dagger_default_hparams", "rover_dagger_hparams_bytes", "rover_dagger_state_bytes", "rover_dagger_param_floats",  # rover_dagger.h
+    "rover_dagger_workspace_bytes", "rover_dagger_rows", "rover_dagger_act", "rover_dagger_record", "rover_dagger_update",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -216,6 +218,19 @@ class SacCollectHparams(C.Structure):
     _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("mode", C.c_int32)]
 
 
+class DaggerHparams(C.Structure):
+    """Mirror of ``struct rover_dagger_hparams`` (include/rover_dagger.h)."""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("env_id_offset", C.c_int32), ("depth_clip", C.c_float),
+                ("depth_scale", C.c_float), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("grad_norm_clip", C.c_float)]
+
+
+class DaggerState(C.Structure):
+    """Mirror of ``struct rover_dagger_state`` (include/rover_dagger.h; it lives in device memory)."""
+    _fields_ = [("steps", C.c_int32), ("bad_index", C.c_int32), ("loss", C.c_float), ("grad_norm", C.c_float),
+                ("clip_coef", C.c_float), ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("reserved", C.c_float)]
+
+
 SCALER_MAX_WIDTH, SCALER_CHUNK_ROWS = 1024, 64
 SCALER_INVERSE, SCALER_SANITISE = 1, 2
 
@@ -330,7 +345,8 @@ _MIRRORS = [("rover_config_bytes", RoverConfig), ("rover_lift_config_bytes", Lif
             ("rover_td3_collect_hparams_bytes", Td3CollectHparams), ("rover_td3_explore_hparams_bytes", Td3ExploreHparams),
             ("rover_sac_hparams_bytes", SacHparams), ("rover_sac_state_bytes", SacState),
             ("rover_sac_collect_hparams_bytes", SacCollectHparams), ("rover_scaler_hparams_bytes", ScalerHparams),
-            ("rover_trace_stream_bytes", TraceStream), ("rover_lift_viewer_config_bytes", LiftViewerConfig)]
+            ("rover_trace_stream_bytes", TraceStream), ("rover_lift_viewer_config_bytes", LiftViewerConfig),
+            ("rover_dagger_hparams_bytes", DaggerHparams), ("rover_dagger_state_bytes", DaggerState)]
 
 
 def load():
@@ -563,6 +579,19 @@ def load():
     lib.rover_tracker_snapshot.argtypes = [vp, i32, i32, vp, i32, vp]
     lib.rover_offpolicy_stage_resolve.argtypes = [vp, i32, C.c_int64, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.rover_offpolicy_stage_rows.argtypes = [slh, vp, i32, vp, C.c_int64, vp, i32, vp, vp, vp]
+    dgh = C.POINTER(DaggerHparams)
+    lib.rover_dagger_default_hparams.argtypes = [dgh]
+    lib.rover_dagger_hparams_bytes.restype = C.c_size_t
+    lib.rover_dagger_state_bytes.restype = C.c_size_t
+    lib.rover_dagger_param_floats.argtypes = [pd]
+    lib.rover_dagger_param_floats.restype = C.c_size_t
+    lib.rover_dagger_workspace_bytes.argtypes = [i32]
+    lib.rover_dagger_workspace_bytes.restype = C.c_size_t
+    lib.rover_dagger_rows.argtypes = [dgh, vp, vp, i32, vp, vp, vp]
+    lib.rover_dagger_act.argtypes = [pd, vp, i32, pd, vp, i32, dgh, C.c_uint64, f32, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.rover_dagger_record.argtypes = [dgh, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.c_int64, C.c_uint64, vp]
+    lib.rover_dagger_update.argtypes = [pd, dgh, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, C.c_int64, vp, C.c_size_t, vp, vp, i32, vp,
+                                        vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
