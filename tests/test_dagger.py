@@ -1,5 +1,6 @@
 """The DAgger specification on the CPU (isaac_rover_orbit_amd/dagger.py): the student rows, the imitation loss with its closed-form
-tanh backward, and the collector's mixing, sharding and checkpoint.  The kernels are held to these in test_gpu_dagger.py."""
+tanh backward, and the collector's mixing, sharding and checkpoint.  The kernels are held to these in test_gpu_dagger.py and, at the
+draws' and the hyper-parameters' edges (the last section here), in test_gpu_dagger_collect_edges.py."""
 import copy
 
 import numpy as np
@@ -244,3 +245,90 @@ def test_checkpoint_after_step_2_reproduces_steps_3_and_4():
     # the indices are the TD3 collector's stream under the same seed and counter
     from isaac_rover_orbit_amd.td3_collect import sample_indices
     assert np.array_equal(full[3][4].numpy(), sample_indices((3 << 32) | 11, 7, 16, 4 * n))
+
+
+# ---------------------------------------------------------------------------------------------------------------- edges
+def test_mix_uniforms_equal_the_by_hand_philox_at_the_top_of_the_ranges():
+    """The specification the kernel's draw is held to, against Philox in Python integers: ids up to 2**31 - 2, every key bit set,
+    counters around 2**32 and at 2**64 - 1.  Exact: u = (k + 0.5) * 2**-23 is a float32."""
+    from dagger_helpers import mix_uniforms_by_hand
+    from td3_helpers import TOP_COUNTERS, TOP_OFFSET, TOP_SEED
+    ids = TOP_OFFSET + np.arange(33)
+    assert ids[-1] == 2 ** 31 - 2
+    seen = []
+    for counter in TOP_COUNTERS:
+        u = D().mix_uniforms(TOP_SEED, ids, counter)
+        assert u.dtype == np.float32 and u.tolist() == mix_uniforms_by_hand(TOP_SEED, ids, counter)
+        assert len(set(u.tolist())) == 33 and 0 < int((u < 0.5).sum()) < 33 and u.min() >= 2.0 ** -24 and u.max() < 1.0
+        seen.append((u < 0.5).tolist())
+    assert seen[0] != seen[1] != seen[2] != seen[0]
+    # another id, seed or counter word is another draw
+    base = D().mix_uniforms(TOP_SEED, ids, TOP_COUNTERS[0])
+    assert not np.array_equal(base, D().mix_uniforms(TOP_SEED, ids - 1, TOP_COUNTERS[0]))
+    assert not np.array_equal(base, D().mix_uniforms(TOP_SEED ^ (1 << 63), ids, TOP_COUNTERS[0]))
+
+
+def test_beta_on_a_draw_takes_the_student():
+    """The mix is u < beta: with beta = u_k env k takes the student, with the next float32 the teacher, nobody else moves."""
+    n, k = 33, 16
+    teacher = lambda rows: torch.tanh(rows[:, 1:3] + rows[:, 7:9])          # noqa: E731
+    stud = lambda rows: torch.tanh(rows[:, 0:2] - rows[:, 400:402])         # noqa: E731
+    steps = Steps(n, 1)
+    u = collector(n, teacher, stud, offset=7).draws()
+    assert u.dtype == np.float32 and len(set(u.tolist())) == n
+    on, after = float(u[k]), float(np.nextafter(u[k], np.float32(1.0)))
+    got = {}
+    for beta in (on, after):
+        col = collector(n, teacher, stud, offset=7)
+        (rec,) = drive(col, steps, [beta])
+        src = rec[3].numpy()
+        assert np.array_equal(np.delete(src, k), np.delete(u < on, k)) and 0 < int(src.sum()) < n
+        assert torch.equal(rec[0], torch.where(rec[3].unsqueeze(1), rec[1], rec[2])) and not torch.equal(rec[1][k], rec[2][k])
+        got[beta] = bool(src[k])
+    assert got == {on: False, after: True}
+    # the smallest possible draw is 2**-24: that beta takes no teacher at all
+    col = collector(n, teacher, stud, offset=7)
+    (rec,) = drive(col, steps, [2.0 ** -24])
+    assert not bool(rec[3].any())
+
+
+@pytest.mark.parametrize("scale", [0.0, -0.1, INF, 1e-45])
+def test_student_rows_at_degenerate_depth_scales(scale):
+    d, e = images(3), env_rows(3)
+    rows = D().student_rows(d, e, depth_scale=scale)
+    s = np.float32(scale)
+    flat = d.view(3, -1).numpy()
+    with np.errstate(invalid="ignore"):
+        pix = np.where(np.isnan(flat) | np.isinf(flat) | (flat < 0), np.float32(10.0), flat)
+        want = s * np.minimum(pix, np.float32(10.0))
+    got = rows[:, 4:].numpy()
+    assert got.dtype == np.float32 and np.array_equal(np.isnan(got), np.isnan(want))
+    assert np.array_equal(got[~np.isnan(got)].view(np.uint32), want[~np.isnan(want)].astype(np.float32).view(np.uint32))
+    zero = flat == 0
+    assert zero.any()
+    if scale == INF:
+        assert np.isnan(got[zero]).all() and np.isinf(got[~zero]).all()          # inf * 0: the zero pixels are NaN, as in torch
+    elif scale == 0.0:
+        assert not got.any()
+    elif scale == 1e-45:
+        assert s > 0 and float(got.max()) == float(s * np.float32(10.0)) > 0      # a denormal scale is a number, not flushed
+    else:
+        assert float(got.max()) == 0.0 and float(got.min()) == float(s * np.float32(10.0))
+    assert torch.equal(rows[:, :4], D().sanitise(e[:, :4]))
+
+
+@pytest.mark.parametrize("clip", [1e-45, float(np.finfo(np.float32).max)])
+def test_student_rows_at_the_ends_of_depth_clip(clip):
+    d, e = images(3), env_rows(3)
+    rows = D().student_rows(d, e, depth_clip=clip)
+    c = np.float32(clip)
+    flat = d.view(3, -1).numpy()
+    got = rows[:, 4:].numpy()
+    assert np.isfinite(got).all() and float(got.max()) == float(np.float32(0.1) * c)
+    bad = np.isnan(flat) | np.isinf(flat) | (flat < 0)
+    assert (got[bad] == np.float32(0.1) * c).all() and (got[flat == 0] == 0).all()
+    if clip < 1.0:                                                              # every positive pixel is above the smallest denormal
+        assert (got[flat > 0] == np.float32(0.1) * c).all()
+    else:                                                                       # nothing is clipped but what is not a depth
+        ok = ~bad
+        assert np.array_equal(got[ok], np.float32(0.1) * flat[ok])
