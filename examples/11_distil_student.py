@@ -9,10 +9,16 @@ teacher with probability beta and by the student otherwise, the student's row an
 ``td3.ReplayMemory``), and one imitation step runs on a batch drawn from it.  ``--update fused`` runs all of that but ``env.step`` as HIP
 kernels (``DAggerCollector`` + ``FusedDAgger``); ``--update torch`` is the specification on the same device.
 
+``--student conv`` keeps the camera at the reference's 160 x 90 and puts a small learned convolutional stem in front of the same
+network (``isaac_rover_orbit_amd.dagger_conv``): the images go into an ``ImageRing`` beside the dataset and stem and network train end
+to end.  The default ``--student mlp31`` is the 31 x 31 student described above.
+
 beta follows ``beta0 * beta_decay ** step``: ``--beta0 1 --beta_decay 1`` is behaviour cloning, ``--beta0 0`` the pure student.
 
     python examples/11_distil_student.py --teacher ppo.pt --num_envs 256 --steps 50 --update fused --save student.pt
     python examples/11_distil_student.py --eval student.pt --num_envs 256 --steps 750
+    python examples/11_distil_student.py --teacher ppo.pt --student conv --num_envs 256 --batch_size 1024 --update fused --save conv.pt
+    python examples/11_distil_student.py --eval conv.pt --student conv --num_envs 256 --steps 750
 
 ``--eval`` drives closed loop from the student's own rows and prints the termination tallies, as examples/03_eval_policy.py does.  No
 claim is made about how well a student trained this way drives.
@@ -28,7 +34,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from isaac_rover_orbit_amd import dagger  # noqa: E402
+from isaac_rover_orbit_amd import dagger, dagger_conv  # noqa: E402
 from isaac_rover_orbit_amd import terrain as T  # noqa: E402
 from isaac_rover_orbit_amd import tracker as tracking  # noqa: E402
 from isaac_rover_orbit_amd.cfg import RoverEnvCfg  # noqa: E402
@@ -48,6 +54,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eval", default=None, metavar="CKPT", help="evaluate this student checkpoint closed loop instead of training")
     ap.add_argument("--update", choices=("torch", "fused"), default="torch",
                     help="collector and update: the torch specification or the fused HIP kernels")
+    ap.add_argument("--student", choices=("mlp31", "conv"), default="mlp31",
+                    help="mlp31: a 31 x 31 camera straight into the network; conv: the 160 x 90 camera through a learned stem")
     ap.add_argument("--num_envs", type=int, default=256)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--beta0", type=float, default=1.0)
@@ -63,24 +71,29 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
-def make_env(n: int):
+def make_env(n: int, student: str = "mlp31"):
     terrain = T.make_procedural_terrain((2048, 2048), seed=1234)
     terrain.make_spawns(2 * n)
     cfg = RoverEnvCfg(); cfg.scene.num_envs = n; cfg.terrain.kind = "custom"
-    cfg.camera = dagger.student_camera_cfg()
+    cfg.camera = dagger_conv.student_camera_cfg() if student == "conv" else dagger.student_camera_cfg()
     return cfg, RoverEnv(cfg, terrain=terrain)
 
 
 def evaluate(args):
     """examples/03_eval_policy.py's loop with the student's rows in place of the env's."""
-    _, env = make_env(args.num_envs)
-    actor = RoverNet.from_checkpoint(args.eval, role="policy")
+    _, env = make_env(args.num_envs, args.student)
+    if args.student == "conv":
+        act = dagger_conv.ConvStudent.from_checkpoint(args.eval).act
+    else:
+        actor = RoverNet.from_checkpoint(args.eval, role="policy")
+        rows = torch.empty(args.num_envs, 965, device="cuda")
+
+        def act(obs, depth):
+            return actor(dagger.fused_student_rows(depth, obs["policy"], out=rows))
     obs, _ = env.reset()
     counts, episodes = torch.zeros(4), 0.0
-    rows = torch.empty(args.num_envs, 965, device="cuda")
     for _ in range(args.steps):
-        dagger.fused_student_rows(env.extras["depth"], obs["policy"], out=rows)
-        obs, rew, terminated, truncated, info = env.step(actor(rows))
+        obs, rew, terminated, truncated, info = env.step(act(obs, env.extras["depth"]))
         log = env.episode_log_vector.cpu()
         if log[13] > 0:
             episodes += float(log[13])
@@ -100,12 +113,27 @@ def main(argv=None):
     dev = torch.device("cuda")
     n = args.num_envs
     M = args.memory_size or max(16, -(-2 * args.batch_size // n))
-    cfg, env = make_env(n)
+    cfg, env = make_env(n, args.student)
     teacher_sd = torch.load(args.teacher, map_location="cpu", weights_only=False)["policy"]
     memory = ReplayMemory(M, n, device=dev)
     student = ppo_example.Net(2, True).to(dev)
     hp = dict(learning_rate=args.learning_rate, grad_norm_clip=args.grad_norm_clip)
-    if args.update == "fused":
+    images = None
+    if args.student == "conv":
+        # the images of every slot of the dataset: (M + 1) x n x 57.6 KB beside the memory
+        images = dagger_conv.ImageRing(M, n, device=dev)
+        if args.update == "fused":
+            trainer = dagger_conv.FusedConvDAgger(student.state_dict(), seed=args.seed, **hp)
+            collector = dagger_conv.ConvDAggerCollector(RoverNet.from_state_dict(teacher_sd, final_act="tanh"), trainer, memory, images,
+                                                        seed=args.seed, env_id_offset=cfg.env_id_offset)
+        else:
+            teacher = ppo_example.Net(2, True).to(dev)
+            teacher.load_state_dict(teacher_sd, strict=False)
+            stem = dagger_conv.ConvStem.seeded(args.seed).to(dev)
+            trainer = dagger_conv.TorchConvDAgger(student, stem, **hp)
+            collector = dagger_conv.TorchConvDAggerCollector(teacher, student, stem, memory, images, seed=args.seed,
+                                                             env_id_offset=cfg.env_id_offset)
+    elif args.update == "fused":
         trainer = dagger.FusedDAgger(student.state_dict(), **hp)
         collector = dagger.DAggerCollector(RoverNet.from_state_dict(teacher_sd, final_act="tanh"), trainer.actor, memory, seed=args.seed,
                                            env_id_offset=cfg.env_id_offset)
@@ -127,7 +155,7 @@ def main(argv=None):
             tracker.step(rew, term, trunc)
             tracker.track_vector(EPISODE_INFO_TAGS, env.episode_log_vector)
             tracker.post_interaction(step)
-        out = trainer.update(memory, idx)
+        out = trainer.update(memory, idx) if images is None else trainer.update(memory, images, idx)
         steps_log += 1
         if (step + 1) % args.log_every == 0 or step + 1 == args.steps:
             if args.update == "fused":

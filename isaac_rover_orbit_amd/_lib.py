@@ -72,6 +72,8 @@ EXPORTS = [
     "rover_lift_viewer_constants", "rover_lift_viewer_env_origins", "rover_lift_viewer_render",
     "rover_dagger_default_hparams", "rover_dagger_hparams_bytes", "rover_dagger_state_bytes", "rover_dagger_param_floats",  # rover_dagger.h
     "rover_dagger_workspace_bytes", "rover_dagger_rows", "rover_dagger_act", "rover_dagger_record", "rover_dagger_update",
+    "rover_dagger_conv_stem_floats", "rover_dagger_conv_param_floats", "rover_dagger_conv_stem_offset",  # rover_dagger_conv.h
+    "rover_dagger_conv_chunk_rows", "rover_dagger_conv_workspace_bytes", "rover_dagger_conv_rows", "rover_dagger_conv_update",
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -592,6 +594,18 @@ def load():
     lib.rover_dagger_record.argtypes = [dgh, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.c_int64, C.c_uint64, vp]
     lib.rover_dagger_update.argtypes = [pd, dgh, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, C.c_int64, vp, C.c_size_t, vp, vp, i32, vp,
                                         vp]
+    lib.rover_dagger_conv_stem_floats.restype = C.c_size_t
+    lib.rover_dagger_conv_param_floats.argtypes = [pd]
+    lib.rover_dagger_conv_param_floats.restype = C.c_size_t
+    lib.rover_dagger_conv_stem_offset.argtypes = [pd]
+    lib.rover_dagger_conv_stem_offset.restype = C.c_size_t
+    lib.rover_dagger_conv_chunk_rows.restype = i32
+    lib.rover_dagger_conv_workspace_bytes.argtypes = [i32]
+    lib.rover_dagger_conv_workspace_bytes.restype = C.c_size_t
+    lib.rover_dagger_conv_rows.argtypes = [dgh, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, C.c_int64,
+                                           C.c_uint64, vp]
+    lib.rover_dagger_conv_update.argtypes = [pd, dgh, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, C.c_int64, vp,
+                                             C.c_size_t, vp, vp, i32, vp, vp, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:
