@@ -106,8 +106,20 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the agent files' rewards_shaper_scale: rewards are multiplied by F as they are recorded (default: off)")
     ap.add_argument("--time_limit_bootstrap", action="store_true",
                     help="skrl's time_limit_bootstrap: rewards += discount * value * truncated as they are recorded")
+    ap.add_argument("--scan_noise", type=float, nargs=2, default=None, metavar=("N_MIN", "N_MAX"),
+                    help="additive uniform noise on the height scan, the reference's Unoise (rover_env_cfg.py:23); default: none")
+    ap.add_argument("--obs_backend", choices=("torch", "fused"), default="torch",
+                    help="who applies --scan_noise: torch ops behind the step kernel, or one HIP launch with counter-based draws "
+                         "(obs_post.ObsPost)")
     tracking.add_arguments(ap)
     return ap
+
+
+class ScanNoise:
+    """Additive uniform noise in the shape of ORBIT's AdditiveUniformNoiseCfg, without its func."""
+
+    def __init__(self, n_min: float, n_max: float):
+        self.n_min, self.n_max = n_min, n_max
 
 
 def main():
@@ -125,6 +137,9 @@ def main():
     terrain = T.make_procedural_terrain((2048, 2048), seed=1234)
     terrain.make_spawns(2 * n)
     cfg = RoverEnvCfg(); cfg.scene.num_envs = n; cfg.terrain.kind = "custom"
+    if args.scan_noise is not None:
+        cfg.observations["height_scan"].noise = ScanNoise(*args.scan_noise)
+        cfg.observation_post_backend = args.obs_backend
     env = RoverEnv(cfg, terrain=terrain)
     policy, value = Net(2, True).to(dev), Net(1, False).to(dev)
     opt = torch.optim.Adam(list(policy.parameters()) + list(value.parameters()), lr=1e-4)

@@ -67,21 +67,36 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--log_every", type=int, default=10, help="env steps per logged line (the fused path syncs only then)")
     ap.add_argument("--save", default=None, metavar="PATH", help="write {'policy': student state_dict}, loadable by --eval and RoverNet")
+    ap.add_argument("--depth_noise_std", type=float, default=None, metavar="S",
+                    help="Gaussian sensor noise of standard deviation S (m) on the depth image the student sees (default: none)")
+    ap.add_argument("--depth_clip_max", type=float, default=None, metavar="M",
+                    help="clip the depth image to [0, M] m after the noise: misses (+inf) become M (default: no clip)")
     tracking.add_arguments(ap)
     return ap
 
 
-def make_env(n: int, student: str = "mlp31"):
+class DepthNoise:
+    """Zero-mean Gaussian noise in the shape of ORBIT's AdditiveGaussianNoiseCfg, without its func."""
+
+    def __init__(self, std: float):
+        self.mean, self.std = 0.0, std
+
+
+def make_env(n: int, student: str = "mlp31", depth_noise_std: float | None = None, depth_clip_max: float | None = None):
     terrain = T.make_procedural_terrain((2048, 2048), seed=1234)
     terrain.make_spawns(2 * n)
     cfg = RoverEnvCfg(); cfg.scene.num_envs = n; cfg.terrain.kind = "custom"
     cfg.camera = dagger_conv.student_camera_cfg() if student == "conv" else dagger.student_camera_cfg()
+    if depth_noise_std is not None:
+        cfg.camera.noise = DepthNoise(depth_noise_std)
+    if depth_clip_max is not None:
+        cfg.camera.clip = (0.0, depth_clip_max)
     return cfg, RoverEnv(cfg, terrain=terrain)
 
 
 def evaluate(args):
     """examples/03_eval_policy.py's loop with the student's rows in place of the env's."""
-    _, env = make_env(args.num_envs, args.student)
+    _, env = make_env(args.num_envs, args.student, args.depth_noise_std, args.depth_clip_max)
     if args.student == "conv":
         act = dagger_conv.ConvStudent.from_checkpoint(args.eval).act
     else:
@@ -113,7 +128,7 @@ def main(argv=None):
     dev = torch.device("cuda")
     n = args.num_envs
     M = args.memory_size or max(16, -(-2 * args.batch_size // n))
-    cfg, env = make_env(n, args.student)
+    cfg, env = make_env(n, args.student, args.depth_noise_std, args.depth_clip_max)
     teacher_sd = torch.load(args.teacher, map_location="cpu", weights_only=False)["policy"]
     memory = ReplayMemory(M, n, device=dev)
     student = ppo_example.Net(2, True).to(dev)

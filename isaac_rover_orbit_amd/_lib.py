@@ -74,6 +74,7 @@ EXPORTS = [
     "rover_dagger_workspace_bytes", "rover_dagger_rows", "rover_dagger_act", "rover_dagger_record", "rover_dagger_update",
     "rover_dagger_conv_stem_floats", "rover_dagger_conv_param_floats", "rover_dagger_conv_stem_offset",  # rover_dagger_conv.h
     "rover_dagger_conv_chunk_rows", "rover_dagger_conv_workspace_bytes", "rover_dagger_conv_rows", "rover_dagger_conv_update",
+    "rover_obs_post_segment_bytes", "rover_obs_post_apply",  # rover_obs_post.h
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -254,6 +255,21 @@ def scaler_workspace_bytes(width: int, max_rows: int) -> int:
     return 8 * width * (1 + (max_rows + SCALER_CHUNK_ROWS - 1) // SCALER_CHUNK_ROWS)
 
 
+OBS_POST_MAX_SEGMENTS, OBS_POST_MAX_WIDTH = 8, 262144
+OBS_POST_NONE, OBS_POST_UNIFORM, OBS_POST_GAUSSIAN, OBS_POST_CONSTANT = 0, 1, 2, 3
+# Word 3 of the Philox counter of the post-processing draws: the HIGH HALF names the stream ("OP": observation rows, "OD": depth
+# images), the low half carries the column quad.  td3_explore.TAGS is the table of the streams named by their upper 24 bits; these
+# two are checked against it by tests/test_obs_post.py.
+OBS_POST_STREAM_ROW = 0x4F500000
+OBS_POST_STREAM_DEPTH = 0x4F440000
+
+
+class ObsPostSegment(C.Structure):
+    """Mirror of ``struct rover_obs_post_segment`` (include/rover_obs_post.h)."""
+    _fields_ = [("col_lo", C.c_int32), ("col_hi", C.c_int32), ("noise", C.c_int32), ("a", C.c_float), ("b", C.c_float),
+                ("has_clip", C.c_int32), ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("scale", C.c_float)]
+
+
 class RoverHipError(RuntimeError):
     pass
 
@@ -348,7 +364,8 @@ _MIRRORS = [("rover_config_bytes", RoverConfig), ("rover_lift_config_bytes", Lif
             ("rover_sac_hparams_bytes", SacHparams), ("rover_sac_state_bytes", SacState),
             ("rover_sac_collect_hparams_bytes", SacCollectHparams), ("rover_scaler_hparams_bytes", ScalerHparams),
             ("rover_trace_stream_bytes", TraceStream), ("rover_lift_viewer_config_bytes", LiftViewerConfig),
-            ("rover_dagger_hparams_bytes", DaggerHparams), ("rover_dagger_state_bytes", DaggerState)]
+            ("rover_dagger_hparams_bytes", DaggerHparams), ("rover_dagger_state_bytes", DaggerState),
+            ("rover_obs_post_segment_bytes", ObsPostSegment)]
 
 
 def load():
@@ -606,6 +623,9 @@ def load():
                                            C.c_uint64, vp]
     lib.rover_dagger_conv_update.argtypes = [pd, dgh, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, C.c_int64, vp,
                                              C.c_size_t, vp, vp, i32, vp, vp, vp, vp]
+    lib.rover_obs_post_segment_bytes.restype = C.c_size_t
+    lib.rover_obs_post_apply.argtypes = [C.POINTER(ObsPostSegment), i32, vp, i32, C.c_int64, i32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                         C.c_uint32, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:

@@ -127,6 +127,11 @@ class CameraCfg:
     near_clip: float = 0.01                            # m (:51 clippingRange)
     far_clip: float = 1000000.0
     every_n_steps: int = 1                             # re-render on steps with common_step_counter % every_n_steps == 0
+    # sensor noise on the rendered image, then a clip (obs_post.py: one HIP launch behind the render, draws keyed by the seed, the
+    # global env id, the call counter and the pixel); both None = the image as rendered, nothing launched.  Misses stay +inf unless
+    # a clip brings them to its upper bound.
+    noise: Any = None                                  # an object with n_min / n_max, mean / std or bias
+    clip: Any = None                                   # (min, max), finite
 
     @property
     def focal_px(self) -> tuple:
@@ -153,6 +158,11 @@ class CameraCfg:
             raise ValueError("camera position and orientation must be finite")
         if int(self.every_n_steps) < 1:
             raise ValueError("camera every_n_steps must be >= 1")
+        if self.noise is not None or self.clip is not None:
+            from .obs_post import image_segments
+            if int(self.width) * int(self.height) > _lib.OBS_POST_MAX_WIDTH:
+                raise ValueError(f"camera noise / clip need height * width <= {_lib.OBS_POST_MAX_WIDTH}")
+            image_segments(self)                       # ValueError for a noise object or clip the kernel cannot run
 
     def to_native(self) -> "_lib.CameraConfig":
         self.validate()
@@ -299,6 +309,10 @@ class RoverEnvCfg:
     stream_observations: bool = False
     log_values: str = "device"              # extras["log"] entries: 0-d device tensors (ORBIT) | "host": views of a pinned mirror, ONE
                                             # synchronisation per step for a trainer that .item()s every entry (skrl_utils.py:139-142)
+    # who finishes the terms of observation_post(): "torch" = a few torch ops per term and step, draws from the env's own
+    # torch.Generator; "fused" = one HIP launch (obs_post.py), draws keyed by (seed, global env id, call counter, column), so
+    # they survive a split over ranks and a checkpoint
+    observation_post_backend: str = "torch"
     # multi-GPU sharding: this process simulates global env ids [env_id_offset, env_id_offset + num_envs)
     env_id_offset: int = 0
     global_num_envs: int | None = None
@@ -342,6 +356,11 @@ class RoverEnvCfg:
             raise ValueError("log_values must be 'device' or 'host'")
         if self.mass_model not in ("lumped", "subtree_weights"):
             raise ValueError("mass_model must be 'subtree_weights' or 'lumped'")
+        if self.observation_post_backend not in ("torch", "fused"):
+            raise ValueError("observation_post_backend must be 'torch' or 'fused'")
+        if self.observation_post_backend == "fused" and self.observation_post():
+            from .obs_post import segments
+            segments(self)                             # ValueError for a noise object the kernel cannot run
         if self.commands.simple_heading:
             raise ValueError("simple_heading=True is not supported (the reference cfg uses False, rover_env_cfg.py:195)")
         if self.camera is not None:
@@ -352,7 +371,8 @@ class RoverEnvCfg:
         """Observation terms whose ORBIT post-processing (ObservationManager.compute_group: noise, then clip, then scale) is not
         what the kernels compute: any ``noise`` / ``clip``, or a ``scale`` != 1 on ``actions`` / ``height_scan`` (the kernels scale
         ``distance`` and ``heading`` only).  For these the kernels write the raw term (scale 1) and ``RoverEnv`` finishes the columns
-        in torch (three small ops per term and step: not the one-launch fast path any more, but the same step kernel)."""
+        in torch (three small ops per term and step: not the one-launch fast path any more, but the same step kernel).
+        With ``observation_post_backend = "fused"`` one HIP launch behind the step kernel finishes them instead (obs_post.py)."""
         out = {}
         for name in OBS_ORDER:
             t = self.observations[name]

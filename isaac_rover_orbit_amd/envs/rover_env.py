@@ -373,6 +373,12 @@ class RoverEnv(RLTaskEnv):
         self._obs_post = [(cols[name], t) for name, t in self.cfg.observation_post().items()]
         self._obs_post_scan = any(sl.start == 4 for sl, _ in self._obs_post)
         self._obs_gen = torch.Generator(device=self.device).manual_seed(int(self.cfg.seed))
+        # observation_post_backend = "fused": the same terms in one HIP launch on the finished row (obs_post.py), the draws keyed
+        # by (seed, global env id, call counter of the launch that wrote the row, column)
+        self._obs_fused = None
+        if self._obs_post and self.cfg.observation_post_backend == "fused":
+            from ..obs_post import ObsPost, segments
+            self._obs_fused = ObsPost(segments(self.cfg), self.obs_dim, seed=int(self.cfg.seed), env_id_offset=int(self.cfg.env_id_offset))
         self._in_user_terms = False
         self._scan_cache = None
         if self._slow_path:
@@ -417,12 +423,17 @@ class RoverEnv(RLTaskEnv):
         the observation buffers, so the image handed out by one render stays valid through the next."""
         cam = self.cfg.camera
         self._camera_cfg = None
+        self._depth_post = None
         self.extras.pop("depth", None)
         self.extras.pop("rgb", None)
         if cam is None:
             return
         self._camera_cfg = cam.to_native()
         self._camera_every = int(cam.every_n_steps)
+        if cam.noise is not None or cam.clip is not None:      # sensor noise / clip: one launch behind every render
+            from ..obs_post import DEPTH_TAG, ObsPost, image_segments
+            self._depth_post = ObsPost(image_segments(cam), int(cam.height) * int(cam.width), seed=int(self.cfg.seed),
+                                       env_id_offset=int(self.cfg.env_id_offset), tag=DEPTH_TAG)
         with torch.cuda.device(self.device):
             nb = int(self._lib.rover_camera_workspace_bytes(self._h, C.byref(self._camera_cfg)))
             if nb == 0:
@@ -437,8 +448,13 @@ class RoverEnv(RLTaskEnv):
         self.extras["rgb"] = None          # what the reference's listener reports without RGB data (rover_camera_env.py:94-98)
 
     def _render_into(self, buf: torch.Tensor):
+        """The depth image of the current state into the row-major (N, H, W) ``buf``, then ``cfg.camera``'s noise and clip in
+        place.  The noise is keyed by the call counter of the launch that left the state, so a re-render of the same state
+        repeats its noise."""
         _lib.check(self._lib.rover_camera_render(self._h, C.byref(self._camera_cfg), _ptr(self._camera_ws), _ptr(buf), self._stream()),
                    "rover_camera_render")
+        if self._depth_post is not None:
+            self._depth_post.apply(buf, self._launch_counter())
 
     def _camera_update(self, force: bool = False):
         """Render the pose the step (or reset) left behind into the next depth buffer: extras["depth"] is its (N, W, H) view."""
@@ -451,7 +467,8 @@ class RoverEnv(RLTaskEnv):
 
     def render_depth(self) -> torch.Tensor:
         """A fresh depth image of the current state, (num_envs, width, height) fp32: the permuted view of a new row-major
-        (num_envs, height, width) buffer, the layout of ``extras["depth"]``."""
+        (num_envs, height, width) buffer, the layout of ``extras["depth"]``.  With ``cfg.camera.noise`` a re-render of the same
+        state repeats its noise (the draws are keyed by the call counter, not by the number of renders)."""
         if self._camera_cfg is None:
             raise RuntimeError("render_depth needs a camera (cfg.camera)")
         buf = torch.empty(self.num_envs, self.cfg.camera.height, self.cfg.camera.width, dtype=torch.float32, device=self.device)
@@ -478,6 +495,11 @@ class RoverEnv(RLTaskEnv):
         _lib.check(self._lib.rover_set_counter(self._h, int(counter)), "rover_set_counter")
         self._sync_counter()
 
+    def _launch_counter(self) -> int:
+        """The call counter of the last reset() / step() launch (the value it ran under): what keys the fused observation and
+        depth noise of the rows that launch left, so ``set_call_counter`` resumes the noise bit for bit."""
+        return max(self.call_counter - 1, 0)
+
     def _bump_counter(self):
         # mirror of the handle's call counter in the config struct (one launch = one count): a config derived from
         # `_native_cfg` at any time (tests: the oracle's) continues in step with the handle
@@ -502,6 +524,9 @@ class RoverEnv(RLTaskEnv):
             self._native_cfg.seed_lo, self._native_cfg.seed_hi = lo, hi
             _lib.check(self._lib.rover_set_seed(self._h, lo, hi), "rover_set_seed")
             self._obs_gen.manual_seed(seed)      # the observation-noise draws of plain (non-ORBIT) noise objects
+            for post in (self._obs_fused, getattr(self, "_depth_post", None)):
+                if post is not None:             # the fused backend's draws are keyed by the same seed
+                    post.seed = seed
         return int(self.cfg.seed)
 
     def reset(self, seed: int | None = None, options=None):
@@ -643,6 +668,9 @@ class RoverEnv(RLTaskEnv):
     def _post_observations(self, obs: torch.Tensor):
         """noise, clip, scale of the observation terms in ``cfg.observation_post()`` on the finished row, in ORBIT's order."""
         self._scan_cache = None          # the raw scan of the new pose, should a consumer of ray_hits_w ask for it
+        if self._obs_fused is not None:
+            self._obs_fused.apply(obs, self._launch_counter())
+            return
         for sl, t in self._obs_post:
             x = obs[:, sl]
             nz = t.noise
