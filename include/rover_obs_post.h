@@ -11,7 +11,9 @@
  *     uniform   x = (x + u * b) + a          a = n_min, b = span = (float)((double)n_max - (double)n_min), u in (0, 1)
  *     gaussian  x = (x + a) + b * e          a = mean, b = std, e a standard normal
  *     constant  x = x + a                    a = bias
- *     clip      x = clamp(x, clip_lo, clip_hi) as torch.clip: a NaN stays a NaN, -inf goes to clip_lo, +inf to clip_hi
+ *     clip      x = clamp(x, clip_lo, clip_hi) as torch.clip: a NaN stays a NaN, -inf goes to clip_lo, +inf to clip_hi.  A clip
+ *               treats -0 < +0: clamp(x) = min(max(x, clip_lo), clip_hi) under that order (IEEE 754-2019 maximum / minimum), so
+ *               clamp(+0, lo = -0) = +0, clamp(-0, lo = +0) = +0 and clamp(+0, hi = -0) = -0, whatever the operand order.
  *     scale     x = x * scale                only when scale != 1
  * Columns outside every segment are neither read nor written.
  *

@@ -109,6 +109,13 @@ def normals(seed: int, env_ids, counter: int, width: int, tag: int) -> np.ndarra
 
 
 # ------------------------------------------------------------------------------------------------------------------- the two classes
+def _clip_ordered(v: np.ndarray, lo, hi) -> np.ndarray:
+    """The header's clip: min(max(v, lo), hi) with -0 < +0 (IEEE 754-2019 maximum / minimum), so a tie of zeros does not depend on
+    the order of the operands; every comparison with a NaN is false, so a NaN stays."""
+    v = np.where((v < lo) | ((v == lo) & np.signbit(v) & ~np.signbit(lo)), lo, v)
+    return np.where((v > hi) | ((v == hi) & ~np.signbit(v) & np.signbit(hi)), hi, v)
+
+
 class _ObsPostBase:
     def __init__(self, segs, width: int, seed: int = 0, env_id_offset: int = 0, tag: int = ROW_TAG):
         self.segments = list(segs)
@@ -155,7 +162,7 @@ class TorchObsPost(_ObsPostBase):
                 elif s.noise == CONSTANT:
                     v = v + a
                 if s.has_clip:
-                    v = np.minimum(np.maximum(v, ft(s.clip_lo)), ft(s.clip_hi))      # NaN stays NaN, as torch.clip
+                    v = _clip_ordered(v, ft(s.clip_lo), ft(s.clip_hi))               # NaN stays NaN, as torch.clip
                 if s.scale != 1.0:
                     v = v * ft(s.scale)
                 out[:, sl] = v

@@ -2,6 +2,7 @@
 
   * segments(): the cfg tables -> the segment list (stock, the noise test's table, a 3 x 3 scanner, the compat shim's noise cfgs)
   * TorchObsPost (the CPU specification) against a hand-written loop over (row, column) on rollout.philox4x32: the draw addressing
+  * normals() and the CUT table of tests/obs_post_cases.py against Python integers and math.*; the clip's order of the zeros
   * moments of the draws, shards, counters and tags
   * every refusal of rover_obs_post_apply through the library (checked before the device is looked at)
   * the kernel's scratch size from the code object
@@ -140,6 +141,115 @@ def test_uniform_spec_against_a_hand_written_loop():
     TorchObsPost([segment(0, 13, noise=Unoise(0.0, 1.0))], width, seed=seed, env_id_offset=offset).apply(one, counter)
     assert np.array_equal(one, u_all)
     assert np.array_equal(got[:, 2], (x[:, 2] + u_all[:, 2] * np.float32(1.0)) + np.float32(0.0))
+
+
+def _philox_by_hand(c, k):
+    """Random123's Philox4x32-10 on Python integers, as td3_helpers.eps_float64_by_hand restates it: (c0, c1, c2, c3), (k0, k1) ->
+    four 32-bit words."""
+    F = 0xFFFFFFFF
+    c, k = [int(v) & F for v in c], [int(v) & F for v in k]
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k[0], p1 & F, (p0 >> 32) ^ c[3] ^ k[1], p0 & F]
+        k = [(k[0] + 0x9E3779B9) & F, (k[1] + 0xBB67AE85) & F]
+    return c
+
+
+def _u_by_hand(w: int) -> float:
+    return ((w >> 9) + 0.5) * 2.0 ** -23
+
+
+def test_gaussian_spec_against_a_hand_written_loop():
+    """obs_post.normals against Python integers and math.*: words (0, 1) of quad q give columns 4 q (cosine) and 4 q + 1 (sine),
+    words (2, 3) give 4 q + 2 and 4 q + 3.  13 columns: the last quad gives its cosine column alone.  Tolerance
+    4 * 2**-52 * max(1, |e|): both sides are float64, the margin is for last-bit differences between libm's and numpy's log, cos
+    and sin."""
+    seed, counter, offset, n, width = (0x1234 << 32) | 0xABCD, (7 << 32) | 5, 1000, 3, 13
+    got = obs_post.normals(seed, offset + np.arange(n), counter, width, ROW_TAG)
+    assert got.shape == (n, width) and got.dtype == np.float64
+    for r in range(n):
+        for c in range(width):
+            w = _philox_by_hand((offset + r, 5, 7, ROW_TAG | (c // 4)), (0xABCD, 0x1234))
+            wa, wb = (w[0], w[1]) if c % 4 < 2 else (w[2], w[3])
+            rho = math.sqrt(-2.0 * math.log(_u_by_hand(wa)))
+            ang = 2.0 * math.pi * _u_by_hand(wb)
+            e = rho * (math.cos(ang) if c % 2 == 0 else math.sin(ang))
+            assert abs(got[r, c] - e) <= 4 * 2.0 ** -52 * max(1.0, abs(e)), (r, c, got[r, c], e)
+    # the uniform and the Gaussian draws read the same words: column c's uniform is the word a hand count gives it
+    u = obs_post.uniforms(seed, offset + np.arange(n), counter, width, ROW_TAG)
+    w = _philox_by_hand((offset + 2, 5, 7, ROW_TAG | 3), (0xABCD, 0x1234))
+    assert float(u[2, 12]) == _u_by_hand(w[0])
+
+
+def test_spec_clip_orders_the_zeros():
+    """The clip rule of include/rover_obs_post.h at ties of zeros: -0 < +0, whatever the order of the operands.  numpy's own
+    minimum / maximum return the bound on such a tie here, and which operand a SIMD lane returns is not something to rely on, so
+    the lengths cover a scalar tail, one vector and more than one."""
+    from obs_post_cases import ZERO_CLIPS, ZERO_SCALES, ZERO_X, clamp_ordered, zero_row, zero_segments, zero_want
+    for scale in ZERO_SCALES:
+        for length in (1, 3, 8, 17):
+            for (lo, hi) in ZERO_CLIPS:
+                x = np.array([ZERO_X[(i + i // 3) % 2] for i in range(length)], np.float32)
+                rows = np.stack([x, -x])
+                want = np.array([[np.float32(clamp_ordered(v, lo, hi)) * np.float32(scale) for v in row] for row in rows], np.float32)
+                got = TorchObsPost([segment(0, length, clip=(lo, hi), scale=scale)], length).apply(rows.copy(), 0)
+                assert np.array_equal(got.view(np.int32), want.view(np.int32)), (scale, length, lo, hi, got, want)
+                got64 = TorchObsPost([segment(0, length, clip=(lo, hi), scale=scale)], length).apply64(rows, 0)
+                assert np.array_equal(np.signbit(got64), np.signbit(want)) and np.array_equal(got64, want)
+        # the table as the GPU test runs it: eight segments of two columns
+        got = TorchObsPost(zero_segments(scale), 16).apply(zero_row(3), 0)
+        assert np.array_equal(got.view(np.int32), zero_want(scale, 3).view(np.int32))
+    # what the rule says, spelled out once
+    assert [math.copysign(1.0, clamp_ordered(x, lo, hi)) for x, lo, hi in
+            ((0.0, -0.0, 4.0), (-0.0, 0.0, 4.0), (0.0, -4.0, -0.0), (-0.0, -4.0, 0.0), (0.0, 0.0, -0.0))] == [1.0, 1.0, -1.0, -1.0, -1.0]
+    assert math.isnan(clamp_ordered(math.nan, 0.0, 0.0)) and clamp_ordered(-math.inf, -0.0, 4.0) == 0.0
+    assert math.copysign(1.0, clamp_ordered(-math.inf, -0.0, 4.0)) == -1.0
+    # away from ties the rule is the plain clip, NaN staying
+    x = np.array([[math.nan, -1.0, 0.05, 7.0, -math.inf, math.inf, -0.0, 1e-40]], np.float32)
+    got = TorchObsPost([segment(0, 8, clip=(-0.5, 0.5))], 8).apply(x.copy(), 0)
+    want = np.array([[np.float32(clamp_ordered(v, -0.5, 0.5)) for v in x[0]]], np.float32)
+    assert np.array_equal(got.view(np.int32), want.view(np.int32))
+
+
+def test_cut_table_spec_against_a_hand_written_loop():
+    """CUT's uniform, constant and clip columns element by element: three noise kinds in quad 1, one-column segments, segments given
+    out of column order, a segment across two quads.  The words come from the integer Philox above, the clip from clamp_ordered;
+    columns no segment covers keep their NaN payloads."""
+    from obs_post_cases import CUT_UNCOVERED, CUT_WIDTH, clamp_ordered, cut, cut_rows, gaussian_columns
+    seed, counter, offset, n = (0x1234 << 32) | 0xABCD, (7 << 32) | 5, 2 ** 32 - 2, 5          # rows 2 .. 4 are env ids 0 .. 2 again
+    segs = cut()
+    assert [s.col_lo for s in segs] != sorted(s.col_lo for s in segs) and len(segs) == _lib.OBS_POST_MAX_SEGMENTS
+    assert min(s.col_lo for s in segs) // 4 == 1
+    x = cut_rows(n)
+    got = TorchObsPost(segs, CUT_WIDTH, seed=seed, env_id_offset=offset).apply(x.copy(), counter)
+    gauss = gaussian_columns(segs)
+    assert gauss == [41, 42, 43, 44, 45, 46, 6, 59, 60]
+    checked = 0
+    for r in range(n):
+        for s in segs:
+            if s.noise == obs_post.GAUSSIAN:
+                continue
+            for c in range(s.col_lo, s.col_hi):
+                v = x[r, c]
+                if s.noise == obs_post.UNIFORM:
+                    w = _philox_by_hand(((offset + r) % 2 ** 32, 5, 7, ROW_TAG | (c // 4)), (0xABCD, 0x1234))[c % 4]
+                    v = (v + np.float32(_u_by_hand(w)) * np.float32(s.b)) + np.float32(s.a)
+                elif s.noise == obs_post.CONSTANT:
+                    v = v + np.float32(s.a)
+                if s.has_clip:
+                    v = np.float32(clamp_ordered(v, s.clip_lo, s.clip_hi))
+                if s.scale != 1.0:
+                    v = v * np.float32(s.scale)
+                assert got[r, c].view(np.int32) == np.float32(v).view(np.int32), (r, c)
+                checked += 1
+    assert checked == n * (1 + 4 + 1 + 3 + 11)
+    un = list(CUT_UNCOVERED)
+    assert np.array_equal(got[:, un].view(np.int32), x[:, un].view(np.int32)) and np.isnan(x[:, un]).all()
+    # the Gaussian columns moved, stay finite and respect their clip; [41, 47) is clipped to +-0.5
+    assert np.isfinite(got[:, gauss]).all() and (got[:, gauss] != x[:, gauss]).all() and np.abs(got[:, 41:47]).max() <= 0.5
+    # env ids wrap at 2**32 (lo32 of env_id_offset + r): rows 2 .. 4 are rows 0 .. 2 of offset 0 on the same inputs
+    zero = TorchObsPost(segs, CUT_WIDTH, seed=seed, env_id_offset=0).apply(x[2:].copy(), counter)
+    assert np.array_equal(got[2:].view(np.int32), zero.view(np.int32))
 
 
 def test_moments_of_the_draws():
