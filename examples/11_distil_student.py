@@ -71,8 +71,40 @@ def build_parser() -> argparse.ArgumentParser:
                     help="Gaussian sensor noise of standard deviation S (m) on the depth image the student sees (default: none)")
     ap.add_argument("--depth_clip_max", type=float, default=None, metavar="M",
                     help="clip the depth image to [0, M] m after the noise: misses (+inf) become M (default: no clip)")
+    # a depth sensor model between the render and the noise / clip above (CameraCfg.sensor, depth_sensor.py); none by default
+    ap.add_argument("--depth_range", type=float, nargs=2, default=None, metavar=("MIN", "MAX"),
+                    help="the sensor's working range (m): depths outside it, misses included, read --depth_invalid")
+    ap.add_argument("--depth_sigma", type=float, nargs=3, default=None, metavar=("S0", "S1", "S2"),
+                    help="axial noise of standard deviation S0 + S1 z + S2 z^2 (m) at depth z")
+    ap.add_argument("--depth_dropout", type=float, nargs=2, default=None, metavar=("P", "P_EDGE"),
+                    help="probability that a pixel loses its data, off and on a depth edge")
+    ap.add_argument("--depth_disparity_step", type=float, default=None, metavar="PX", help="quantise the disparity in steps of PX pixels")
+    ap.add_argument("--depth_baseline", type=float, default=None, metavar="M", help="stereo baseline (m) of the disparity steps (default 0.05)")
+    ap.add_argument("--depth_invalid", type=float, default=None, metavar="V", help="what a pixel without data reads (default 0)")
     tracking.add_arguments(ap)
     return ap
+
+
+def sensor_cfg(args):
+    """``CameraCfg.sensor`` of the --depth_range / _sigma / _dropout / _disparity_step / _baseline / _invalid flags; None without any."""
+    from isaac_rover_orbit_amd.cfg import DepthSensorCfg
+    given = (args.depth_range, args.depth_sigma, args.depth_dropout, args.depth_disparity_step, args.depth_baseline, args.depth_invalid)
+    if all(v is None for v in given):
+        return None
+    s = DepthSensorCfg()
+    if args.depth_range is not None:
+        s.range_min, s.range_max = args.depth_range
+    if args.depth_sigma is not None:
+        s.sigma = tuple(args.depth_sigma)
+    if args.depth_dropout is not None:
+        s.p_drop, s.p_edge = args.depth_dropout
+    if args.depth_disparity_step is not None:
+        s.disparity_step = args.depth_disparity_step
+    if args.depth_baseline is not None:
+        s.baseline = args.depth_baseline
+    if args.depth_invalid is not None:
+        s.invalid_value = args.depth_invalid
+    return s
 
 
 class DepthNoise:
@@ -82,11 +114,12 @@ class DepthNoise:
         self.mean, self.std = 0.0, std
 
 
-def make_env(n: int, student: str = "mlp31", depth_noise_std: float | None = None, depth_clip_max: float | None = None):
+def make_env(n: int, student: str = "mlp31", depth_noise_std: float | None = None, depth_clip_max: float | None = None, sensor=None):
     terrain = T.make_procedural_terrain((2048, 2048), seed=1234)
     terrain.make_spawns(2 * n)
     cfg = RoverEnvCfg(); cfg.scene.num_envs = n; cfg.terrain.kind = "custom"
     cfg.camera = dagger_conv.student_camera_cfg() if student == "conv" else dagger.student_camera_cfg()
+    cfg.camera.sensor = sensor
     if depth_noise_std is not None:
         cfg.camera.noise = DepthNoise(depth_noise_std)
     if depth_clip_max is not None:
@@ -96,7 +129,7 @@ def make_env(n: int, student: str = "mlp31", depth_noise_std: float | None = Non
 
 def evaluate(args):
     """examples/03_eval_policy.py's loop with the student's rows in place of the env's."""
-    _, env = make_env(args.num_envs, args.student, args.depth_noise_std, args.depth_clip_max)
+    _, env = make_env(args.num_envs, args.student, args.depth_noise_std, args.depth_clip_max, sensor_cfg(args))
     if args.student == "conv":
         act = dagger_conv.ConvStudent.from_checkpoint(args.eval).act
     else:
@@ -128,7 +161,7 @@ def main(argv=None):
     dev = torch.device("cuda")
     n = args.num_envs
     M = args.memory_size or max(16, -(-2 * args.batch_size // n))
-    cfg, env = make_env(n, args.student, args.depth_noise_std, args.depth_clip_max)
+    cfg, env = make_env(n, args.student, args.depth_noise_std, args.depth_clip_max, sensor_cfg(args))
     teacher_sd = torch.load(args.teacher, map_location="cpu", weights_only=False)["policy"]
     memory = ReplayMemory(M, n, device=dev)
     student = ppo_example.Net(2, True).to(dev)

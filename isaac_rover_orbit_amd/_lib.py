@@ -75,6 +75,7 @@ EXPORTS = [
     "rover_dagger_conv_stem_floats", "rover_dagger_conv_param_floats", "rover_dagger_conv_stem_offset",  # rover_dagger_conv.h
     "rover_dagger_conv_chunk_rows", "rover_dagger_conv_workspace_bytes", "rover_dagger_conv_rows", "rover_dagger_conv_update",
     "rover_obs_post_segment_bytes", "rover_obs_post_apply",  # rover_obs_post.h
+    "rover_depth_sensor_cfg_bytes", "rover_depth_sensor_apply",  # rover_depth_sensor.h
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -270,6 +271,20 @@ class ObsPostSegment(C.Structure):
                 ("has_clip", C.c_int32), ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("scale", C.c_float)]
 
 
+DEPTH_SENSOR_MAX_PIXELS = 16384
+# the depth sensor model's two streams (include/rover_depth_sensor.h), named like the two above by the high half of word 3
+DEPTH_SENSOR_STREAM_NORMAL = 0x444E0000
+DEPTH_SENSOR_STREAM_DROPOUT = 0x44550000
+
+
+class DepthSensorCfg(C.Structure):
+    """Mirror of ``struct rover_depth_sensor_cfg`` (include/rover_depth_sensor.h)."""
+    _fields_ = [("range_min", C.c_float), ("range_max", C.c_float), ("sigma0", C.c_float), ("sigma1", C.c_float),
+                ("sigma2", C.c_float), ("p_drop", C.c_float), ("p_edge", C.c_float), ("edge_rel", C.c_float),
+                ("edge_at_invalid", C.c_int32), ("disparity_step", C.c_float), ("fb", C.c_float), ("inv_step", C.c_float),
+                ("invalid_value", C.c_float)]
+
+
 class RoverHipError(RuntimeError):
     pass
 
@@ -365,7 +380,7 @@ _MIRRORS = [("rover_config_bytes", RoverConfig), ("rover_lift_config_bytes", Lif
             ("rover_sac_collect_hparams_bytes", SacCollectHparams), ("rover_scaler_hparams_bytes", ScalerHparams),
             ("rover_trace_stream_bytes", TraceStream), ("rover_lift_viewer_config_bytes", LiftViewerConfig),
             ("rover_dagger_hparams_bytes", DaggerHparams), ("rover_dagger_state_bytes", DaggerState),
-            ("rover_obs_post_segment_bytes", ObsPostSegment)]
+            ("rover_obs_post_segment_bytes", ObsPostSegment), ("rover_depth_sensor_cfg_bytes", DepthSensorCfg)]
 
 
 def load():
@@ -626,6 +641,9 @@ def load():
     lib.rover_obs_post_segment_bytes.restype = C.c_size_t
     lib.rover_obs_post_apply.argtypes = [C.POINTER(ObsPostSegment), i32, vp, i32, C.c_int64, i32, C.c_uint64, C.c_uint64, C.c_uint64,
                                          C.c_uint32, vp]
+    lib.rover_depth_sensor_cfg_bytes.restype = C.c_size_t
+    lib.rover_depth_sensor_apply.argtypes = [C.POINTER(DepthSensorCfg), vp, vp, i32, i32, C.c_int64, i32, C.c_uint64, C.c_uint64,
+                                             C.c_uint64, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:

@@ -112,6 +112,54 @@ class TerrainCfg:
 
 
 @dataclass
+class DepthSensorCfg:
+    """A stereo / structured-light depth sensor in front of the rendered depth (include/rover_depth_sensor.h, depth_sensor.py):
+    a working range, pixel dropout that is likelier on depth edges, axial noise sigma(z) = sigma[0] + sigma[1] z + sigma[2] z^2
+    and disparity quantisation, in that order; a pixel without data reads ``invalid_value``.  The defaults change nothing but a
+    miss (+inf stays valid under ``range_max = inf``)."""
+    range_min: float = 0.0                             # m
+    range_max: float = math.inf
+    sigma: tuple = (0.0, 0.0, 0.0)                     # m, 1, 1 / m
+    p_drop: float = 0.0                                # dropout probability of a pixel off an edge
+    p_edge: float = 0.0                                # ... of a pixel on one
+    edge_rel: float = 0.1                              # |z - zn| > edge_rel * min(z, zn) to a 4-neighbour makes an edge
+    edge_at_invalid: bool = True                       # a neighbour outside the range makes one too
+    disparity_step: float = 0.0                        # px; 0 = no quantisation
+    baseline: float = 0.05                             # m
+    invalid_value: float = 0.0                         # what depth cameras report
+
+    def to_native(self, focal_px: float) -> "_lib.DepthSensorCfg":
+        """The library's struct, checked as the library checks it (the values as the fp32 struct holds them); ``focal_px`` is the
+        camera's horizontal focal length in pixels: fb = float32(focal_px * baseline) and inv_step = float32(1 / step), both
+        formed in double."""
+        if len(tuple(self.sigma)) != 3:
+            raise ValueError("depth sensor sigma must be (sigma0, sigma1, sigma2)")
+        c = _lib.DepthSensorCfg()
+        c.range_min, c.range_max = float(self.range_min), float(self.range_max)
+        c.sigma0, c.sigma1, c.sigma2 = (float(v) for v in self.sigma)
+        c.p_drop, c.p_edge, c.edge_rel = float(self.p_drop), float(self.p_edge), float(self.edge_rel)
+        c.edge_at_invalid = 1 if self.edge_at_invalid else 0
+        c.disparity_step, c.invalid_value = float(self.disparity_step), float(self.invalid_value)
+        ok = lambda v: math.isfinite(v) and v >= 0.0   # noqa: E731
+        if not (ok(c.sigma0) and ok(c.sigma1) and ok(c.sigma2) and ok(c.edge_rel)):
+            raise ValueError("depth sensor sigma and edge_rel must be finite and >= 0")
+        if not (0.0 <= c.p_drop <= 1.0 and 0.0 <= c.p_edge <= 1.0):
+            raise ValueError("depth sensor p_drop and p_edge must be in [0, 1]")
+        if not c.range_min >= 0.0 or not c.range_max >= c.range_min:
+            raise ValueError("depth sensor range must satisfy 0 <= range_min <= range_max (range_max may be inf)")
+        if not ok(c.disparity_step):
+            raise ValueError("depth sensor disparity_step must be finite and >= 0")
+        if c.disparity_step > 0.0:
+            c.fb = float(focal_px) * float(self.baseline)
+            c.inv_step = 1.0 / float(self.disparity_step)
+            if not (math.isfinite(c.fb) and c.fb > 0.0 and math.isfinite(c.inv_step) and c.inv_step > 0.0):
+                raise ValueError("depth sensor focal length * baseline and 1 / disparity_step must be finite and > 0")
+        if math.isnan(c.invalid_value):
+            raise ValueError("depth sensor invalid_value must not be a NaN")
+        return c
+
+
+@dataclass
 class CameraCfg:
     """The rover's on-board depth camera (``RoverEnvCamera``, rover_camera_env.py:44-62): a pinhole on the Body link whose
     ``distance_to_camera`` image is a ray cast against the terrain's triangle mesh (include/rover_camera.h; RGB is not rendered)."""
@@ -132,6 +180,9 @@ class CameraCfg:
     # a clip brings them to its upper bound.
     noise: Any = None                                  # an object with n_min / n_max, mean / std or bias
     clip: Any = None                                   # (min, max), finite
+    # a depth sensor model between the render and noise / clip (depth_sensor.py: one HIP launch of its own, keyed the same way);
+    # None = nothing launched.  With one, extras["depth_valid"] counts each env's pixels that carry data.
+    sensor: DepthSensorCfg | None = None
 
     @property
     def focal_px(self) -> tuple:
@@ -163,6 +214,10 @@ class CameraCfg:
             if int(self.width) * int(self.height) > _lib.OBS_POST_MAX_WIDTH:
                 raise ValueError(f"camera noise / clip need height * width <= {_lib.OBS_POST_MAX_WIDTH}")
             image_segments(self)                       # ValueError for a noise object or clip the kernel cannot run
+        if self.sensor is not None:
+            if int(self.width) * int(self.height) > _lib.DEPTH_SENSOR_MAX_PIXELS:
+                raise ValueError(f"a camera sensor needs height * width <= {_lib.DEPTH_SENSOR_MAX_PIXELS}")
+            self.sensor.to_native(self.focal_px[0])    # ValueError for a parameter the kernel refuses
 
     def to_native(self) -> "_lib.CameraConfig":
         self.validate()

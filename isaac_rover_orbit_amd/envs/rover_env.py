@@ -424,12 +424,17 @@ class RoverEnv(RLTaskEnv):
         cam = self.cfg.camera
         self._camera_cfg = None
         self._depth_post = None
+        self._depth_sensor = None
         self.extras.pop("depth", None)
         self.extras.pop("rgb", None)
+        self.extras.pop("depth_valid", None)
         if cam is None:
             return
         self._camera_cfg = cam.to_native()
         self._camera_every = int(cam.every_n_steps)
+        if cam.sensor is not None:                             # the sensor model: one launch behind every render, ahead of noise / clip
+            from ..depth_sensor import DepthSensor
+            self._depth_sensor = DepthSensor.from_camera(cam, seed=int(self.cfg.seed), env_id_offset=int(self.cfg.env_id_offset))
         if cam.noise is not None or cam.clip is not None:      # sensor noise / clip: one launch behind every render
             from ..obs_post import DEPTH_TAG, ObsPost, image_segments
             self._depth_post = ObsPost(image_segments(cam), int(cam.height) * int(cam.width), seed=int(self.cfg.seed),
@@ -441,18 +446,24 @@ class RoverEnv(RLTaskEnv):
             self._camera_ws = torch.zeros((nb + 3) // 4, dtype=torch.float32, device=self.device)
             self._depth = [torch.full((self.num_envs, cam.height, cam.width), float("inf"), dtype=torch.float32, device=self.device)
                            for _ in range(self._nbuf)]
+            if self._depth_sensor is not None:                 # each depth buffer's count of pixels that carry data
+                self._depth_valid = [torch.zeros(self.num_envs, dtype=torch.int32, device=self.device) for _ in range(self._nbuf)]
             _lib.check(self._lib.rover_camera_prepare(self._h, C.byref(self._camera_cfg), _ptr(self._camera_ws), nb, self._stream()),
                        "rover_camera_prepare")
         self._depth_cur = 0
         self.extras["depth"] = self._depth[0].permute(0, 2, 1)
         self.extras["rgb"] = None          # what the reference's listener reports without RGB data (rover_camera_env.py:94-98)
+        if self._depth_sensor is not None:
+            self.extras["depth_valid"] = self._depth_valid[0]
 
-    def _render_into(self, buf: torch.Tensor):
-        """The depth image of the current state into the row-major (N, H, W) ``buf``, then ``cfg.camera``'s noise and clip in
-        place.  The noise is keyed by the call counter of the launch that left the state, so a re-render of the same state
-        repeats its noise."""
+    def _render_into(self, buf: torch.Tensor, valid: torch.Tensor | None = None):
+        """The depth image of the current state into the row-major (N, H, W) ``buf``, then ``cfg.camera``'s sensor model (its
+        per-env count of valid pixels into ``valid``), then its noise and clip, all in place.  The draws are keyed by the call
+        counter of the launch that left the state, so a re-render of the same state repeats its noise."""
         _lib.check(self._lib.rover_camera_render(self._h, C.byref(self._camera_cfg), _ptr(self._camera_ws), _ptr(buf), self._stream()),
                    "rover_camera_render")
+        if self._depth_sensor is not None:
+            self._depth_sensor.apply(buf, self._launch_counter(), valid_out=valid)
         if self._depth_post is not None:
             self._depth_post.apply(buf, self._launch_counter())
 
@@ -462,7 +473,11 @@ class RoverEnv(RLTaskEnv):
             return
         self._depth_cur = (self._depth_cur + 1) % self._nbuf
         buf = self._depth[self._depth_cur]
-        self._render_into(buf)
+        if self._depth_sensor is None:
+            self._render_into(buf)
+        else:
+            self._render_into(buf, self._depth_valid[self._depth_cur])
+            self.extras["depth_valid"] = self._depth_valid[self._depth_cur]
         self.extras["depth"] = buf.permute(0, 2, 1)
 
     def render_depth(self) -> torch.Tensor:
@@ -524,7 +539,7 @@ class RoverEnv(RLTaskEnv):
             self._native_cfg.seed_lo, self._native_cfg.seed_hi = lo, hi
             _lib.check(self._lib.rover_set_seed(self._h, lo, hi), "rover_set_seed")
             self._obs_gen.manual_seed(seed)      # the observation-noise draws of plain (non-ORBIT) noise objects
-            for post in (self._obs_fused, getattr(self, "_depth_post", None)):
+            for post in (self._obs_fused, getattr(self, "_depth_post", None), getattr(self, "_depth_sensor", None)):
                 if post is not None:             # the fused backend's draws are keyed by the same seed
                     post.seed = seed
         return int(self.cfg.seed)
