@@ -4,8 +4,9 @@
 // counter-based draw and the beta mix.  See include/rover_dagger.h for the contract.
 //
 //   rover_dagger_rows_kernel  image + env rows -> student rows (and the sanitised env rows the teacher reads); with a record struct
-//                             also reward / terminated / ring_pos of the transition and the batch's row indices
-//                             (offpolicy_collect.hpp's index stream)
+//                             also reward / terminated / ring_pos of the transition and the batch's row indices.  The pixel
+//                             rule, the record struct with its host checks and the index stream's tag are
+//                             collect_record.hpp's, shared with dagger_conv_kernels.hip
 //   rover_dagger_act_kernel   TEACHER: tanh mean -> the label; STUDENT: tanh mean, the draw, the mix -> the env's action.  The mode
 //                             is a launch argument and the branch on it is wave-uniform.
 #include <hip/hip_runtime.h>
@@ -28,33 +29,13 @@ constexpr int PIX = 961;                      // 31 x 31 pixels = OBS - PROP
 constexpr int ROWS_THREADS = 256;             // rows kernel: one 16-byte piece of the output per thread
 enum { DAGGER_TEACHER = 0, DAGGER_STUDENT = 1 };
 
-struct DaggerRec {
-    const float *rew;
-    const uint8_t *terminated;
-    float *rew_out;
-    uint8_t *term_out;
-    int32_t *ring_pos_entry;
-    int32_t ring_pos_value;
-    int64_t *idx_out;
-    int batch;
-    uint64_t mem_rows;
-    uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
-};
-
-// a pixel that is NaN, +-inf or negative counts as `clip` (d >= 0 fails for NaN, -inf and every negative; +inf falls to the min)
-__device__ __forceinline__ float depth_value(float d, float clip, float scale)
-{
-    const float v = d >= 0.0f ? d : clip;
-    return scale * fminf(v, clip);
-}
-
 // VEC: every pointer is 16-byte aligned.  Thread gid owns floats [4 gid, 4 gid + 4) of the output, which is `total` = n * 965
 // floats.  Output float 965 r + 4 + p and depth float 961 r + p lie 4 r + 4 floats apart: an aligned output piece inside one row's
 // pixel columns is an aligned piece of the image.  The grid also covers n and batch threads for the record and the indices.
 template <bool VEC>
 __global__ __launch_bounds__(ROWS_THREADS) void rover_dagger_rows_kernel(const float *__restrict__ depth, const float *__restrict__ env,
                                                                          float *__restrict__ out, float *__restrict__ teacher,
-                                                                         size_t total, int n, float clip, float scale, DaggerRec R)
+                                                                         size_t total, int n, float clip, float scale, RecFields R)
 {
     const size_t gid = (size_t)blockIdx.x * ROWS_THREADS + threadIdx.x;
     const size_t g0 = 4 * gid;
@@ -139,12 +120,6 @@ __global__ __launch_bounds__(TDC_THREADS) void rover_dagger_act_kernel(rover_pol
     }
 }
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-
 // rover_dagger_rows and rover_dagger_record: argument checks, the vector / scalar choice, the grid and the launch
 int rows_launch(const char *fn, const rover_dagger_hparams *h, const float *depth, const float *env_raw, int32_t n, float *rows_out,
                 float *teacher_rows_out, const float *rew, const uint8_t *terminated, float *rew_out, uint8_t *term_out,
@@ -161,12 +136,7 @@ int rows_launch(const char *fn, const rover_dagger_hparams *h, const float *dept
         (teacher_rows_out && (overlap(teacher_rows_out, bytes, env_raw, bytes) || overlap(teacher_rows_out, bytes, depth, dbytes) ||
                               overlap(teacher_rows_out, bytes, rows_out, bytes))))
         return collect_fail(ROVER_ERR_INVALID, fn, ": the outputs must not alias the inputs or each other");
-    const int given = (rew != nullptr) + (terminated != nullptr) + (rew_out != nullptr) + (term_out != nullptr);
-    if (given != 0 && given != 4) return collect_fail(ROVER_ERR_INVALID, fn, ": rew, terminated, rew_out, term_out: all or none NULL");
-    if (idx_out) {
-        if (batch < 1) return collect_fail(ROVER_ERR_INVALID, fn, ": batch must be >= 1");
-        if (mem_rows < 1 || mem_rows > ((int64_t)1 << 32)) return collect_fail(ROVER_ERR_INVALID, fn, ": mem_rows must lie in [1, 2^32]");
-    }
+    if (int rc = rec_check(fn, rew, terminated, rew_out, term_out, idx_out, batch, mem_rows)) return rc;
     const bool vec = ((reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(env_raw) | reinterpret_cast<uintptr_t>(rows_out) |
                        reinterpret_cast<uintptr_t>(teacher_rows_out)) & 15) == 0;
     size_t threads = (total + 3) >> 2;
@@ -174,13 +144,7 @@ int rows_launch(const char *fn, const rover_dagger_hparams *h, const float *dept
     if (idx_out && threads < (size_t)batch) threads = (size_t)batch;
     const size_t blocks = (threads + ROWS_THREADS - 1) / ROWS_THREADS;
     if (blocks > 0x7FFFFFFFu) return collect_fail(ROVER_ERR_INVALID, fn, ": n too large");
-    DaggerRec R = {};
-    R.rew = rew; R.terminated = terminated; R.rew_out = rew_out; R.term_out = term_out;
-    R.ring_pos_entry = ring_pos_entry; R.ring_pos_value = ring_pos_value;
-    R.idx_out = idx_out; R.batch = idx_out ? batch : 0; R.mem_rows = idx_out ? (uint64_t)mem_rows : 1u;
-    R.seed_lo = h->seed_lo; R.seed_hi = h->seed_hi;
-    R.ctr_lo = (uint32_t)(counter & 0xFFFFFFFFu);
-    R.ctr_hi = (uint32_t)(counter >> 32);
+    const RecFields R = rec_fill(h, counter, rew, terminated, rew_out, term_out, ring_pos_entry, ring_pos_value, idx_out, batch, mem_rows);
     if (vec)
         hipLaunchKernelGGL(rover_dagger_rows_kernel<true>, dim3((unsigned)blocks), dim3(ROWS_THREADS), 0, static_cast<hipStream_t>(stream),
                            depth, env_raw, rows_out, teacher_rows_out, total, n, h->depth_clip, h->depth_scale, R);

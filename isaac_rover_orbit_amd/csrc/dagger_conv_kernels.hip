@@ -9,7 +9,11 @@
 //   dagger_conv_forward_kernel       update: one workgroup per sampled row, the same stem from the image ring into a gathered row
 //   dagger_conv_backward_kernel      update: one workgroup per chunk of 8 sampled rows; recomputes the pre-activations, sums
 //                                    db2 / dw2 / db1 per thread and dW1 = dpre^T im2col(x) on v_mfma_f32_16x16x4_f32
-//   dagger_conv_head / norm / final / adam   rover_dagger.h's loss head and optimiser tail over the vector [head | stem]
+//   dagger_head / norm / final / adam_kernel   dagger_tail.hpp's loss head and optimiser tail, shared with dagger_kernels.hip: Adam
+//                                    over the vector [head | stem], the replicas of the head alone
+//
+// The record struct with its host checks, the pixel rule depth_value() and the index stream's tag are collect_record.hpp's,
+// shared with dagger_collect_kernels.hip and the off-policy collectors.
 //
 // stem_feature() is the ONE device function that forms a feature (stem_pre() is its first half, which the backward calls for the
 // pre-activations): every kernel agrees on the bits.  The network's forward, backward, weight gradients, the input gradient (the
@@ -26,10 +30,10 @@
 #include "rover_internal.hpp"
 #include "offpolicy_net.hpp"
 #include "train_math.hpp"
+#include "dagger_tail.hpp"
 
 namespace {
 
-using State = rover_dagger_state;
 constexpr int IH = ROVER_DAGGER_CONV_IMG_H, IW = ROVER_DAGGER_CONV_IMG_W, PIXN = ROVER_DAGGER_CONV_PIXELS;
 constexpr int FS = 31, FEAT = FS * FS;                       // 31 x 31 features = OBS - PROP
 constexpr int KH = 6, KW = 10, SH = 3, SW = 5, PADH = 3;     // kernel, stride, rows of zero padding above and below
@@ -41,18 +45,9 @@ constexpr int XS_F = (IH + 2 * PADH) * IW;                   // the x image in L
 constexpr int RC = 8;                                        // sampled rows per workgroup of the backward
 constexpr int DPP = 68;                                      // pitch of a wave's dpre rows in LDS: lanes (c, k) hit banks 4 c + k
 constexpr int NSUM = 2 * CCH + 1;                            // db1[8], dw2[8], db2
-constexpr int NORM_BLOCKS = 64;                              // fixed chunks of the gradient's sum of squares
-constexpr uint32_t INDEX_TAG = 0x54335300u;                  // "T3S\0": the TD3 collector's index stream (rover_td3_collect.h)
 static_assert(O_B2 + 1 == STEM_F && FEAT + PROP == OBS && PIXN == IH * IW, "stem layout");
 static_assert(PIXN / 4 == 7 * ST + 16, "stage_image's load plan");
 static_assert(SWAVES * 2 * 64 >= FEAT, "two groups of 64 outputs per wave cover the features");
-
-// a pixel that is NaN, +-inf or negative counts as `clip` (rover_dagger.h's rule, the same expression)
-__device__ __forceinline__ float depth_value(float d, float clip, float scale)
-{
-    const float v = d >= 0.0f ? d : clip;
-    return scale * fminf(v, clip);
-}
 
 // The image of one env into LDS rows 3 .. 92 of xs (rows 0 .. 2 and 93 .. 95 are the zero padding), 16 bytes per lane per load,
 // all of a thread's loads in flight before the first use.  RAW: src holds metres; x = depth_value() also goes to img_out (the
@@ -118,23 +113,10 @@ __device__ __forceinline__ float stem_feature(const float *xs, const float *__re
 }
 
 // ---- collector
-struct ConvRec {
-    const float *rew;
-    const uint8_t *terminated;
-    float *rew_out;
-    uint8_t *term_out;
-    int32_t *ring_pos_entry;
-    int32_t ring_pos_value;
-    int64_t *idx_out;
-    int batch;
-    uint64_t mem_rows;
-    uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
-};
-
 __global__ __launch_bounds__(ST) void rover_dagger_conv_rows_kernel(const float *__restrict__ prm, const float *__restrict__ depth,
                                                                     const float *__restrict__ env, float *__restrict__ slot,
                                                                     float *__restrict__ img, float *__restrict__ teacher, int n,
-                                                                    float clip, float scale, ConvRec R)
+                                                                    float clip, float scale, RecFields R)
 {
     __shared__ __align__(16) float xs[XS_F];
     const int r = blockIdx.x, tid = threadIdx.x;
@@ -293,122 +275,30 @@ __global__ __launch_bounds__(ST, 4) void dagger_conv_backward_kernel(const float
     if (tid < NSUM) p[O_B1 + tid] = xs[tid * ST];             // b1[8], w2[8], b2: the order of the packed stem
 }
 
-// ---- loss head, norm, final, Adam: rover_dagger.h's (the text of dagger_kernels.hip's kernels; that translation unit keeps them in
-// its unnamed namespace), Adam over [head | stem] with the replicas of the head alone
-struct Head {
-    const float *z;                    // the last layer's output, pitch 4
-    const float *labels;               // (valid, 2)
-    const int64_t *idx; int64_t valid;
-    float inv_n;
-    float *dz;                         // dZ6, pitch 4
-    float *dz_out;                     // (rows, 2) or NULL
-    int rows;
-    float *rowp;
-};
-__global__ __launch_bounds__(FT) void dagger_conv_head_kernel(Head A)
-{
-    __shared__ float red[FT];
-    const int r = blockIdx.x * FT + threadIdx.x;
-    float v = 0.0f;
-    if (r < A.rows) {
-        int64_t i = A.idx[r];
-        if (i < 0 || i >= A.valid) i = 0;
-        const size_t o = (size_t)r * MW[NL - 1];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const float t = rv_tanhf(A.z[o + c]);
-            const float d = t - A.labels[2 * i + c];
-            const float tt = t * t;
-            const float g = d * (1.0f - tt);
-            const float dz = g * A.inv_n;
-            A.dz[o + c] = dz;
-            if (A.dz_out) A.dz_out[2 * (size_t)r + c] = dz;
-            v = v + d * d;
-        }
-    }
-    const float tot = block_sum(v, red);
-    if (threadIdx.x == 0) A.rowp[(size_t)blockIdx.x * RP] = tot;
-}
-
-__global__ __launch_bounds__(FT) void dagger_conv_norm_kernel(const float *grad, int P, float *normp)
-{
-    __shared__ float red[FT];
-    const float tot = block_sum(sumsq_partial(grad, P, NORM_BLOCKS, FT), red);
-    if (threadIdx.x == 0) normp[(size_t)blockIdx.x * RP] = tot;
-}
-
-__global__ __launch_bounds__(FT) void dagger_conv_final_kernel(const float *rowp, int nblk, const float *normp, float inv_n, float max_norm,
-                                                               float beta1, float beta2, float lr, rover_dagger_state *st)
-{
-    __shared__ float red[FT];
-    float tot[1], sq[1];
-    reduce_rows(rowp, nblk, 1, tot, red);
-    reduce_rows(normp, NORM_BLOCKS, 1, sq, red);
-    if (threadIdx.x == 0) {
-        const float norm = sqrtf(sq[0]);
-        st->loss = (tot[0] * inv_n) * 0.5f;
-        st->grad_norm = norm;
-        st->clip_coef = max_norm > 0.0f ? grad_clip_coef(norm, max_norm) : 1.0f;
-        st->steps += 1;
-        adam_scalars(st->steps, beta1, beta2, lr, &st->step_size, &st->bc2_sqrt);
-    }
-}
-
-__global__ __launch_bounds__(FT) void dagger_conv_adam_kernel(float *params, float *grad, float *m, float *v, const rover_dagger_state *st,
-                                                              int P, int head, float beta1, float beta2, float eps, float *rep, int n_copies)
-{
-    const int e = blockIdx.x * FT + threadIdx.x;
-    if (e >= P) return;
-    const float p = adam_element_clipped(params, grad, m, v, e, &st->clip_coef, &st->step_size, &st->bc2_sqrt, beta1, beta2, eps);
-    if (e < head) refresh_replicas(rep, n_copies, (size_t)head, (size_t)e, p);
-}
-
-// ---- host side
-size_t head_floats() { return (net_floats(false) + 63) & ~(size_t)63; }          // rover_dagger_param_floats
+// ---- host side: the vector is [head | stem], head_floats() + STEM_PAD floats
 size_t param_floats() { return head_floats() + STEM_PAD; }
 
-// workspace: ro_s, ro_n, ident (int64 per row), the loss's block partials, the norm's chunk partials, the gathered rows and dRow
-// (965 floats per row each), one network region, the weight-gradient chunk partials, the stem's chunk partials
+// workspace: dagger_tail.hpp's, with ident (int64 per row) behind ro_n, the gathered rows and dRow (965 floats per row each) in
+// front of the network region, and the stem's chunk partials at the end
 size_t ws_floats(int rows)
 {
     const size_t R = (size_t)rows;
-    return 6 * al4(R) + rowp_floats(rows) + al4((size_t)RP * NORM_BLOCKS) + 2 * al4((size_t)OBS * R) + 2 * (size_t)ROW_F * R +
-           (size_t)cdiv(rows, CH) * net_floats(false) + (size_t)cdiv(rows, RC) * STEM_PAD;
+    return ws_shared_floats(rows) + 2 * al4(R) + 2 * al4((size_t)OBS * R) + (size_t)cdiv(rows, RC) * STEM_PAD;
 }
-struct Ws {
-    int64_t *ro_s, *ro_n, *ident;
-    float *a, *r, *nt;                 // the gather's transition outputs: not asked for here
-    float *rowp, *normp, *rows, *drow, *part, *spart;
-    Region reg;
+struct ConvWs : Ws {
+    int64_t *ident;
+    float *rows, *drow, *spart;
 };
-Ws ws_at(void *ws, int rows)
+ConvWs ws_at(void *ws, int rows)
 {
-    Ws w = {};
+    ConvWs w = {};
     const size_t R = (size_t)rows;
-    float *f = static_cast<float *>(ws);
-    w.ro_s = reinterpret_cast<int64_t *>(f); f += 2 * al4(R);
-    w.ro_n = reinterpret_cast<int64_t *>(f); f += 2 * al4(R);
-    w.ident = reinterpret_cast<int64_t *>(f); f += 2 * al4(R);
-    w.rowp = f; f += rowp_floats(rows);
-    w.normp = f; f += al4((size_t)RP * NORM_BLOCKS);
-    w.rows = f; f += al4((size_t)OBS * R);
-    w.drow = f; f += al4((size_t)OBS * R);
-    for (int s = 0; s < 2; ++s)
-        for (int l = 0; l < NL; ++l) {
-            (s ? w.reg.scr : w.reg.cache)[l] = f;
-            f += (size_t)MW[l] * R;
-        }
-    w.part = f; f += (size_t)cdiv(rows, CH) * net_floats(false);
-    w.spart = f;
+    float *ident;
+    w.spart = ws_carve(w, ws, rows, 2 * al4(R), &ident, 2 * al4((size_t)OBS * R), &w.rows);
+    w.ident = reinterpret_cast<int64_t *>(ident);
+    w.drow = w.rows + al4((size_t)OBS * R);
     return w;
 }
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
 }  // namespace
 
@@ -449,21 +339,8 @@ int rover_dagger_conv_rows(const rover_dagger_hparams *h, const float *stem, con
                               overlap(teacher_rows_out, rb, ring_slot_out, rb) || overlap(teacher_rows_out, rb, image_slot_out, ib) ||
                               overlap(teacher_rows_out, rb, stem, STEM_F * sizeof(float)))))
         return rover_internal_fail(ROVER_ERR_INVALID, "rover_dagger_conv_rows: the outputs must not alias the inputs or each other");
-    const int given = (rew != nullptr) + (terminated != nullptr) + (rew_out != nullptr) + (term_out != nullptr);
-    if (given != 0 && given != 4)
-        return rover_internal_fail(ROVER_ERR_INVALID, "rover_dagger_conv_rows: rew, terminated, rew_out, term_out: all or none NULL");
-    if (idx_out) {
-        if (batch < 1) return rover_internal_fail(ROVER_ERR_INVALID, "rover_dagger_conv_rows: batch must be >= 1");
-        if (mem_rows < 1 || mem_rows > ((int64_t)1 << 32))
-            return rover_internal_fail(ROVER_ERR_INVALID, "rover_dagger_conv_rows: mem_rows must lie in [1, 2^32]");
-    }
-    ConvRec R = {};
-    R.rew = rew; R.terminated = terminated; R.rew_out = rew_out; R.term_out = term_out;
-    R.ring_pos_entry = ring_pos_entry; R.ring_pos_value = ring_pos_value;
-    R.idx_out = idx_out; R.batch = idx_out ? batch : 0; R.mem_rows = idx_out ? (uint64_t)mem_rows : 1u;
-    R.seed_lo = h->seed_lo; R.seed_hi = h->seed_hi;
-    R.ctr_lo = (uint32_t)(counter & 0xFFFFFFFFu);
-    R.ctr_hi = (uint32_t)(counter >> 32);
+    if (int rc = rec_check("rover_dagger_conv_rows", rew, terminated, rew_out, term_out, idx_out, batch, mem_rows)) return rc;
+    const RecFields R = rec_fill(h, counter, rew, terminated, rew_out, term_out, ring_pos_entry, ring_pos_value, idx_out, batch, mem_rows);
     hipLaunchKernelGGL(rover_dagger_conv_rows_kernel, dim3((unsigned)n), dim3(ST), 0, static_cast<hipStream_t>(stream), stem, depth,
                        env_raw, ring_slot_out, image_slot_out, teacher_rows_out, (int)n, h->depth_clip, h->depth_scale, R);
     return launched("rover_dagger_conv_rows_kernel launch: %s");
@@ -476,30 +353,16 @@ int rover_dagger_conv_update(const rover_policy_desc *student, const rover_dagge
                              void *state, float *replicas, int32_t n_copies, float *dz_out, float *rows_out, float *drow_out,
                              void *stream)
 {
-    if (!student) return rover_internal_fail(ROVER_ERR_INVALID, "descriptor is NULL");
-    if (!is_net(student, false, ROVER_ACT_TANH, true))
-        return rover_internal_fail(ROVER_ERR_UNSUPPORTED, "the fused DAgger update runs the reference policy (rover_policy_default_desc(2, 1), "
-                                                          "packed by rover_policy_pack) only");
-    if (img_h != IH || img_w != IW) return rover_internal_fail(ROVER_ERR_UNSUPPORTED, "the stem reads 90 x 160 images only");
-    if (!h || !params || !grad || !adam_m || !adam_v || !obs_ring || !image_ring || !ring_pos || !labels || !idx || !ws || !state)
-        return rover_internal_fail(ROVER_ERR_INVALID, "NULL argument");
-    if (n < 1) return rover_internal_fail(ROVER_ERR_INVALID, "n must be >= 1");
-    if (slots < 2 || num_envs < 1) return rover_internal_fail(ROVER_ERR_INVALID, "the ring needs >= 2 slots and >= 1 env");
-    if (image_slots < slots) return rover_internal_fail(ROVER_ERR_INVALID, "the image ring must have the observation ring's slots or more");
-    if (valid_rows < 1 || valid_rows > (int64_t)(slots - 1) * num_envs)
-        return rover_internal_fail(ROVER_ERR_INVALID, "valid_rows must be in [1, (slots - 1) * num_envs]");
-    if (ws_bytes < rover_dagger_conv_workspace_bytes(n)) return rover_internal_fail(ROVER_ERR_INVALID, "DAgger workspace too small");
-    if (misaligned(ws) || misaligned(params) || misaligned(grad) || misaligned(adam_m) || misaligned(adam_v) || misaligned(image_ring))
-        return rover_internal_fail(ROVER_ERR_INVALID, "workspace, parameter vectors and image ring must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(state) & 7) return rover_internal_fail(ROVER_ERR_INVALID, "state must be 8-byte aligned");
-    if (replicas && n_copies < 1) return rover_internal_fail(ROVER_ERR_INVALID, "n_copies must be >= 1");
-    if (!(h->grad_norm_clip >= 0.0f)) return rover_internal_fail(ROVER_ERR_INVALID, "grad_norm_clip must be >= 0");
+    const UpdateImage im = {img_h == IH && img_w == IW, image_ring, image_slots};
+    if (int rc = update_check(student, h, params, grad, adam_m, adam_v, obs_ring, slots, num_envs, ring_pos, labels, idx, n, valid_rows,
+                              ws, ws_bytes, rover_dagger_conv_workspace_bytes(n), state, replicas, n_copies, &im))
+        return rc;
     int dev;
     if (int rc = device_of(params, &dev)) return rc;
     DeviceGuard guard(dev);
     hipStream_t s = static_cast<hipStream_t>(stream);
     rover_dagger_state *st = static_cast<rover_dagger_state *>(state);
-    Ws w = ws_at(ws, n);
+    ConvWs w = ws_at(ws, n);
     float *rows = rows_out ? rows_out : w.rows, *drow = drow_out ? drow_out : w.drow;
     const int PH = (int)net_floats(false), P = (int)param_floats();
     const size_t so = head_floats();
@@ -511,12 +374,7 @@ int rover_dagger_conv_update(const rover_policy_desc *student, const rover_dagge
     if (int rc = launched("dagger_conv_forward_kernel launch: %s")) return rc;
     FwdJob job = {pi, w.ident, nullptr, 0, &w.reg};
     if (int rc = forward<State>(&job, 1, rows, n, s)) return rc;
-    const float inv_n = 1.0f / (float)n;
-    Head H = {};
-    H.z = w.reg.cache[NL - 1]; H.labels = labels; H.idx = idx; H.valid = valid_rows; H.inv_n = inv_n;
-    H.dz = w.reg.scr[NL - 1]; H.dz_out = dz_out; H.rows = n; H.rowp = w.rowp;
-    hipLaunchKernelGGL(dagger_conv_head_kernel, dim3(cdiv(n, FT)), dim3(FT), 0, s, H);
-    if (int rc = launched("dagger_conv_head_kernel launch: %s")) return rc;
+    if (int rc = dagger_head(w, labels, idx, valid_rows, n, dz_out, s)) return rc;
     Region *regs[1] = {&w.reg};
     for (int l = NL - 1; l >= 1; --l)
         if (int rc = back_layer<State>(&pi, regs, 1, l, n, s)) return rc;
@@ -542,13 +400,7 @@ int rover_dagger_conv_update(const rover_policy_desc *student, const rover_dagge
                        grad + so);
     if (int rc = launched("offpolicy_combine_kernel (stem) launch: %s")) return rc;
     if (int rc = wgrad<State>(&pi, regs, w.ident, 1, rows, n, w.part, grad, s)) return rc;
-    hipLaunchKernelGGL(dagger_conv_norm_kernel, dim3(NORM_BLOCKS), dim3(FT), 0, s, (const float *)grad, P, w.normp);
-    hipLaunchKernelGGL(dagger_conv_final_kernel, dim3(1), dim3(FT), 0, s, (const float *)w.rowp, cdiv(n, FT), (const float *)w.normp, inv_n,
-                       h->grad_norm_clip, h->beta1, h->beta2, h->lr, st);
-    if (int rc = launched("dagger_conv final launch: %s")) return rc;
-    hipLaunchKernelGGL(dagger_conv_adam_kernel, dim3(cdiv(P, FT)), dim3(FT), 0, s, params, grad, adam_m, adam_v,
-                       (const rover_dagger_state *)st, P, PH, h->beta1, h->beta2, h->eps, replicas, (int)n_copies);
-    return launched("dagger_conv_adam_kernel launch: %s");
+    return dagger_tail(h, params, grad, adam_m, adam_v, P, PH, w, n, st, replicas, n_copies, s);
 }
 
 }  // extern "C"

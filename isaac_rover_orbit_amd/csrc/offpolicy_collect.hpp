@@ -1,6 +1,7 @@
 // offpolicy_collect.hpp -- what the off-policy transition collectors share (td3_collect_kernels.hip, td3_explore_kernels.hip,
 // sac_collect_kernels.hip): the record kernel, the batch's index stream, the standard normal pair of one Philox block, and the host
-// side of the act and record entry points (argument checks, grid sizing, launch).
+// side of the act and record entry points (argument checks, grid sizing, launch).  The index stream's tag, the record's
+// members (RecFields) and collect_fail are collect_record.hpp's, which the DAgger collectors include too.
 //
 //   offpolicy_collect_record_kernel  the env's raw rows sanitised into a ring slot, reward / terminated / ring_pos of the transition,
 //                                    the batch's row indices and, for a launch struct with DRAWS, four standard normals per batch
@@ -21,12 +22,12 @@
 
 #include "../../include/rover_hip.h"
 #include "../../include/rover_td3_explore.h"
+#include "collect_record.hpp"
 #include "rover_internal.hpp"
 #include "td3_actor_tile.hpp"
 
 namespace {
 
-constexpr uint32_t INDEX_TAG = 0x54335300u;   // "T3S\0": word 3 of the Philox counter of the batch's row indices
 constexpr int REC_THREADS = 256, REC_PER = 4; // record kernel: pieces (16 bytes, or one float on the scalar path) per thread
 constexpr int FLAT_THREADS = 256;             // the random and draw kernels: one lane per value or pair
 
@@ -95,14 +96,6 @@ __global__ __launch_bounds__(REC_THREADS) void offpolicy_collect_record_kernel(c
             }
         }
     }
-}
-
-// rover_last_error() = "<fn><text><detail>": the three parts go through fixed formats, none of them is one
-inline int collect_fail(int code, const char *fn, const char *text, const char *detail = "")
-{
-    char msg[384];
-    snprintf(msg, sizeof(msg), "%s%s%s", fn, text, detail);
-    return rover_internal_fail(code, "%s", msg);
 }
 
 // The record entry points: argument checks, the vector / scalar choice, the grid, the launch struct and the launch.  `eps_out` is

@@ -54,18 +54,8 @@ __global__ __launch_bounds__(TDC_THREADS) void rover_td3_collect_act_kernel(rove
 }
 
 // the record kernel's launch struct (offpolicy_collect.hpp): no draws besides the indices
-struct RecLaunch {
+struct RecLaunch : RecFields {
     static constexpr bool DRAWS = false;
-    const float *rew;
-    const uint8_t *terminated;
-    float *rew_out;
-    uint8_t *term_out;
-    int32_t *ring_pos_entry;
-    int32_t ring_pos_value;
-    int64_t *idx_out;
-    int batch;
-    uint64_t mem_rows;
-    uint32_t seed_lo, seed_hi, ctr_lo, ctr_hi;
 };
 
 }  // namespace

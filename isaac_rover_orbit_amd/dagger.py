@@ -72,14 +72,20 @@ def sanitise(rows: torch.Tensor) -> torch.Tensor:
     return torch.nan_to_num(rows, nan=0.0, posinf=FLT_MAX, neginf=0.0)
 
 
-def student_rows(depth: torch.Tensor, env_rows: torch.Tensor, depth_clip: float = HPARAMS["depth_clip"],
-                 depth_scale: float = HPARAMS["depth_scale"]) -> torch.Tensor:
-    """The student rows (n, 965) in the dtype of ``env_rows``: the specification of ``rover_dagger_rows``.  One product per pixel."""
-    d = image_buffer(depth).to(env_rows.dtype)
+def depth_pixels(d: torch.Tensor, depth_clip: float, depth_scale: float) -> torch.Tensor:
+    """The pixel rule, in the dtype of ``d``: ``depth_scale * min(d, depth_clip)``, where a NaN, +-inf or negative pixel counts as
+    ``depth_clip``.  One product per pixel."""
     clip = torch.tensor(depth_clip, dtype=d.dtype, device=d.device)
     scale = torch.tensor(depth_scale, dtype=d.dtype, device=d.device)
     d = torch.where(torch.isnan(d) | torch.isinf(d) | (d < 0), clip, d)
-    return torch.cat([sanitise(env_rows[:, :PROP]), scale * torch.minimum(d, clip)], dim=1)
+    return scale * torch.minimum(d, clip)
+
+
+def student_rows(depth: torch.Tensor, env_rows: torch.Tensor, depth_clip: float = HPARAMS["depth_clip"],
+                 depth_scale: float = HPARAMS["depth_scale"]) -> torch.Tensor:
+    """The student rows (n, 965) in the dtype of ``env_rows``: the specification of ``rover_dagger_rows``."""
+    x = depth_pixels(image_buffer(depth).to(env_rows.dtype), depth_clip, depth_scale)
+    return torch.cat([sanitise(env_rows[:, :PROP]), x], dim=1)
 
 
 def mix_uniforms(seed: int, env_ids, counter: int) -> np.ndarray:
@@ -159,8 +165,10 @@ class _DaggerCollectorBase(_CollectorBase):
         if not (0 < self.depth_clip < float("inf")):
             raise ValueError("depth_clip must be positive and finite")
 
+    _image_buffer = staticmethod(image_buffer)                    # the camera's: dagger_conv's collectors set their own
+
     def _image(self, depth) -> torch.Tensor:
-        d = image_buffer(depth)
+        d = self._image_buffer(depth)
         if d.shape[0] != self.n or d.dtype != torch.float32 or d.device != self.memory.obs.device:
             raise ValueError(f"depth must hold {self.n} float32 images on {self.memory.obs.device}")
         return d
@@ -275,12 +283,16 @@ class FusedDAgger(_fused.FusedOffPolicy):
         super().__init__(default_hparams, hparams, device, n_copies)
         self.desc_a, pa = pack(student_sd, "tanh")
         self.desc_c = None
-        self.P = int(self._lib.rover_dagger_param_floats(C.byref(self.desc_a)))
+        self.P = int(getattr(self._lib, self._PARAM_FLOATS)(C.byref(self.desc_a)))
         if self.P == 0:
-            raise _lib.RoverHipError(f"FusedDAgger runs {self._RUNS}")
+            raise _lib.RoverHipError(f"{type(self).__name__} runs {self._RUNS}")
         self.n_a, self.n_c = pa.size, 0
-        self._alloc(np.concatenate([pa, np.zeros(self.P - pa.size, np.float32)]))
+        self._alloc(self._flat(pa))
         self.state = torch.zeros(C.sizeof(_lib.DaggerState) // 4, dtype=torch.int32, device=self.device)
+
+    def _flat(self, pa: np.ndarray) -> np.ndarray:
+        """The initial vector of ``P`` floats: the packed student, then zeros."""
+        return np.concatenate([pa, np.zeros(self.P - pa.size, np.float32)])
 
     @staticmethod
     def _checkpoint_args(ck):

@@ -25,7 +25,6 @@ from __future__ import annotations
 import ctypes as C
 from typing import Mapping
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -33,11 +32,9 @@ import torch.nn.functional as F
 from . import _fused, _lib
 from ._fused import f32_cuda, holds, launch, ptr
 from .cfg import CameraCfg
-from .dagger import (HPARAMS, LOG_STD_KEY, DAggerCollector, FusedDAgger, _DaggerCollectorBase, _collector_hparams, _hparams, default_hparams,
-                     imitation_dz, imitation_loss, mix_uniforms, sanitise)
-from .ppo import pack
-from .td3 import ACT_DIM, OBS_DIM, ReplayMemory
-from .td3_collect import sample_indices
+from .dagger import (HPARAMS, LOG_STD_KEY, DAggerCollector, FusedDAgger, TorchDAggerCollector, _DaggerCollectorBase, _collector_hparams,
+                     _hparams, depth_pixels, imitation_dz, imitation_loss, mix_uniforms, sanitise)  # noqa: F401 (mix_uniforms: re-export)
+from .td3 import OBS_DIM, ReplayMemory
 
 IMG_H, IMG_W, PIXELS = 90, 160, 14400
 SIDE, FEATURES, PROP = 31, 961, 4
@@ -67,11 +64,7 @@ def image_buffer(depth: torch.Tensor) -> torch.Tensor:
 def preprocess(depth: torch.Tensor, depth_clip: float = HPARAMS["depth_clip"], depth_scale: float = HPARAMS["depth_scale"],
                dtype=torch.float32) -> torch.Tensor:
     """x (n, 90, 160) in ``dtype``: ``dagger.student_rows``' pixel rule.  One product per pixel."""
-    d = image_buffer(depth).to(dtype)
-    clip = torch.tensor(depth_clip, dtype=d.dtype, device=d.device)
-    scale = torch.tensor(depth_scale, dtype=d.dtype, device=d.device)
-    d = torch.where(torch.isnan(d) | torch.isinf(d) | (d < 0), clip, d)
-    return scale * torch.minimum(d, clip)
+    return depth_pixels(image_buffer(depth).to(dtype), depth_clip, depth_scale)
 
 
 class ConvStem(nn.Module):
@@ -225,11 +218,7 @@ class TorchConvDAgger:
 
 
 class _ConvCollectorBase(_DaggerCollectorBase):
-    def _image(self, depth) -> torch.Tensor:
-        d = image_buffer(depth)
-        if d.shape[0] != self.n or d.dtype != torch.float32 or d.device != self.memory.obs.device:
-            raise ValueError(f"depth must hold {self.n} float32 images on {self.memory.obs.device}")
-        return d
+    _image_buffer = staticmethod(image_buffer)
 
     def _ring(self, images: ImageRing) -> ImageRing:
         if not images.fits(self.memory):
@@ -237,20 +226,15 @@ class _ConvCollectorBase(_DaggerCollectorBase):
         return images
 
 
-class TorchConvDAggerCollector(_ConvCollectorBase):
-    """The specification, in torch / numpy: ``dagger.TorchDAggerCollector`` with the stem in its rows.  ``teacher`` / ``student``:
-    callables (n, 965) -> (n, 2) returning the tanh mean; ``stem``: a callable x (n, 90, 160) -> (n, 961)."""
+class TorchConvDAggerCollector(TorchDAggerCollector, _ConvCollectorBase):
+    """The specification, in torch / numpy: ``dagger.TorchDAggerCollector`` (its ``draws``, ``begin``, ``act`` and ``record``) with the
+    stem in its rows.  ``teacher`` / ``student``: callables (n, 965) -> (n, 2) returning the tanh mean; ``stem``: a callable
+    x (n, 90, 160) -> (n, 961)."""
 
     def __init__(self, teacher, student, stem, memory: ReplayMemory, images: ImageRing, seed: int = 42, env_id_offset: int = 0,
                  depth_clip: float = HPARAMS["depth_clip"], depth_scale: float = HPARAMS["depth_scale"]):
-        super().__init__(memory, seed, env_id_offset, depth_clip, depth_scale)
-        self.teacher, self.student, self.stem, self.images = teacher, student, stem, self._ring(images)
-        self.teacher_rows = None
-        self.last: dict = {}
-
-    def draws(self, counter: int | None = None) -> np.ndarray:
-        ids = self.env_id_offset + np.arange(self.n, dtype=np.int64)
-        return mix_uniforms(self.seed, ids, self.counter if counter is None else counter)
+        super().__init__(teacher, student, memory, seed, env_id_offset, depth_clip, depth_scale)
+        self.stem, self.images = stem, self._ring(images)
 
     def _rows(self, raw, depth, slot: int) -> None:
         x = preprocess(self._image(depth), self.depth_clip, self.depth_scale)
@@ -259,46 +243,10 @@ class TorchConvDAggerCollector(_ConvCollectorBase):
         self.teacher_rows = sanitise(raw)
 
     @torch.no_grad()
-    def begin(self, raw_obs, depth) -> None:
-        m = self.memory
-        self._rows(self._raw(raw_obs), depth, m.cursor)
-        m._last_next, m._last_version = None, -1
-
-    @torch.no_grad()
     def resume(self, raw_obs) -> None:
         """What a resumed run calls in place of ``begin``: only the teacher's rows are refilled.  Both rings are the checkpoint's: the
         cursor slot keeps the features its last ``record`` wrote, one update older than the stem a ``begin`` would apply now."""
         self.teacher_rows = sanitise(self._raw(raw_obs))
-
-    @torch.no_grad()
-    def act(self, beta: float) -> torch.Tensor:
-        m = self.memory
-        beta = self._beta(beta)
-        label = self.teacher(self.teacher_rows)
-        a_s = self.student(m.obs[m.cursor])
-        source = torch.from_numpy(self.draws() < beta).to(label.device)
-        a = torch.where(source.unsqueeze(1), label, a_s)
-        m.actions[m.memory_index] = label
-        self.last = {"label": label, "student": a_s, "source": source}
-        self.counter += 1
-        return a
-
-    @torch.no_grad()
-    def record(self, raw_obs, depth, rew, terminated, batch_size: int | None = None):
-        m = self.memory
-        raw = self._raw(raw_obs)
-        self._transition(rew, terminated)
-        k, w = m.memory_index, m.cursor
-        self._rows(raw, depth, (w + 1) % m.slots)
-        m.rewards[k] = rew.reshape(self.n)
-        m.terminated[k] = terminated.reshape(self.n) != 0
-        m.ring_pos[k] = w
-        self._advance()
-        idx = None
-        if batch_size is not None:
-            idx = torch.from_numpy(sample_indices(self.seed, self.counter, batch_size, len(m))).to(m.device)
-        self.counter += 1
-        return idx
 
 
 # ---------------------------------------------------------------------------------------------------------------- fused
@@ -337,27 +285,23 @@ class FusedConvDAgger(FusedDAgger):
     _RUNS = "the reference policy network (Net(2, True)) behind the stem only (rover_dagger_conv.h)"
 
     def __init__(self, student_sd: Mapping[str, torch.Tensor], stem=None, device="cuda", n_copies: int = 4, seed: int = 42, **hparams):
-        hparams = {self._CONVERT.get(k, k): v for k, v in hparams.items()}
-        _fused.FusedOffPolicy.__init__(self, default_hparams, hparams, device, n_copies)
-        self.desc_a, pa = pack(student_sd, "tanh")
-        self.desc_c = None
-        self.P = int(self._lib.rover_dagger_conv_param_floats(C.byref(self.desc_a)))
-        if self.P == 0:
-            raise _lib.RoverHipError(f"FusedConvDAgger runs {self._RUNS}")
-        self.stem_offset = int(self._lib.rover_dagger_conv_stem_offset(C.byref(self.desc_a)))
-        self.chunk_rows = int(self._lib.rover_dagger_conv_chunk_rows())
         if stem is None:
             stem = ConvStem.seeded(seed)
         elif not isinstance(stem, nn.Module):
             m = ConvStem()
             m.load_state_dict(stem)
             stem = m
-        flat = np.zeros(self.P, np.float32)
-        flat[:pa.size] = pa
-        flat[self.stem_offset:self.stem_offset + STEM_FLOATS] = stem.packed().float().cpu().numpy()
-        self.n_a, self.n_c = pa.size, 0
-        self._alloc(flat)
-        self.state = torch.zeros(C.sizeof(_lib.DaggerState) // 4, dtype=torch.int32, device=self.device)
+        self._stem0 = stem.packed().float().cpu().numpy()
+        super().__init__(student_sd, device, n_copies, **hparams)
+
+    def _flat(self, pa):
+        """``[head | stem]``: the base's vector with the initial stem at ``stem_offset``."""
+        self.stem_offset = int(self._lib.rover_dagger_conv_stem_offset(C.byref(self.desc_a)))
+        self.chunk_rows = int(self._lib.rover_dagger_conv_chunk_rows())
+        flat = super()._flat(pa)
+        flat[self.stem_offset:self.stem_offset + STEM_FLOATS] = self._stem0
+        del self._stem0                                            # from here on ``stem`` is the view of ``params``
+        return flat
 
     @staticmethod
     def _checkpoint_args(ck):

@@ -10,8 +10,8 @@ Per function one line: its base name, the instruction count and sha256[:12] of t
 descriptor's register / LDS / scratch values, and SAME or DIFFERENT (then with the second listing's figures).  Compared are
 the instruction lines (comments stripped, directives dropped, local label numbers and symbol names normalised) and
 .amdhsa_next_free_vgpr, .amdhsa_next_free_sgpr, .amdhsa_accum_offset, .amdhsa_group_segment_fixed_size and
-.amdhsa_private_segment_fixed_size.  Functions are paired by base name: the td3_ / sac_ / offpolicy_ / ppo_ / lift_ prefix (also
-as rover_td3_collect_ / rover_sac_collect_ / offpolicy_collect_) and template arguments are ignored, several functions of one base
+.amdhsa_private_segment_fixed_size.  Functions are paired by base name: the td3_ / sac_ / offpolicy_ / ppo_ / lift_ / dagger_ /
+dagger_conv_ prefix (also as rover_td3_collect_ / rover_sac_collect_ / offpolicy_collect_) and template arguments are ignored, several functions of one base
 name (a template's instantiations) pair in their order of appearance.
 A function only one listing has is reported and fails the comparison, unless --common is given (two different files that share
 some kernels: python tools/isa_same.py --common new/td3_kernels.s new/sac_kernels.s, or new/ppo_kernels.s new/lift_ppo_kernels.s).
@@ -41,7 +41,7 @@ def base_name(sym):
             i = j + n
         if ids:
             name = ids[-1]
-    return re.sub(r"^(rover_(td3|sac)_collect|offpolicy_collect|td3|sac|offpolicy|ppo|lift)_", "", name)
+    return re.sub(r"^(dagger_conv|dagger|rover_(td3|sac)_collect|offpolicy_collect|td3|sac|offpolicy|ppo|lift)_", "", name)
 
 
 def normalise(line):
