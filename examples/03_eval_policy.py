@@ -3,6 +3,12 @@
 146-155): the skrl checkpoint's policy is packed once and evaluated by the fused MFMA kernel between env steps.
 
     python examples/03_eval_policy.py --checkpoint <.../policies/best_agent.pt> --num_envs 1024 --steps 750
+
+``--scan_source elevation``: the actor reads its height scan out of a rolling elevation map built from the on-board depth camera
+(``RoverEnvCfg.elevation``) in place of the oracle ray cast, so the same checkpoint runs on what the camera can see -- forward
+only, through the sensor model of ``--depth_range`` / ``--depth_sigma`` / ``--depth_dropout``:
+
+    python examples/03_eval_policy.py --checkpoint best_agent.pt --scan_source elevation --depth_range 0.3 8 --depth_dropout 0.01 0.4
 """
 import argparse
 import os
@@ -17,19 +23,74 @@ from isaac_rover_orbit_amd.envs import RoverEnv  # noqa: E402
 from isaac_rover_orbit_amd.policy import RoverNet  # noqa: E402
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--checkpoint", required=True)
     ap.add_argument("--num_envs", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=750)
-    args = ap.parse_args()
-    terrain = T.make_procedural_terrain((2048, 2048), seed=1234)
-    terrain.make_spawns(2 * args.num_envs)
+    ap.add_argument("--scan_source", choices=("raycast", "elevation"), default="raycast",
+                    help="where the actor's height scan comes from: the oracle ray cast, or an elevation map built from the depth camera")
+    ap.add_argument("--depth_range", type=float, nargs=2, default=None, metavar=("MIN", "MAX"),
+                    help="the sensor's working range (m): depths outside it, misses included, carry no data")
+    ap.add_argument("--depth_sigma", type=float, nargs=3, default=None, metavar=("S0", "S1", "S2"),
+                    help="axial noise of standard deviation S0 + S1 z + S2 z^2 (m) at depth z")
+    ap.add_argument("--depth_dropout", type=float, nargs=2, default=None, metavar=("P", "P_EDGE"),
+                    help="probability that a pixel loses its data, off and on a depth edge")
+    ap.add_argument("--map_alpha", type=float, default=1.0, help="weight of the newest frame on a cell the map already knows")
+    return ap
+
+
+def make_cfg(args) -> RoverEnvCfg:
+    """The env cfg of the flags: with ``--scan_source elevation`` the camera, its sensor model (None without a --depth_* flag) and
+    the map; otherwise exactly the default."""
     cfg = RoverEnvCfg()
     cfg.scene.num_envs = args.num_envs
     cfg.terrain.kind = "custom"
-    env = RoverEnv(cfg, terrain=terrain)
+    if args.scan_source == "elevation":
+        from isaac_rover_orbit_amd.cfg import CameraCfg, DepthSensorCfg, ElevationMapCfg
+        cfg.camera = CameraCfg()
+        if any(v is not None for v in (args.depth_range, args.depth_sigma, args.depth_dropout)):
+            s = cfg.camera.sensor = DepthSensorCfg()
+            if args.depth_range is not None:
+                s.range_min, s.range_max = args.depth_range
+            if args.depth_sigma is not None:
+                s.sigma = tuple(args.depth_sigma)
+            if args.depth_dropout is not None:
+                s.p_drop, s.p_edge = args.depth_dropout
+        cfg.elevation = ElevationMapCfg(alpha=args.map_alpha)
+    return cfg
+
+
+def eval_on_map(env, actor, steps: int):
+    """The loop of ``main`` with the actor on ``policy_rows(obs, extras["elevation_scan"])``; also the mean known share."""
+    from isaac_rover_orbit_amd.elevation import policy_rows
+    obs, info = env.reset()
+    counts, episodes, known = torch.zeros(4), 0.0, 0.0
+    rows = torch.empty_like(obs["policy"])
+    for _ in range(steps):
+        torch.nan_to_num_(obs["policy"], neginf=0.0)
+        policy_rows(obs["policy"], info["elevation_scan"], out=rows)
+        obs, rew, terminated, truncated, info = env.step(actor.act(rows))
+        log = env.episode_log_vector.cpu()
+        known += float(info["elevation_count"].float().mean()) / (rows.shape[1] - 4)
+        if log[13] > 0:
+            episodes += float(log[13])
+            counts += log[7:11]
+    return episodes, counts, known / max(steps, 1)
+
+
+def main():
+    args = build_parser().parse_args()
+    terrain = T.make_procedural_terrain((2048, 2048), seed=1234)
+    terrain.make_spawns(2 * args.num_envs)
+    env = RoverEnv(make_cfg(args), terrain=terrain)
     actor = RoverNet.from_checkpoint(args.checkpoint, role="policy")
+    if args.scan_source == "elevation":
+        episodes, counts, known = eval_on_map(env, actor, args.steps)
+        print(f"episodes finished: {episodes:.0f}; terminations (time_out, success, far, collision): {counts.tolist()}; "
+              f"mean known share of the scan: {known:.3f}")
+        env.close()
+        return
     obs, _ = env.reset()
     counts = torch.zeros(4)                              # time_out, is_success, far_from_target, collision
     episodes = 0.0

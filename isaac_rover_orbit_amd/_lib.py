@@ -76,6 +76,7 @@ EXPORTS = [
     "rover_dagger_conv_chunk_rows", "rover_dagger_conv_workspace_bytes", "rover_dagger_conv_rows", "rover_dagger_conv_update",
     "rover_obs_post_segment_bytes", "rover_obs_post_apply",  # rover_obs_post.h
     "rover_depth_sensor_cfg_bytes", "rover_depth_sensor_apply",  # rover_depth_sensor.h
+    "rover_elevation_cfg_bytes", "rover_elevation_step", "rover_elevation_scan",  # rover_elevation.h
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -285,6 +286,16 @@ class DepthSensorCfg(C.Structure):
                 ("invalid_value", C.c_float)]
 
 
+ELEVATION_MIN_GRID, ELEVATION_MAX_GRID, ELEVATION_MAX_PIXELS, ELEVATION_MAX_RAYS = 8, 128, 16384, 4096
+
+
+class ElevationCfg(C.Structure):
+    """Mirror of ``struct rover_elevation_cfg`` (include/rover_elevation.h)."""
+    _fields_ = [("cell", C.c_float), ("inv_cell", C.c_float), ("grid", C.c_int32), ("range_min", C.c_float),
+                ("range_max", C.c_float), ("alpha", C.c_float), ("mount_pos", C.c_float * 3), ("height_offset", C.c_float),
+                ("unknown_value", C.c_float)]
+
+
 class RoverHipError(RuntimeError):
     pass
 
@@ -380,7 +391,8 @@ _MIRRORS = [("rover_config_bytes", RoverConfig), ("rover_lift_config_bytes", Lif
             ("rover_sac_collect_hparams_bytes", SacCollectHparams), ("rover_scaler_hparams_bytes", ScalerHparams),
             ("rover_trace_stream_bytes", TraceStream), ("rover_lift_viewer_config_bytes", LiftViewerConfig),
             ("rover_dagger_hparams_bytes", DaggerHparams), ("rover_dagger_state_bytes", DaggerState),
-            ("rover_obs_post_segment_bytes", ObsPostSegment), ("rover_depth_sensor_cfg_bytes", DepthSensorCfg)]
+            ("rover_obs_post_segment_bytes", ObsPostSegment), ("rover_depth_sensor_cfg_bytes", DepthSensorCfg),
+            ("rover_elevation_cfg_bytes", ElevationCfg)]
 
 
 def load():
@@ -644,6 +656,11 @@ def load():
     lib.rover_depth_sensor_cfg_bytes.restype = C.c_size_t
     lib.rover_depth_sensor_apply.argtypes = [C.POINTER(DepthSensorCfg), vp, vp, i32, i32, C.c_int64, i32, C.c_uint64, C.c_uint64,
                                              C.c_uint64, vp, vp]
+    lib.rover_elevation_cfg_bytes.restype = C.c_size_t
+    lib.rover_elevation_step.argtypes = [C.POINTER(ElevationCfg), vp, C.c_int64, i32, i32, vp, vp, vp, C.c_int64, C.c_int64, vp, vp,
+                                         vp, vp, vp, i32, vp, i32, vp, C.c_int64, vp, vp, i32, vp]
+    lib.rover_elevation_scan.argtypes = [C.POINTER(ElevationCfg), vp, vp, C.c_int64, C.c_int64, vp, vp, vp, i32, vp, i32, vp,
+                                         C.c_int64, vp, vp, i32, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:

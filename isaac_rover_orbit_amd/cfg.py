@@ -160,6 +160,54 @@ class DepthSensorCfg:
 
 
 @dataclass
+class ElevationMapCfg:
+    """A rolling, robot-centric elevation map built from the depth camera (include/rover_elevation.h, elevation.py): ``grid`` x
+    ``grid`` world-anchored cells of ``cell`` metres around the rover, fed by the pixels within ``[range_min, range_max]``, the
+    cell's height the frame's maximum, blended into a known cell with weight ``alpha``.  The policy's height scan is read out of
+    the map; a column over an unknown cell reads ``unknown_value``."""
+    cell: float = 0.1                                  # m
+    grid: int = 64                                     # cells per side: a power of two in [8, 128]
+    range_min: float = 0.1                             # m, > 0: the depth sensor's invalid_value = 0 falls out here
+    range_max: float = 5.0
+    alpha: float = 1.0                                 # 1 = the newest frame replaces a cell's height
+    unknown_value: float = 0.0
+
+    def check(self):
+        """ValueError for what the library refuses, on the values as the fp32 struct holds them."""
+        f32 = lambda x: C.c_float(float(x)).value      # noqa: E731
+        g = int(self.grid)
+        if g != self.grid or g < _lib.ELEVATION_MIN_GRID or g > _lib.ELEVATION_MAX_GRID or g & (g - 1):
+            raise ValueError(f"elevation grid must be a power of two in [{_lib.ELEVATION_MIN_GRID}, {_lib.ELEVATION_MAX_GRID}]")
+        cell = f32(self.cell)
+        inv_cell = f32(1.0 / float(self.cell)) if math.isfinite(cell) and cell > 0.0 else math.nan
+        if not (math.isfinite(inv_cell) and inv_cell > 0.0):
+            raise ValueError("elevation cell and 1 / cell must be finite and > 0")
+        lo, hi = f32(self.range_min), f32(self.range_max)
+        if not (math.isfinite(lo) and lo > 0.0 and hi >= lo):
+            raise ValueError("elevation range must satisfy 0 < range_min <= range_max (range_max may be inf)")
+        if not 0.0 < f32(self.alpha) <= 1.0:
+            raise ValueError("elevation alpha must be in (0, 1]")
+        if math.isnan(f32(self.unknown_value)):
+            raise ValueError("elevation unknown_value must not be a NaN")
+
+    def to_native(self, mount_pos, height_offset: float) -> "_lib.ElevationCfg":
+        """The library's struct: ``mount_pos`` is the camera's position on the Body link, ``height_offset`` the height scanner's;
+        inv_cell = float32(1 / cell), formed in double."""
+        self.check()
+        c = _lib.ElevationCfg()
+        c.cell, c.inv_cell, c.grid = float(self.cell), 1.0 / float(self.cell), int(self.grid)
+        c.range_min, c.range_max, c.alpha = float(self.range_min), float(self.range_max), float(self.alpha)
+        if len(tuple(mount_pos)) != 3 or not all(math.isfinite(C.c_float(float(v)).value) for v in mount_pos):
+            raise ValueError("elevation mount_pos must be three finite values")
+        for i in range(3):
+            c.mount_pos[i] = float(mount_pos[i])
+        c.height_offset, c.unknown_value = float(height_offset), float(self.unknown_value)
+        if math.isnan(c.height_offset):
+            raise ValueError("elevation height_offset must not be a NaN")
+        return c
+
+
+@dataclass
 class CameraCfg:
     """The rover's on-board depth camera (``RoverEnvCamera``, rover_camera_env.py:44-62): a pinhole on the Body link whose
     ``distance_to_camera`` image is a ray cast against the terrain's triangle mesh (include/rover_camera.h; RGB is not rendered)."""
@@ -373,6 +421,9 @@ class RoverEnvCfg:
     global_num_envs: int | None = None
     # the on-board depth camera (RoverEnvCamera): None = no camera, nothing rendered
     camera: CameraCfg | None = None
+    # a rolling elevation map fed by the camera (elevation.py): None = no map, nothing launched.  With one, extras["elevation_scan"]
+    # is the height scan read out of the map, beside extras["elevation_known"] and extras["elevation_count"]
+    elevation: ElevationMapCfg | None = None
     # the rgb_array viewer's camera (render_mode="rgb_array"): ORBIT's ViewerCfg defaults
     viewer: ViewerCfg = field(default_factory=ViewerCfg)
 
@@ -420,6 +471,15 @@ class RoverEnvCfg:
             raise ValueError("simple_heading=True is not supported (the reference cfg uses False, rover_env_cfg.py:195)")
         if self.camera is not None:
             self.camera.validate()
+        if self.elevation is not None:
+            if self.camera is None:
+                raise ValueError("cfg.elevation needs cfg.camera: the map is built from the depth image")
+            if int(self.camera.width) * int(self.camera.height) > _lib.ELEVATION_MAX_PIXELS:
+                raise ValueError(f"an elevation map needs camera height * width <= {_lib.ELEVATION_MAX_PIXELS}")
+            nx, ny = self.height_scanner.grid
+            if nx * ny > _lib.ELEVATION_MAX_RAYS:
+                raise ValueError(f"an elevation map needs at most {_lib.ELEVATION_MAX_RAYS} scan rays")
+            self.elevation.to_native(self.camera.position, self.height_scanner.height_offset)
         self.viewer.validate(self.scene.num_envs)
 
     def observation_post(self) -> dict:

@@ -1,0 +1,390 @@
+// elevation_kernels.hip -- the rolling elevation map from the depth camera (scroll, unproject, reduce, fuse, scan) as one launch
+// (gfx950 / CDNA4, wave64).
+//
+// See include/rover_elevation.h for the contract and the operation order.  Two kernels:
+//   elevation_step_kernel<G>  one workgroup of 512 threads per env, so the env index -- and with it the pose, the reset flag and
+//                             the old origin -- is uniform over the workgroup.  One G x G LDS array of 32-bit words serves three
+//                             times: cleared to 0 it takes the frame's keys (pass 1: depth in 16-byte loads where the image and
+//                             the ray table start on a 16-byte boundary, four pixels and three ray quads per thread and trip; one
+//                             LDS unsigned-max atomic per surviving point); pass 2 walks the slots once, reads the old global
+//                             value under the scroll rule, fuses, stores to global and puts the fused float back into the same
+//                             LDS word; the scan then looks its columns up in LDS.  A slot is read and written by the same thread
+//                             in pass 2, so the map is updated in place without a second copy.
+//   elevation_scan_kernel     step 8 alone, the map read from global memory.
+// Both run scan_rows(), so they agree on the bits.  The known count is a ballot / popcount per wave into one LDS int per wave,
+// summed by thread 0: no atomics on global memory, no float atomics.
+// LDS: 4 G^2 bytes of map + 8 wave counters (32 bytes): 65568 bytes at G = 128 (two workgroups per CU), 16416 at G = 64.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/rover_hip.h"
+#include "../../include/rover_elevation.h"
+#include "rover_internal.hpp"
+
+namespace {
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+constexpr int TT = 512;
+constexpr int WAVES = TT / 64;
+constexpr uint32_t QNAN = 0x7FC00000u;
+
+struct ElevArgs {
+    rover_elevation_cfg cfg;
+    const float *depth, *ray_b, *pos, *quat, *ray_x, *ray_y;
+    const uint8_t *reset_a, *reset_b;
+    float *map;                   // the scan kernel only reads it
+    int32_t *origin;              // likewise
+    float *scan_out;
+    uint8_t *known_out;
+    int32_t *count_out;
+    long long pitch, comp_stride, env_stride, scan_pitch;
+    int hw, nx, ny, log_g;
+};
+
+struct Pose {
+    float px, py, pz, qw, qx, qy, qz;
+    bool ok;
+};
+
+__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) < INFINITY; }      // false for a NaN
+
+__device__ __forceinline__ Pose load_pose(const ElevArgs &A, int e)
+{
+    const float *p = A.pos + (size_t)e * (size_t)A.env_stride, *q = A.quat + (size_t)e * (size_t)A.env_stride;
+    const size_t cs = (size_t)A.comp_stride;
+    Pose P;
+    P.px = p[0]; P.py = p[cs]; P.pz = p[2 * cs];
+    P.qw = q[0]; P.qx = q[cs]; P.qy = q[2 * cs]; P.qz = q[3 * cs];
+    P.ok = finite_f(P.px) && finite_f(P.py) && finite_f(P.pz) && finite_f(P.qw) && finite_f(P.qx) && finite_f(P.qy) &&
+           finite_f(P.qz);
+    return P;
+}
+
+// the global cell of a finite world coordinate
+__device__ __forceinline__ int cell_of(float v, float inv_cell)
+{
+    return (int)fminf(fmaxf(floorf(__fmul_rn(v, inv_cell)), -1073741824.0f), 1073741824.0f);
+}
+
+__device__ __forceinline__ uint32_t key_of(float v)
+{
+    const uint32_t b = __float_as_uint(v);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float value_of(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
+// one point of pass 1
+__device__ __forceinline__ void splat(uint32_t *keys, const ElevArgs &A, const Pose &P, const float (&R)[9], int lo_x, int lo_y,
+                                      int G, int log_g, float d, float rx, float ry, float rz)
+{
+    const rover_elevation_cfg &c = A.cfg;
+    if (!(finite_f(d) && d >= c.range_min && d <= c.range_max)) return;
+    const float bx = __fadd_rn(c.mount_pos[0], __fmul_rn(d, rx));
+    const float by = __fadd_rn(c.mount_pos[1], __fmul_rn(d, ry));
+    const float bz = __fadd_rn(c.mount_pos[2], __fmul_rn(d, rz));
+    const float wx = __fadd_rn(P.px, __fadd_rn(__fadd_rn(__fmul_rn(R[0], bx), __fmul_rn(R[1], by)), __fmul_rn(R[2], bz)));
+    const float wy = __fadd_rn(P.py, __fadd_rn(__fadd_rn(__fmul_rn(R[3], bx), __fmul_rn(R[4], by)), __fmul_rn(R[5], bz)));
+    const float wz = __fadd_rn(P.pz, __fadd_rn(__fadd_rn(__fmul_rn(R[6], bx), __fmul_rn(R[7], by)), __fmul_rn(R[8], bz)));
+    if (!(finite_f(wx) && finite_f(wy) && finite_f(wz))) return;
+    const int gx = cell_of(wx, c.inv_cell), gy = cell_of(wy, c.inv_cell);
+    if ((uint32_t)gx - (uint32_t)lo_x >= (uint32_t)G || (uint32_t)gy - (uint32_t)lo_y >= (uint32_t)G) return;
+    atomicMax(&keys[((gy & (G - 1)) << log_g) | (gx & (G - 1))], key_of(wz));      // slot < G * G: both terms are masked
+}
+
+// Step 8 for the env of this workgroup: `load(slot)` is the map's float at a slot < G * G, (cx, cy) the centre of its window.
+template <class Load>
+__device__ __forceinline__ void scan_rows(const ElevArgs &A, const Pose &P, int e, int G, int log_g, int cx, int cy, bool usable,
+                                          int *wave_known, Load load)
+{
+    const rover_elevation_cfg &c = A.cfg;
+    const int tid = threadIdx.x, cols = A.nx * A.ny;
+    float *row = A.scan_out + (size_t)e * (size_t)A.scan_pitch;
+    uint8_t *known_row = A.known_out ? A.known_out + (size_t)e * (size_t)cols : nullptr;
+    const int lo_x = cx - (G >> 1), lo_y = cy - (G >> 1);
+    float cyaw = 0.0f, syaw = 0.0f;
+    if (usable) {
+        const float a = __fsub_rn(1.0f, __fmul_rn(2.0f, __fadd_rn(__fmul_rn(P.qy, P.qy), __fmul_rn(P.qz, P.qz))));
+        const float b = __fmul_rn(2.0f, __fadd_rn(__fmul_rn(P.qw, P.qz), __fmul_rn(P.qx, P.qy)));
+        const float inv = 1.0f / sqrtf(__fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b)));
+        cyaw = __fmul_rn(a, inv);
+        syaw = __fmul_rn(b, inv);
+    }
+    int count = 0;                                                   // wave-uniform
+    for (int base = tid & ~63; base < cols; base += TT) {            // wave-uniform trip count
+        const int col = base + (tid & 63);
+        bool known = false;
+        if (col < cols) {
+            float out = c.unknown_value;
+            if (usable) {
+                const int i = col / A.nx, j = col - i * A.nx;
+                const float ox = A.ray_x[j], oy = A.ray_y[i];
+                const float x = __fadd_rn(P.px, __fsub_rn(__fmul_rn(cyaw, ox), __fmul_rn(syaw, oy)));
+                const float y = __fadd_rn(P.py, __fadd_rn(__fmul_rn(syaw, ox), __fmul_rn(cyaw, oy)));
+                if (finite_f(x) && finite_f(y)) {
+                    const int gx = cell_of(x, c.inv_cell), gy = cell_of(y, c.inv_cell);
+                    if ((uint32_t)gx - (uint32_t)lo_x < (uint32_t)G && (uint32_t)gy - (uint32_t)lo_y < (uint32_t)G) {
+                        const float h = load(((gy & (G - 1)) << log_g) | (gx & (G - 1)));
+                        if (h == h) {
+                            known = true;
+                            out = __fsub_rn(__fsub_rn(P.pz, h), c.height_offset);
+                        }
+                    }
+                }
+            }
+            row[col] = out;
+            if (known_row) known_row[col] = known ? 1 : 0;
+        }
+        count += __popcll(__ballot(known));
+    }
+    if (A.count_out) {                                               // kernel argument: uniform over the workgroup
+        if ((tid & 63) == 0) wave_known[tid >> 6] = count;
+        __syncthreads();
+        if (tid == 0) {
+            int total = 0;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) total += wave_known[w];
+            A.count_out[e] = total;
+        }
+    }
+}
+
+template <int G>
+__global__ __launch_bounds__(TT) void elevation_step_kernel(ElevArgs A)
+{
+    constexpr int LOG_G = G == 8 ? 3 : G == 16 ? 4 : G == 32 ? 5 : G == 64 ? 6 : 7;
+    constexpr int CELLS = G * G;
+    __shared__ __attribute__((aligned(16))) uint32_t keys[CELLS];
+    __shared__ int wave_known[WAVES];
+    const rover_elevation_cfg &c = A.cfg;
+    const int tid = threadIdx.x, e = blockIdx.x;
+    const Pose P = load_pose(A, e);
+    const bool reset = (A.reset_a && A.reset_a[e]) || (A.reset_b && A.reset_b[e]);
+    float *map = A.map + (size_t)e * CELLS;
+
+    if (!P.ok) {                                                     // uniform over the workgroup
+        if (reset)
+            for (int s = tid; s < CELLS; s += TT) map[s] = __uint_as_float(QNAN);
+        if (A.scan_out) scan_rows(A, P, e, G, LOG_G, 0, 0, false, wave_known, [](int) { return 0.0f; });
+        return;
+    }
+    const int old_x = A.origin[2 * e], old_y = A.origin[2 * e + 1];
+    const int cx = cell_of(P.px, c.inv_cell), cy = cell_of(P.py, c.inv_cell);
+    const int lo_x = cx - G / 2, lo_y = cy - G / 2;
+
+    for (int s = tid; s < CELLS; s += TT) keys[s] = 0u;
+    __syncthreads();
+
+    // ---- pass 1: this frame's points, reduced per cell with the LDS unsigned max
+    if (A.depth) {
+        const float xx = __fmul_rn(P.qx, P.qx), yy = __fmul_rn(P.qy, P.qy), zz = __fmul_rn(P.qz, P.qz);
+        const float xy = __fmul_rn(P.qx, P.qy), xz = __fmul_rn(P.qx, P.qz), yz = __fmul_rn(P.qy, P.qz);
+        const float wx = __fmul_rn(P.qw, P.qx), wy = __fmul_rn(P.qw, P.qy), wz = __fmul_rn(P.qw, P.qz);
+        const float R[9] = {__fsub_rn(1.0f, __fmul_rn(2.0f, __fadd_rn(yy, zz))), __fmul_rn(2.0f, __fsub_rn(xy, wz)),
+                            __fmul_rn(2.0f, __fadd_rn(xz, wy)),
+                            __fmul_rn(2.0f, __fadd_rn(xy, wz)), __fsub_rn(1.0f, __fmul_rn(2.0f, __fadd_rn(xx, zz))),
+                            __fmul_rn(2.0f, __fsub_rn(yz, wx)),
+                            __fmul_rn(2.0f, __fsub_rn(xz, wy)), __fmul_rn(2.0f, __fadd_rn(yz, wx)),
+                            __fsub_rn(1.0f, __fmul_rn(2.0f, __fadd_rn(xx, yy)))};
+        const float *img = A.depth + (size_t)e * (size_t)A.pitch;
+        const int hw = A.hw;
+        int done = 0;                                                // pixels the 16-byte path has taken
+        if (((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(A.ray_b)) & 15) == 0) {
+            const int nq = hw >> 2;
+            for (int q = tid; q < nq; q += TT) {
+                const v4f d = *reinterpret_cast<const v4f *>(img + 4 * q);
+                const v4f *rq = reinterpret_cast<const v4f *>(A.ray_b + 12 * (size_t)q);
+                const v4f r0 = rq[0], r1 = rq[1], r2 = rq[2];
+                splat(keys, A, P, R, lo_x, lo_y, G, LOG_G, d.x, r0.x, r0.y, r0.z);
+                splat(keys, A, P, R, lo_x, lo_y, G, LOG_G, d.y, r0.w, r1.x, r1.y);
+                splat(keys, A, P, R, lo_x, lo_y, G, LOG_G, d.z, r1.z, r1.w, r2.x);
+                splat(keys, A, P, R, lo_x, lo_y, G, LOG_G, d.w, r2.y, r2.z, r2.w);
+            }
+            done = 4 * nq;
+        }
+        for (int k = done + tid; k < hw; k += TT) {
+            const float *r = A.ray_b + 3 * (size_t)k;
+            splat(keys, A, P, R, lo_x, lo_y, G, LOG_G, img[k], r[0], r[1], r[2]);
+        }
+    }
+    __syncthreads();
+
+    // ---- pass 2: scroll, fuse, store; the fused float goes back into the slot's LDS word
+    const int olo_x = old_x - G / 2, olo_y = old_y - G / 2;
+    for (int s = tid; s < CELLS; s += TT) {
+        const int sx = s & (G - 1), sy = s >> LOG_G;
+        // the global cell the slot denotes in the new and in the old window (wrapping arithmetic: equal iff the cells are equal)
+        const uint32_t nx_ = (uint32_t)lo_x + (((uint32_t)sx - (uint32_t)lo_x) & (G - 1));
+        const uint32_t ny_ = (uint32_t)lo_y + (((uint32_t)sy - (uint32_t)lo_y) & (G - 1));
+        const uint32_t ox_ = (uint32_t)olo_x + (((uint32_t)sx - (uint32_t)olo_x) & (G - 1));
+        const uint32_t oy_ = (uint32_t)olo_y + (((uint32_t)sy - (uint32_t)olo_y) & (G - 1));
+        float v = __uint_as_float(QNAN);
+        if (!reset && nx_ == ox_ && ny_ == oy_) v = map[s];
+        const uint32_t k = keys[s];
+        if (k != 0u) {
+            const float f = value_of(k);
+            v = (v != v || c.alpha == 1.0f) ? f : __fadd_rn(v, __fmul_rn(c.alpha, __fsub_rn(f, v)));
+        }
+        if (v != v) v = __uint_as_float(QNAN);
+        map[s] = v;
+        keys[s] = __float_as_uint(v);
+    }
+    if (tid == 0) {
+        A.origin[2 * e] = cx;
+        A.origin[2 * e + 1] = cy;
+    }
+    if (!A.scan_out) return;                                         // kernel argument: uniform
+    __syncthreads();
+    scan_rows(A, P, e, G, LOG_G, cx, cy, true, wave_known, [&](int s) { return __uint_as_float(keys[s]); });
+}
+
+__global__ __launch_bounds__(TT) void elevation_scan_kernel(ElevArgs A)
+{
+    __shared__ int wave_known[WAVES];
+    const int e = blockIdx.x, G = A.cfg.grid;
+    const Pose P = load_pose(A, e);
+    const float *map = A.map + ((size_t)e << (2 * A.log_g));
+    scan_rows(A, P, e, G, A.log_g, A.origin[2 * e], A.origin[2 * e + 1], P.ok, wave_known, [=](int s) { return map[s]; });
+}
+
+bool pos_ok(float v) { return std::isfinite(v) && v > 0.0f; }
+
+bool overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y ? y - x < a_bytes : x - y < b_bytes;
+}
+
+// the checks both entry points share; `who` names the entry point in the message
+int check_common(const char *who, const rover_elevation_cfg *cfg, const float *pos, const float *quat, int64_t comp_stride,
+                 int64_t env_stride, const float *map, const int32_t *origin, const float *ray_x, int32_t nx, const float *ray_y,
+                 int32_t ny, const float *scan_out, int64_t scan_pitch, const int32_t *count_out, int32_t n)
+{
+    auto refuse = [who](const char *why) {
+        rover_internal_fail(ROVER_ERR_INVALID, who, why);
+        return ROVER_ERR_INVALID;
+    };
+    auto unsupported = [who](const char *why) {
+        rover_internal_fail(ROVER_ERR_UNSUPPORTED, who, why);
+        return ROVER_ERR_UNSUPPORTED;
+    };
+    if (!cfg || !pos || !quat || !map || !origin || !ray_x || !ray_y) return refuse("NULL argument");
+    if (n <= 0) return refuse("n must be > 0");
+    const int g = cfg->grid;
+    if (g < ROVER_ELEVATION_MIN_GRID || g > ROVER_ELEVATION_MAX_GRID || (g & (g - 1)) != 0)
+        return unsupported("grid must be a power of two in [8, 128]");
+    if (nx <= 0 || ny <= 0) return refuse("nx and ny must be > 0");
+    if ((int64_t)nx * (int64_t)ny > ROVER_ELEVATION_MAX_RAYS) return unsupported("nx * ny must be <= 4096");
+    if (comp_stride <= 0 || env_stride <= 0) return refuse("comp_stride and env_stride must be > 0");
+    if ((reinterpret_cast<uintptr_t>(pos) | reinterpret_cast<uintptr_t>(quat) | reinterpret_cast<uintptr_t>(map) |
+         reinterpret_cast<uintptr_t>(origin) | reinterpret_cast<uintptr_t>(ray_x) | reinterpret_cast<uintptr_t>(ray_y) |
+         reinterpret_cast<uintptr_t>(scan_out) | reinterpret_cast<uintptr_t>(count_out)) & 3)
+        return refuse("float and int32 pointers must be 4-byte aligned");
+    if (scan_out && scan_pitch < (int64_t)nx * (int64_t)ny) return refuse("scan_pitch must be >= nx * ny");
+    if (scan_out && scan_pitch > (INT64_MAX / 8) / (int64_t)n) return refuse("n * scan_pitch is out of range");
+    const rover_elevation_cfg &c = *cfg;
+    if (!pos_ok(c.cell) || !pos_ok(c.inv_cell)) return refuse("cell and inv_cell must be finite and > 0");
+    if (!pos_ok(c.range_min)) return refuse("range_min must be finite and > 0");
+    if (!(c.range_max >= c.range_min)) return refuse("range_max must be >= range_min");
+    if (!(c.alpha > 0.0f && c.alpha <= 1.0f)) return refuse("alpha must be in (0, 1]");
+    if (c.unknown_value != c.unknown_value) return refuse("unknown_value must not be a NaN");
+    if (c.height_offset != c.height_offset) return refuse("height_offset must not be a NaN");
+    if (!(std::isfinite(c.mount_pos[0]) && std::isfinite(c.mount_pos[1]) && std::isfinite(c.mount_pos[2])))
+        return refuse("mount_pos must be finite");
+    if (scan_out) {
+        const uint64_t map_bytes = (uint64_t)n * (uint64_t)g * (uint64_t)g * 4u;
+        const uint64_t scan_bytes = ((uint64_t)(n - 1) * (uint64_t)scan_pitch + (uint64_t)nx * (uint64_t)ny) * 4u;
+        if (overlap(map, map_bytes, scan_out, scan_bytes)) return refuse("map and scan_out overlap");
+    }
+    return ROVER_OK;
+}
+
+int log2_of(int g)
+{
+    int l = 0;
+    while ((1 << l) < g) ++l;
+    return l;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t rover_elevation_cfg_bytes(void) { return sizeof(rover_elevation_cfg); }
+
+int rover_elevation_step(const rover_elevation_cfg *cfg, const float *depth, int64_t pitch_floats, int32_t height, int32_t width,
+                         const float *ray_b, const float *pos, const float *quat, int64_t comp_stride, int64_t env_stride,
+                         const uint8_t *reset_a, const uint8_t *reset_b, float *map, int32_t *origin, const float *ray_x,
+                         int32_t nx, const float *ray_y, int32_t ny, float *scan_out, int64_t scan_pitch, uint8_t *known_out,
+                         int32_t *count_out, int32_t n, void *stream)
+{
+    static const char who[] = "rover_elevation_step: %s";
+    auto refuse = [](const char *why) { return rover_internal_fail(ROVER_ERR_INVALID, who, why); };
+    if (int rc = check_common(who, cfg, pos, quat, comp_stride, env_stride, map, origin, ray_x, nx, ray_y, ny, scan_out, scan_pitch,
+                              count_out, n))
+        return rc;
+    if (depth && !ray_b) return refuse("NULL argument (depth needs ray_b)");
+    if (height <= 0 || width <= 0) return refuse("height and width must be > 0");
+    const int64_t hw = (int64_t)height * (int64_t)width;
+    if (hw > ROVER_ELEVATION_MAX_PIXELS) return rover_internal_fail(ROVER_ERR_UNSUPPORTED, who, "height * width must be <= 16384");
+    if ((reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(ray_b)) & 3)
+        return refuse("float and int32 pointers must be 4-byte aligned");
+    if (depth) {
+        if (pitch_floats < hw) return refuse("pitch_floats must be >= height * width");
+        if (pitch_floats > (INT64_MAX / 8) / (int64_t)n) return refuse("n * pitch_floats is out of range");
+        const uint64_t map_bytes = (uint64_t)n * (uint64_t)cfg->grid * (uint64_t)cfg->grid * 4u;
+        const uint64_t depth_bytes = ((uint64_t)(n - 1) * (uint64_t)pitch_floats + (uint64_t)hw) * 4u;
+        if (overlap(map, map_bytes, depth, depth_bytes)) return refuse("map and depth overlap");
+    }
+    int dev;
+    if (int rc = device_of(map, &dev, true)) return rc;
+    DeviceGuard guard(dev);
+    ElevArgs A;
+    A.cfg = *cfg;
+    A.depth = depth; A.ray_b = ray_b; A.pos = pos; A.quat = quat; A.ray_x = ray_x; A.ray_y = ray_y;
+    A.reset_a = reset_a; A.reset_b = reset_b;
+    A.map = map; A.origin = origin;
+    A.scan_out = scan_out; A.known_out = known_out; A.count_out = count_out;
+    A.pitch = (long long)pitch_floats; A.comp_stride = (long long)comp_stride; A.env_stride = (long long)env_stride;
+    A.scan_pitch = (long long)scan_pitch;
+    A.hw = (int)hw; A.nx = nx; A.ny = ny; A.log_g = log2_of(cfg->grid);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (cfg->grid) {
+    case 8:   hipLaunchKernelGGL(elevation_step_kernel<8>, dim3((unsigned)n), dim3(TT), 0, st, A); break;
+    case 16:  hipLaunchKernelGGL(elevation_step_kernel<16>, dim3((unsigned)n), dim3(TT), 0, st, A); break;
+    case 32:  hipLaunchKernelGGL(elevation_step_kernel<32>, dim3((unsigned)n), dim3(TT), 0, st, A); break;
+    case 64:  hipLaunchKernelGGL(elevation_step_kernel<64>, dim3((unsigned)n), dim3(TT), 0, st, A); break;
+    default:  hipLaunchKernelGGL(elevation_step_kernel<128>, dim3((unsigned)n), dim3(TT), 0, st, A); break;
+    }
+    return launched("elevation_step_kernel launch: %s");
+}
+
+int rover_elevation_scan(const rover_elevation_cfg *cfg, const float *pos, const float *quat, int64_t comp_stride,
+                         int64_t env_stride, const float *map, const int32_t *origin, const float *ray_x, int32_t nx,
+                         const float *ray_y, int32_t ny, float *scan_out, int64_t scan_pitch, uint8_t *known_out,
+                         int32_t *count_out, int32_t n, void *stream)
+{
+    static const char who[] = "rover_elevation_scan: %s";
+    if (!scan_out) return rover_internal_fail(ROVER_ERR_INVALID, who, "NULL argument");
+    if (int rc = check_common(who, cfg, pos, quat, comp_stride, env_stride, map, origin, ray_x, nx, ray_y, ny, scan_out, scan_pitch,
+                              count_out, n))
+        return rc;
+    int dev;
+    if (int rc = device_of(map, &dev, true)) return rc;
+    DeviceGuard guard(dev);
+    ElevArgs A;
+    A.cfg = *cfg;
+    A.depth = nullptr; A.ray_b = nullptr; A.pos = pos; A.quat = quat; A.ray_x = ray_x; A.ray_y = ray_y;
+    A.reset_a = nullptr; A.reset_b = nullptr;
+    A.map = const_cast<float *>(map); A.origin = const_cast<int32_t *>(origin);
+    A.scan_out = scan_out; A.known_out = known_out; A.count_out = count_out;
+    A.pitch = 0; A.comp_stride = (long long)comp_stride; A.env_stride = (long long)env_stride;
+    A.scan_pitch = (long long)scan_pitch;
+    A.hw = 0; A.nx = nx; A.ny = ny; A.log_g = log2_of(cfg->grid);
+    hipLaunchKernelGGL(elevation_scan_kernel, dim3((unsigned)n), dim3(TT), 0, static_cast<hipStream_t>(stream), A);
+    return launched("elevation_scan_kernel launch: %s");
+}
+
+}  // extern "C"

@@ -428,6 +428,9 @@ class RoverEnv(RLTaskEnv):
         self.extras.pop("depth", None)
         self.extras.pop("rgb", None)
         self.extras.pop("depth_valid", None)
+        self._elevation = None
+        for key in ("elevation_scan", "elevation_known", "elevation_count"):
+            self.extras.pop(key, None)
         if cam is None:
             return
         self._camera_cfg = cam.to_native()
@@ -455,6 +458,18 @@ class RoverEnv(RLTaskEnv):
         self.extras["rgb"] = None          # what the reference's listener reports without RGB data (rover_camera_env.py:94-98)
         if self._depth_sensor is not None:
             self.extras["depth_valid"] = self._depth_valid[0]
+        if self.cfg.elevation is not None:                     # the rolling elevation map: one launch behind the camera chain
+            from ..elevation import ElevationMap
+            em = self._elevation = ElevationMap(self.cfg.elevation, cam, self.cfg.height_scanner, self.num_envs, self.device)
+            with torch.cuda.device(self.device):
+                self._elev_out = [(torch.full((self.num_envs, em.columns), float(self.cfg.elevation.unknown_value),
+                                              dtype=torch.float32, device=self.device),
+                                   torch.zeros((self.num_envs, em.columns), dtype=torch.uint8, device=self.device),
+                                   torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)) for _ in range(self._nbuf)]
+                self._elev_mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
+            self._elev_cur = 0
+            self._elev_pose = (self.state[_lib.POS:_lib.POS + 3].t(), self.state[_lib.QUAT:_lib.QUAT + 4].t())
+            self.extras["elevation_scan"], self.extras["elevation_known"], self.extras["elevation_count"] = self._elev_out[0]
 
     def _render_into(self, buf: torch.Tensor, valid: torch.Tensor | None = None):
         """The depth image of the current state into the row-major (N, H, W) ``buf``, then ``cfg.camera``'s sensor model (its
@@ -467,9 +482,15 @@ class RoverEnv(RLTaskEnv):
         if self._depth_post is not None:
             self._depth_post.apply(buf, self._launch_counter())
 
-    def _camera_update(self, force: bool = False):
-        """Render the pose the step (or reset) left behind into the next depth buffer: extras["depth"] is its (N, W, H) view."""
-        if self._camera_cfg is None or not (force or self.common_step_counter % self._camera_every == 0):
+    def _camera_update(self, force: bool = False, reset=(None, None)):
+        """Render the pose the step (or reset) left behind into the next depth buffer: extras["depth"] is its (N, W, H) view.
+        With ``cfg.elevation`` the map is then updated on every call, without a frame on a step that renders nothing; ``reset``:
+        the step's terminated and time-out buffers, whose envs start their maps over."""
+        if self._camera_cfg is None:
+            return
+        if not (force or self.common_step_counter % self._camera_every == 0):
+            if self._elevation is not None:
+                self._elevation_update(None, reset)
             return
         self._depth_cur = (self._depth_cur + 1) % self._nbuf
         buf = self._depth[self._depth_cur]
@@ -479,6 +500,16 @@ class RoverEnv(RLTaskEnv):
             self._render_into(buf, self._depth_valid[self._depth_cur])
             self.extras["depth_valid"] = self._depth_valid[self._depth_cur]
         self.extras["depth"] = buf.permute(0, 2, 1)
+        if self._elevation is not None:
+            self._elevation_update(buf, reset)
+
+    def _elevation_update(self, depth, reset):
+        """One ``rover_elevation_step`` launch into the next set of output buffers (they rotate as the depth buffers do)."""
+        self._elev_cur = (self._elev_cur + 1) % self._nbuf
+        scan, known, count = self._elev_out[self._elev_cur]
+        pos, quat = self._elev_pose
+        self._elevation.update(depth, pos, quat, reset=reset, scan_out=scan, known_out=known, count_out=count)
+        self.extras["elevation_scan"], self.extras["elevation_known"], self.extras["elevation_count"] = scan, known, count
 
     def render_depth(self) -> torch.Tensor:
         """A fresh depth image of the current state, (num_envs, width, height) fp32: the permuted view of a new row-major
@@ -558,6 +589,8 @@ class RoverEnv(RLTaskEnv):
         if self._obs_post:
             self._post_observations(obs)
         self.obs_buf = {"policy": obs}
+        if self._elevation is not None:
+            self._elevation.clear()
         self._camera_update(force=True)
         return self.obs_buf, self.extras
 
@@ -583,6 +616,9 @@ class RoverEnv(RLTaskEnv):
         if self._obs_post:
             self._post_observations(obs)
         self.obs_buf = {"policy": obs}
+        if self._elevation is not None:                   # the masked envs' maps start over with a frame of their new pose
+            self._elev_mask.fill_(1) if mask_d is None else self._elev_mask.copy_(mask_d)
+            self._camera_update(force=True, reset=(self._elev_mask, None))
         return self.obs_buf, self.extras
 
     def _check_action(self, action: torch.Tensor) -> torch.Tensor:
@@ -614,7 +650,7 @@ class RoverEnv(RLTaskEnv):
         self.reward_buf = self._rew[k]
         self.reset_terminated = self._term_b[k]
         self.reset_time_outs = self._trunc_b[k]
-        self._camera_update()
+        self._camera_update(reset=(self._term[k], self._trunc[k]))
         return self.obs_buf, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
 
     def _fresh_scan(self) -> torch.Tensor:
@@ -677,7 +713,7 @@ class RoverEnv(RLTaskEnv):
         self.obs_buf = self._obs_dicts[k]
         if self._obs_post:
             self._post_observations(self.obs_buf["policy"])
-        self._camera_update()
+        self._camera_update(reset=(self._term[k], self._trunc[k]))
         return self.obs_buf, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
 
     def _post_observations(self, obs: torch.Tensor):
@@ -759,7 +795,7 @@ class RoverEnv(RLTaskEnv):
         self.reward_buf = self._rew[k]
         self.reset_terminated = self._term_b[k]
         self.reset_time_outs = self._trunc_b[k]
-        self._camera_update()
+        self._camera_update(reset=(self._term[k], self._trunc[k]))
         return a.value, b.value
 
     def profile_event_overhead(self, reps: int = 100) -> float:
@@ -859,11 +895,14 @@ class RoverEnv(RLTaskEnv):
     def state_dict(self) -> dict:
         """Everything needed to continue bit-for-bit: state words, the last observation, the episodic log vector."""
         self.flush_log()
-        return {"state": self.get_state().cpu(), "obs": self.obs_buf["policy"].detach().cpu().clone(),
-                "log": self._log.detach().cpu().clone(), "num_envs": self.num_envs,
-                "common_step_counter": int(self.common_step_counter), "call_counter": self.call_counter,
-                # the Philox key: an env re-seeded with seed() / reset(seed=) must be restored with ITS key
-                "seed_lo": int(self._native_cfg.seed_lo), "seed_hi": int(self._native_cfg.seed_hi)}
+        sd = {"state": self.get_state().cpu(), "obs": self.obs_buf["policy"].detach().cpu().clone(),
+              "log": self._log.detach().cpu().clone(), "num_envs": self.num_envs,
+              "common_step_counter": int(self.common_step_counter), "call_counter": self.call_counter,
+              # the Philox key: an env re-seeded with seed() / reset(seed=) must be restored with ITS key
+              "seed_lo": int(self._native_cfg.seed_lo), "seed_hi": int(self._native_cfg.seed_hi)}
+        if self._elevation is not None:                        # the map is state of its own: what the camera saw earlier
+            sd.update(self._elevation.state_dict())
+        return sd
 
     def load_state_dict(self, sd: dict):
         """Restore a ``state_dict()`` of an env of the same size and configuration; returns the observation dict."""
@@ -878,6 +917,8 @@ class RoverEnv(RLTaskEnv):
             self.seed(int(sd["seed_lo"]) | (int(sd["seed_hi"]) << 32))
         _lib.check(self._lib.rover_set_counter(self._h, int(sd.get("call_counter", 0))), "rover_set_counter")
         self._sync_counter()                                   # the struct mirror follows the handle
+        if self._elevation is not None and "elevation_map" in sd:
+            self._elevation.load_state_dict(sd)
         self.obs_buf = self._obs_dicts[self._cur]
         return self.obs_buf
 
