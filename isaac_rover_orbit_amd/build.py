@@ -27,6 +27,7 @@ HEADERS = [os.path.join(_PKG, "csrc", "rover_model.hpp"), os.path.join(_PKG, "cs
            os.path.join(_PKG, "csrc", "train_math.hpp"), os.path.join(_PKG, "csrc", "offpolicy_collect.hpp"),
            os.path.join(_PKG, "csrc", "train_shared.hpp"), os.path.join(_PKG, "csrc", "lift_render.hpp"),
            os.path.join(_PKG, "csrc", "collect_record.hpp"), os.path.join(_PKG, "csrc", "dagger_tail.hpp"),
+           os.path.join(_PKG, "csrc", "viewer_common.hpp"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_lift.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_hip.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_terrain.h"),

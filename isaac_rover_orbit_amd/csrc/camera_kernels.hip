@@ -27,12 +27,6 @@ using terrain_march::L2;
 using terrain_march::Pyramid;
 using terrain_march::pyramid_of;
 
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t _e = (expr);                                                                                        \
-        if (_e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, #expr ": %s", hipGetErrorString(_e));         \
-    } while (0)
-
 constexpr int TILE = 8;      // pixels per side of a wave's tile
 constexpr int WAVES = 4;     // waves (tiles) per workgroup
 

@@ -1,5 +1,6 @@
 // lift_viewer_kernels.hip -- the rgb_array viewer of FrankaCubeLift-v0 (gfx950): one world-placed pinhole camera that renders every
-// env's table, arm, gripper, cube and goal marker into one RGBA image.  DESIGN.md section 29 is the image contract;
+// env's table, arm, gripper, cube and goal marker into one RGBA image.  DESIGN.md section 37 is the image contract it shares with
+// the rover's viewer (camera, hit rule, sky, packing and the host's config code: viewer_common.hpp), section 29 this scene;
 // include/rover_lift_viewer.h the ABI.
 //
 // Reference: ORBIT's RLTaskEnv.render() in "rgb_array" mode (the viewport camera cfg.viewer places; manipulation_env_cfg.py:235
@@ -23,17 +24,11 @@
 #include "lift_render.hpp"
 #include "rover_internal.hpp"
 #include "rover_render.hpp"
+#include "viewer_common.hpp"
 
 namespace {
 
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t _e = (expr);                                                                                        \
-        if (_e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, #expr ": %s", hipGetErrorString(_e));         \
-    } while (0)
-
-constexpr int TILE = 8;         // pixels per side of a wave's tile
-constexpr int WAVES = 4;        // waves (tiles) per workgroup
+using namespace viewer_common;
 
 // ---- per-env record of the pose pass (floats, world frame)
 constexpr int PW_SPHERE = 0;    // 4  bounding sphere (centre, radius) of everything the env draws
@@ -52,8 +47,6 @@ constexpr int POSE_WORDS = 64;
 struct Layout {
     size_t off_ovf, off_pose, bytes;
 };
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 Layout layout_of(int n)
 {
@@ -84,7 +77,6 @@ struct PoseParams {
     float *pose;
 };
 
-__device__ __forceinline__ float dot3(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 __device__ __forceinline__ bool finite3(const float *a) { return isfinite(a[0]) && isfinite(a[1]) && isfinite(a[2]); }
 
 struct Bounds {
@@ -213,42 +205,13 @@ struct ViewParams {
     float inv_spacing;
     const int *ovf_count, *ovf;
     const float *pose;
-    // camera
-    int img_w, img_h, tiles_x, tiles;
-    float eye[3], fwd[3], right[3], up[3];
-    float inv_f, half_w, half_h;
+    Pinhole cam;
     float near_clip, far_clip;
     // outputs
     uint32_t *rgba;
     float *depth;
     int32_t *object_id;
 };
-
-struct Best {
-    float t;
-    int id;
-    float n[3];                  // geometric normal facing the ray
-};
-
-__device__ __forceinline__ void offer(Best &b, float t, int id, const float *n, const float *d, float far_clip)
-{
-    if (t <= far_clip && (t < b.t || (t == b.t && id < b.id))) {
-        const float s = dot3(n, d) > 0.0f ? -1.0f : 1.0f;
-        b.t = t; b.id = id; b.n[0] = s * n[0]; b.n[1] = s * n[1]; b.n[2] = s * n[2];
-    }
-}
-
-// [t0, t1] of the ray o + t d inside a sphere; false if it misses
-__device__ __forceinline__ bool sphere_span(const float *o, const float *d, const float *c, float r, float &t0, float &t1)
-{
-    const float oc[3] = {o[0] - c[0], o[1] - c[1], o[2] - c[2]};
-    const float b = dot3(oc, d), cc = dot3(oc, oc) - r * r;
-    const float disc = b * b - cc;
-    if (!(disc >= 0.0f)) return false;
-    const float sq = sqrtf(disc);
-    t0 = -b - sq; t1 = -b + sq;
-    return true;
-}
 
 // the box {x : |g_a . (x - c)| <= h_a, a = 0, 1, 2}; the normal of face a is g_a, normalised
 __device__ void test_box(const float *o, const float *d, const float *c, const float *g, const float *h, float near_clip, float far_clip,
@@ -378,18 +341,7 @@ __device__ void test_env(const ViewParams &p, int env, const float *o, const flo
         const float ch[3] = {LR_CUBE_HALF, LR_CUBE_HALF, LR_CUBE_HALF};
         test_box(o, d, P + PW_CUBE, P + PW_CUBE_INV, ch, p.near_clip, p.far_clip, id0 + LR_K_CUBE, b);
     }
-    if (mask >> LR_K_GOAL & 1) {
-        const float *c = P + PW_GOAL;
-        float t0, t1;
-        if (sphere_span(o, d, c, LR_GOAL_RADIUS, t0, t1)) {
-            const float t = t0 >= p.near_clip ? t0 : t1;
-            if (t >= p.near_clip) {
-                float nrm[3];
-                for (int i = 0; i < 3; ++i) nrm[i] = (o[i] + t * d[i] - c[i]) * (1.0f / LR_GOAL_RADIUS);
-                offer(b, t, id0 + LR_K_GOAL, nrm, d, p.far_clip);
-            }
-        }
-    }
+    if (mask >> LR_K_GOAL & 1) test_marker(o, d, P + PW_GOAL, LR_GOAL_RADIUS, p.near_clip, p.far_clip, id0 + LR_K_GOAL, b);
 }
 
 // the envs of lattice cells (bu + du, bv - 1 .. bv + 1) or (bu - 1 .. bu + 1, bv + dv): one side of a 3 x 3 neighbourhood
@@ -409,22 +361,20 @@ __device__ __forceinline__ bool clip_axis(float go, float gd, float lo, float hi
     return true;
 }
 
-__device__ __forceinline__ uint32_t to_byte(float x) { return (uint32_t)rintf(255.0f * fminf(fmaxf(x, 0.0f), 1.0f)); }
-
 __global__ __launch_bounds__(TILE * TILE * WAVES) void lift_viewer_render_kernel(ViewParams p)
 {
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES + (threadIdx.x >> 6)));
-    if (wave >= p.tiles) return;
+    if (wave >= p.cam.tiles) return;
     const int lane = threadIdx.x & 63;
-    const int u = (wave % p.tiles_x) * TILE + (lane & (TILE - 1));
-    const int v = (wave / p.tiles_x) * TILE + (lane >> 3);
-    if (u >= p.img_w || v >= p.img_h) return;
+    const int u = (wave % p.cam.tiles_x) * TILE + (lane & (TILE - 1));
+    const int v = (wave / p.cam.tiles_x) * TILE + (lane >> 3);
+    if (u >= p.cam.img_w || v >= p.cam.img_h) return;
 
     // ---- ray through the pixel centre
-    const float o[3] = {p.eye[0], p.eye[1], p.eye[2]};
-    const float cx = ((float)u + 0.5f - p.half_w) * p.inv_f, cy = -((float)v + 0.5f - p.half_h) * p.inv_f;
+    const float o[3] = {p.cam.eye[0], p.cam.eye[1], p.cam.eye[2]};
+    const float cx = ((float)u + 0.5f - p.cam.half_w) * p.cam.inv_f, cy = -((float)v + 0.5f - p.cam.half_h) * p.cam.inv_f;
     float d[3];
-    for (int i = 0; i < 3; ++i) d[i] = p.fwd[i] + cx * p.right[i] + cy * p.up[i];
+    for (int i = 0; i < 3; ++i) d[i] = p.cam.fwd[i] + cx * p.cam.right[i] + cy * p.cam.up[i];
     const float dn = 1.0f / sqrtf(dot3(d, d));
     for (int i = 0; i < 3; ++i) d[i] *= dn;
 
@@ -476,9 +426,7 @@ __global__ __launch_bounds__(TILE * TILE * WAVES) void lift_viewer_render_kernel
     // ---- shading
     float rgb[3];
     if (b.id == LR_ID_SKY) {
-        const float hz[3] = RR_SKY_HORIZON, zn[3] = RR_SKY_ZENITH;
-        const float w = fmaxf(d[2], 0.0f);
-        for (int i = 0; i < 3; ++i) rgb[i] = hz[i] + (zn[i] - hz[i]) * w;
+        sky_colour(d, rgb);
     } else {
         const int kind = b.id < LR_ID_ENV0 ? -1 : (b.id - LR_ID_ENV0) % LR_IDS_PER_ENV;
         const float gr[3] = LR_ALBEDO_GROUND, tb[3] = LR_ALBEDO_TABLE, ar[3] = LR_ALBEDO_ARM, hd[3] = LR_ALBEDO_HAND,
@@ -494,30 +442,16 @@ __global__ __launch_bounds__(TILE * TILE * WAVES) void lift_viewer_render_kernel
             rgb[i] = alb * shade;
         }
     }
-    const size_t px = (size_t)v * p.img_w + u;
-    p.rgba[px] = to_byte(rgb[0]) | (to_byte(rgb[1]) << 8) | (to_byte(rgb[2]) << 16) | 0xFF000000u;
+    const size_t px = (size_t)v * p.cam.img_w + u;
+    p.rgba[px] = pack_rgba(rgb);
     if (p.depth) p.depth[px] = b.id == LR_ID_SKY ? INFINITY : b.t;
     if (p.object_id) p.object_id[px] = b.id;
 }
 
-double norm3(const double *v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
-
-// the C entry's checks; n <= 0: the env index is not checked (workspace_bytes checks n itself)
+// the C entry's checks: the shared ones, then the lift's two members
 bool config_ok(const rover_lift_viewer_config *c, int n)
 {
-    if (!c) return false;
-    for (int i = 0; i < 3; ++i)
-        if (!std::isfinite(c->eye[i]) || !std::isfinite(c->lookat[i])) return false;
-    const double dx = (double)c->lookat[0] - c->eye[0], dy = (double)c->lookat[1] - c->eye[1];
-    if (dx == 0.0 && dy == 0.0) return false;                      // eye == lookat, or a view along +-Z
-    if (!(std::isfinite(c->focal_length) && std::isfinite(c->horizontal_aperture) && c->focal_length > 0.0f &&
-          c->horizontal_aperture > 0.0f))
-        return false;
-    if (!(c->near_clip >= 0.0f && c->near_clip < c->far_clip)) return false;
-    if (c->width < 1 || c->height < 1 || c->width > ROVER_VIEWER_MAX_SIZE || c->height > ROVER_VIEWER_MAX_SIZE) return false;
-    if (!(std::isfinite(c->env_spacing) && c->env_spacing > 0.0f && std::isfinite(c->ee_offset_z))) return false;
-    if (c->origin_type == ROVER_VIEWER_ORIGIN_ENV) return c->env_index >= 0 && c->env_index < n;
-    return c->origin_type == ROVER_VIEWER_ORIGIN_WORLD;
+    return view_config_ok(c, n) && std::isfinite(c->env_spacing) && c->env_spacing > 0.0f && std::isfinite(c->ee_offset_z);
 }
 
 void origin_of(int env, int rows, int cols, double spacing, double *out)
@@ -535,15 +469,7 @@ extern "C" {
 int rover_lift_viewer_default_config(rover_lift_viewer_config *c)
 {
     if (!c) return rover_internal_fail(ROVER_ERR_INVALID, "cfg is NULL");
-    c->eye[0] = c->eye[1] = -6.0f; c->eye[2] = 3.5f;           // manipulation_env_cfg.py:235
-    c->lookat[0] = c->lookat[1] = c->lookat[2] = 0.0f;
-    c->origin_type = ROVER_VIEWER_ORIGIN_WORLD;
-    c->env_index = 0;
-    c->width = 1280; c->height = 720;
-    c->focal_length = RR_FOCAL_LENGTH;
-    c->horizontal_aperture = RR_HORIZONTAL_APERTURE;
-    c->near_clip = RR_NEAR_CLIP; c->far_clip = RR_FAR_CLIP;
-    c->draw_targets = 1;
+    default_view(c, -6.0f, -6.0f, 3.5f);                       // manipulation_env_cfg.py:235
     c->env_spacing = 2.5f;
     c->ee_offset_z = 0.1034f;
     return ROVER_OK;
@@ -619,27 +545,12 @@ int rover_lift_viewer_render(const float *state, int32_t num_envs, const rover_l
     ViewParams p;
     p.n = num_envs; p.rows = rows; p.cols = cols; p.inv_spacing = pp.inv_spacing;
     p.ovf_count = pp.ovf_count; p.ovf = pp.ovf; p.pose = pp.pose;
-    p.img_w = cfg->width; p.img_h = cfg->height;
-    p.tiles_x = (cfg->width + TILE - 1) / TILE;
-    p.tiles = p.tiles_x * ((cfg->height + TILE - 1) / TILE);
-    // camera basis: forward = lookat - eye, right = forward x +Z, up = right x forward (float64, then rounded)
-    double f[3] = {(double)cfg->lookat[0] - cfg->eye[0], (double)cfg->lookat[1] - cfg->eye[1], (double)cfg->lookat[2] - cfg->eye[2]};
-    const double fl = norm3(f);
-    for (double &x : f) x /= fl;
-    double r[3] = {f[1], -f[0], 0.0};
-    const double rl = norm3(r);
-    for (double &x : r) x /= rl;
-    const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
     double org[3] = {0.0, 0.0, 0.0};
     if (cfg->origin_type == ROVER_VIEWER_ORIGIN_ENV) origin_of(cfg->env_index, rows, cols, (double)cfg->env_spacing, org);
-    for (int i = 0; i < 3; ++i) {
-        p.eye[i] = (float)((double)cfg->eye[i] + org[i]); p.fwd[i] = (float)f[i]; p.right[i] = (float)r[i]; p.up[i] = (float)u[i];
-    }
-    p.inv_f = (float)((double)cfg->horizontal_aperture / ((double)cfg->width * cfg->focal_length));
-    p.half_w = 0.5f * (float)cfg->width; p.half_h = 0.5f * (float)cfg->height;
+    p.cam = pinhole_of(cfg, org);
     p.near_clip = cfg->near_clip; p.far_clip = cfg->far_clip;
     p.rgba = rgba; p.depth = depth; p.object_id = object_id;
-    const unsigned blocks = (unsigned)((p.tiles + WAVES - 1) / WAVES);
+    const unsigned blocks = (unsigned)((p.cam.tiles + WAVES - 1) / WAVES);
     hipLaunchKernelGGL(lift_viewer_render_kernel, dim3(blocks), dim3(TILE * TILE * WAVES), 0, st, p);
     HIP_TRY(hipGetLastError());
     return ROVER_OK;

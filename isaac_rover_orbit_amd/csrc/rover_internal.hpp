@@ -33,6 +33,13 @@ inline int launched(const char *what)
     return ROVER_OK;
 }
 
+// in an entry point: a failed HIP call is the entry's ROVER_ERR_HIP, with the call's text and the runtime's message
+#define HIP_TRY(expr)                                                                                                  \
+    do {                                                                                                               \
+        hipError_t _e = (expr);                                                                                        \
+        if (_e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, #expr ": %s", hipGetErrorString(_e));         \
+    } while (0)
+
 // Every entry point that launches work runs on the handle's device, whatever the calling thread's current device is.
 struct DeviceGuard {
     int prev = -1;

@@ -3489,6 +3489,7 @@ int fail(int code, const char *fmt, const char *detail = "")
     snprintf(g_err, sizeof(g_err), fmt, detail);
     return code;
 }
+#undef HIP_TRY  // rover_internal.hpp's goes through rover_internal_fail, which is defined below; this unit calls fail() itself
 #define HIP_TRY(expr)                                                                                                  \
     do {                                                                                                               \
         hipError_t _e = (expr);                                                                                        \

@@ -12,12 +12,6 @@
 
 namespace {
 
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t _e = (expr);                                                                                        \
-        if (_e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, #expr ": %s", hipGetErrorString(_e));         \
-    } while (0)
-
 __global__ void fill_f32_kernel(float *dst, size_t n, float v)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

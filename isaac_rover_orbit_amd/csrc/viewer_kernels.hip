@@ -1,5 +1,6 @@
 // viewer_kernels.hip -- the rgb_array viewer (gfx950): one world-placed pinhole camera that renders the terrain mesh, every env's
-// rover and every env's target into one RGBA image.  DESIGN.md section 11 is the image contract; include/rover_viewer.h the ABI.
+// rover and every env's target into one RGBA image.  DESIGN.md section 37 is the image contract it shares with the lift's viewer
+// (camera, hit rule, sky, packing and the host's config code: viewer_common.hpp), section 11 this scene; include/rover_viewer.h the ABI.
 //
 // Reference: ORBIT's RLTaskEnv.render() in "rgb_array" mode (the viewport camera cfg.viewer places; rover_env_cfg.py:272 sets its
 // eye), which gymnasium.wrappers.RecordVideo records in examples/02_train/train.py:123-125.
@@ -23,21 +24,16 @@
 #include "rover_model.hpp"
 #include "rover_render.hpp"
 #include "terrain_march.hpp"
+#include "viewer_common.hpp"
 
 namespace {
+
+using namespace viewer_common;
 
 using terrain_march::L2;
 using terrain_march::Pyramid;
 using terrain_march::pyramid_of;
 
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t _e = (expr);                                                                                        \
-        if (_e != hipSuccess) return rover_internal_fail(ROVER_ERR_HIP, #expr ": %s", hipGetErrorString(_e));         \
-    } while (0)
-
-constexpr int TILE = 8;         // pixels per side of a wave's tile
-constexpr int WAVES = 4;        // waves (tiles) per workgroup
 constexpr int POSE_WORDS = 48;  // per env: pos (3), R row-major (9), wheel centres (6 x 3), wheel axles (6 x 3), world frame
 
 // ---- workspace layout (all offsets 256-byte aligned): pyramid | counts | start | cursor | items | overflow | poses
@@ -49,10 +45,6 @@ struct Layout {
     size_t off_cnt, off_start, off_cur, off_items, off_ovf, off_pose, bytes;
     float rover_r;               // bounding radius of a rover about its root position (any bogie / steer angle)
 };
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-double norm3(const double *v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
 
 float rover_bound_radius()
 {
@@ -240,10 +232,7 @@ struct ViewParams {
     const int *start, *items, *ovf_count, *ovf;
     const float *pose;
     float rover_r;
-    // camera
-    int img_w, img_h, tiles_x, tiles;
-    float eye[3], fwd[3], right[3], up[3];
-    float inv_f, half_w, half_h;
+    Pinhole cam;
     float near_clip, far_clip;
     // outputs
     uint32_t *rgba;
@@ -251,44 +240,12 @@ struct ViewParams {
     int32_t *object_id;
 };
 
-struct Best {
-    float t;
-    int id;
-    float n[3];                  // geometric normal (objects; the terrain's is formed at shading)
-};
-
-__device__ __forceinline__ void offer(Best &b, float t, int id, float nx, float ny, float nz, float far_clip)
-{
-    if (t <= far_clip && (t < b.t || (t == b.t && id < b.id))) { b.t = t; b.id = id; b.n[0] = nx; b.n[1] = ny; b.n[2] = nz; }
-}
-
-__device__ __forceinline__ float dot3(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-
-// [t0, t1] of the ray o + t d inside a sphere; false if it misses
-__device__ __forceinline__ bool sphere_span(const float *o, const float *d, const float *c, float r, float &t0, float &t1)
-{
-    const float oc[3] = {o[0] - c[0], o[1] - c[1], o[2] - c[2]};
-    const float b = dot3(oc, d), cc = dot3(oc, oc) - r * r;
-    const float disc = b * b - cc;
-    if (!(disc >= 0.0f)) return false;
-    const float sq = sqrtf(disc);
-    t0 = -b - sq; t1 = -b + sq;
-    return true;
-}
-
 __device__ void test_target(const ViewParams &p, int env, const float *o, const float *d, float near_clip, Best &b)
 {
     const size_t N = (size_t)p.n;
     const float c[3] = {p.state[ROVER_TARGET_W * N + env], p.state[(ROVER_TARGET_W + 1) * N + env],
                         p.state[(ROVER_TARGET_W + 2) * N + env] + RR_TARGET_Z_OFFSET};
-    float t0, t1;
-    if (!sphere_span(o, d, c, RR_TARGET_RADIUS, t0, t1)) return;
-    const float t = t0 >= near_clip ? t0 : t1;
-    if (!(t >= near_clip)) return;
-    float nrm[3];
-    for (int i = 0; i < 3; ++i) nrm[i] = (o[i] + t * d[i] - c[i]) * (1.0f / RR_TARGET_RADIUS);
-    const float s = dot3(nrm, d) > 0.0f ? -1.0f : 1.0f;
-    offer(b, t, RR_ID_ENV0 + RR_IDS_PER_ENV * env + 7, s * nrm[0], s * nrm[1], s * nrm[2], p.far_clip);
+    test_marker(o, d, c, RR_TARGET_RADIUS, near_clip, p.far_clip, RR_ID_ENV0 + RR_IDS_PER_ENV * env + 7, b);
 }
 
 __device__ void test_rover(const ViewParams &p, int env, const float *o, const float *d, float near_clip, Best &b)
@@ -321,8 +278,8 @@ __device__ void test_rover(const ViewParams &p, int env, const float *o, const f
             const float t = front ? te : tx;
             const int a = front ? ae : ax;
             if (t >= near_clip) {
-                const float s = dl[a] > 0.0f ? -1.0f : 1.0f;      // the face normal facing the ray, Body axis a -> world column a
-                offer(b, t, id0, s * R[a], s * R[3 + a], s * R[6 + a], p.far_clip);
+                const float nrm[3] = {R[a], R[3 + a], R[6 + a]};  // the face normal, Body axis a -> world column a (nrm . d is dl[a])
+                offer(b, t, id0, nrm, d, p.far_clip);
             }
         }
     }
@@ -367,8 +324,7 @@ __device__ void test_rover(const ViewParams &p, int env, const float *o, const f
             const float nn = 1.0f / sqrtf(fmaxf(dot3(nrm, nrm), 1.0e-30f));
             for (int i = 0; i < 3; ++i) nrm[i] *= nn;
         }
-        const float s = dot3(nrm, d) > 0.0f ? -1.0f : 1.0f;
-        offer(b, t, id0 + 1 + k, s * nrm[0], s * nrm[1], s * nrm[2], p.far_clip);
+        offer(b, t, id0 + 1 + k, nrm, d, p.far_clip);
     }
 }
 
@@ -378,26 +334,24 @@ __device__ __forceinline__ void test_item(const ViewParams &p, int it, const flo
     else test_rover(p, it >> 1, o, d, p.near_clip, b);
 }
 
-__device__ __forceinline__ uint32_t to_byte(float x) { return (uint32_t)rintf(255.0f * fminf(fmaxf(x, 0.0f), 1.0f)); }
-
 __global__ __launch_bounds__(TILE * TILE * WAVES) void rover_viewer_render_kernel(ViewParams p)
 {
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES + (threadIdx.x >> 6)));
-    if (wave >= p.tiles) return;
+    if (wave >= p.cam.tiles) return;
     const int lane = threadIdx.x & 63;
-    const int u = (wave % p.tiles_x) * TILE + (lane & (TILE - 1));
-    const int v = (wave / p.tiles_x) * TILE + (lane >> 3);
-    if (u >= p.img_w || v >= p.img_h) return;
+    const int u = (wave % p.cam.tiles_x) * TILE + (lane & (TILE - 1));
+    const int v = (wave / p.cam.tiles_x) * TILE + (lane >> 3);
+    if (u >= p.cam.img_w || v >= p.cam.img_h) return;
 
     // ---- eye (wave-uniform), ray through the pixel centre
-    float o[3] = {p.eye[0], p.eye[1], p.eye[2]};
+    float o[3] = {p.cam.eye[0], p.cam.eye[1], p.cam.eye[2]};
     if (p.origin_env >= 0) {
         const size_t N = (size_t)p.n;
         for (int i = 0; i < 3; ++i) o[i] += p.state[(ROVER_POS + i) * N + p.origin_env];
     }
-    const float cx = ((float)u + 0.5f - p.half_w) * p.inv_f, cy = -((float)v + 0.5f - p.half_h) * p.inv_f;
+    const float cx = ((float)u + 0.5f - p.cam.half_w) * p.cam.inv_f, cy = -((float)v + 0.5f - p.cam.half_h) * p.cam.inv_f;
     float d[3];
-    for (int i = 0; i < 3; ++i) d[i] = p.fwd[i] + cx * p.right[i] + cy * p.up[i];
+    for (int i = 0; i < 3; ++i) d[i] = p.cam.fwd[i] + cx * p.cam.right[i] + cy * p.cam.up[i];
     const float dn = 1.0f / sqrtf(dot3(d, d));
     for (int i = 0; i < 3; ++i) d[i] *= dn;
 
@@ -445,9 +399,7 @@ __global__ __launch_bounds__(TILE * TILE * WAVES) void rover_viewer_render_kerne
     // ---- shading
     float alb[3], rgb[3];
     if (b.id == RR_ID_SKY) {
-        const float hz[3] = RR_SKY_HORIZON, zn[3] = RR_SKY_ZENITH;
-        const float w = fmaxf(d[2], 0.0f);
-        for (int i = 0; i < 3; ++i) rgb[i] = hz[i] + (zn[i] - hz[i]) * w;
+        sky_colour(d, rgb);
     } else {
         if (b.id == RR_ID_GROUND) {
             // the hit triangle of cell (ix, iy): lower (fx >= fy) corners 00, 01, 11; upper 00, 10, 11
@@ -477,27 +429,10 @@ __global__ __launch_bounds__(TILE * TILE * WAVES) void rover_viewer_render_kerne
         const float shade = RR_K_AMBIENT + RR_K_DIFFUSE * fmaxf(dot3(b.n, l) * ln, 0.0f);
         for (int i = 0; i < 3; ++i) rgb[i] = alb[i] * shade;
     }
-    const size_t px = (size_t)v * p.img_w + u;
-    p.rgba[px] = to_byte(rgb[0]) | (to_byte(rgb[1]) << 8) | (to_byte(rgb[2]) << 16) | 0xFF000000u;
+    const size_t px = (size_t)v * p.cam.img_w + u;
+    p.rgba[px] = pack_rgba(rgb);
     if (p.depth) p.depth[px] = b.id == RR_ID_SKY ? INFINITY : b.t;
     if (p.object_id) p.object_id[px] = b.id;
-}
-
-// the C entry's checks; `n` = the handle's env count (env_index)
-bool config_ok(const rover_viewer_config *c, int n)
-{
-    if (!c) return false;
-    for (int i = 0; i < 3; ++i)
-        if (!std::isfinite(c->eye[i]) || !std::isfinite(c->lookat[i])) return false;
-    const double dx = (double)c->lookat[0] - c->eye[0], dy = (double)c->lookat[1] - c->eye[1];
-    if (dx == 0.0 && dy == 0.0) return false;                      // eye == lookat, or a view along +-Z
-    if (!(std::isfinite(c->focal_length) && std::isfinite(c->horizontal_aperture) && c->focal_length > 0.0f &&
-          c->horizontal_aperture > 0.0f))
-        return false;
-    if (!(c->near_clip >= 0.0f && c->near_clip < c->far_clip)) return false;
-    if (c->width < 1 || c->height < 1 || c->width > ROVER_VIEWER_MAX_SIZE || c->height > ROVER_VIEWER_MAX_SIZE) return false;
-    if (c->origin_type == ROVER_VIEWER_ORIGIN_ENV) return c->env_index >= 0 && c->env_index < n;
-    return c->origin_type == ROVER_VIEWER_ORIGIN_WORLD;
 }
 
 }  // namespace
@@ -507,15 +442,7 @@ extern "C" {
 int rover_viewer_default_config(rover_viewer_config *c)
 {
     if (!c) return rover_internal_fail(ROVER_ERR_INVALID, "cfg is NULL");
-    c->eye[0] = c->eye[1] = c->eye[2] = 7.5f;                  // ORBIT ViewerCfg
-    c->lookat[0] = c->lookat[1] = c->lookat[2] = 0.0f;
-    c->origin_type = ROVER_VIEWER_ORIGIN_WORLD;
-    c->env_index = 0;
-    c->width = 1280; c->height = 720;
-    c->focal_length = RR_FOCAL_LENGTH;
-    c->horizontal_aperture = RR_HORIZONTAL_APERTURE;
-    c->near_clip = RR_NEAR_CLIP; c->far_clip = RR_FAR_CLIP;
-    c->draw_targets = 1;
+    default_view(c, 7.5f, 7.5f, 7.5f);                         // ORBIT ViewerCfg
     return ROVER_OK;
 }
 
@@ -525,7 +452,7 @@ size_t rover_viewer_workspace_bytes(const rover_sim *sim, const rover_viewer_con
 {
     if (!sim) return 0;
     const rover_sim_view s = rover_internal_view(const_cast<rover_sim *>(sim));
-    if (!s.have_terrain || !config_ok(cfg, s.n)) return 0;
+    if (!s.have_terrain || !view_config_ok(cfg, s.n)) return 0;
     return layout_of(s).bytes;
 }
 
@@ -533,7 +460,7 @@ int rover_viewer_prepare(rover_sim *sim, const rover_viewer_config *cfg, void *w
 {
     if (!sim || !ws) return rover_internal_fail(ROVER_ERR_INVALID, "sim / ws is NULL");
     const rover_sim_view s = rover_internal_view(sim);
-    if (!config_ok(cfg, s.n)) return rover_internal_fail(ROVER_ERR_INVALID, "invalid rover_viewer_config");
+    if (!view_config_ok(cfg, s.n)) return rover_internal_fail(ROVER_ERR_INVALID, "invalid rover_viewer_config");
     if (!s.have_terrain) return rover_internal_fail(ROVER_ERR_STATE, "rover_set_terrain has not been called");
     DeviceGuard guard(s.device);
     if (bytes < layout_of(s).bytes) return rover_internal_fail(ROVER_ERR_INVALID, "viewer workspace too small");
@@ -550,7 +477,7 @@ int rover_viewer_render(rover_sim *sim, const rover_viewer_config *cfg, void *ws
 {
     if (!sim || !ws || !rgba) return rover_internal_fail(ROVER_ERR_INVALID, "sim / ws / rgba is NULL");
     const rover_sim_view s = rover_internal_view(sim);
-    if (!config_ok(cfg, s.n)) return rover_internal_fail(ROVER_ERR_INVALID, "invalid rover_viewer_config");
+    if (!view_config_ok(cfg, s.n)) return rover_internal_fail(ROVER_ERR_INVALID, "invalid rover_viewer_config");
     if (!s.have_terrain) return rover_internal_fail(ROVER_ERR_STATE, "rover_set_terrain has not been called");
     if (!s.state) return rover_internal_fail(ROVER_ERR_STATE, "rover_bind has not been called");
     if (s.phase_open) return rover_internal_fail(ROVER_ERR_STATE, "rover_viewer_render between rover_step_begin and rover_step_finish");
@@ -589,25 +516,10 @@ int rover_viewer_render(rover_sim *sim, const rover_viewer_config *cfg, void *ws
     p.draw_targets = bp.draw_targets;
     p.start = bp.start; p.items = bp.items; p.ovf_count = bp.counts + L.nb; p.ovf = bp.ovf; p.pose = bp.pose;
     p.rover_r = L.rover_r;
-    p.img_w = cfg->width; p.img_h = cfg->height;
-    p.tiles_x = (cfg->width + TILE - 1) / TILE;
-    p.tiles = p.tiles_x * ((cfg->height + TILE - 1) / TILE);
-    // camera basis: forward = lookat - eye, right = forward x +Z, up = right x forward (float64, then rounded)
-    double f[3] = {(double)cfg->lookat[0] - cfg->eye[0], (double)cfg->lookat[1] - cfg->eye[1], (double)cfg->lookat[2] - cfg->eye[2]};
-    const double fl = norm3(f);
-    for (double &x : f) x /= fl;
-    double r[3] = {f[1], -f[0], 0.0};
-    const double rl = norm3(r);
-    for (double &x : r) x /= rl;
-    const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
-    for (int i = 0; i < 3; ++i) {
-        p.eye[i] = cfg->eye[i]; p.fwd[i] = (float)f[i]; p.right[i] = (float)r[i]; p.up[i] = (float)u[i];
-    }
-    p.inv_f = (float)((double)cfg->horizontal_aperture / ((double)cfg->width * cfg->focal_length));
-    p.half_w = 0.5f * (float)cfg->width; p.half_h = 0.5f * (float)cfg->height;
+    p.cam = pinhole_of(cfg, nullptr);                              // ENV origin: the kernel adds the env's ROVER_POS
     p.near_clip = cfg->near_clip; p.far_clip = cfg->far_clip;
     p.rgba = rgba; p.depth = depth; p.object_id = object_id;
-    const unsigned blocks = (unsigned)((p.tiles + WAVES - 1) / WAVES);
+    const unsigned blocks = (unsigned)((p.cam.tiles + WAVES - 1) / WAVES);
     hipLaunchKernelGGL(rover_viewer_render_kernel, dim3(blocks), dim3(TILE * TILE * WAVES), 0, st, p);
     HIP_TRY(hipGetLastError());
     return ROVER_OK;

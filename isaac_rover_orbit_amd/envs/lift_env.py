@@ -21,6 +21,7 @@ from .. import _lib
 from .._fused import stream
 from ..cfg import ViewerCfg
 from ._logdict import LogDict
+from ._viewer import ViewerMixin, resolve_render_mode
 from .rover_env import RLTaskEnv, _ptr, _spaces
 
 REWARD_ORDER = ["reaching_object", "lifting_object", "object_goal_tracking", "object_goal_tracking_fine_grained", "action_rate",
@@ -102,14 +103,6 @@ class _Managers:
     pass
 
 
-def resolve_render_mode(render_mode, kwargs: dict):
-    """``render_mode`` as the constructor honours it: the reference passes ``viewport=args_cli.video`` (train.py:123-125), which
-    means ``"rgb_array"``.  Pops ``viewport`` from ``kwargs``."""
-    if render_mode is None and kwargs.pop("viewport", False):
-        render_mode = "rgb_array"
-    return render_mode
-
-
 def lift_viewer_native(viewer: ViewerCfg, num_envs: int, env_spacing: float, ee_offset_z: float) -> "_lib.LiftViewerConfig":
     """``cfg.viewer`` (validated by ``ViewerCfg.validate``) plus the scene's spacing and the tool offset as the C struct."""
     base = viewer.to_native(num_envs)
@@ -122,7 +115,7 @@ def lift_viewer_native(viewer: ViewerCfg, num_envs: int, env_spacing: float, ee_
     return c
 
 
-class FrankaCubeLiftEnv(RLTaskEnv):
+class FrankaCubeLiftEnv(ViewerMixin, RLTaskEnv):
     """MI355X-native ``FrankaCubeLift-v0``.
 
     ``render_mode="rgb_array"`` (or the reference's ``viewport=True``): ``render()`` returns the (H, W, 3) uint8 frame of the camera
@@ -289,57 +282,20 @@ class FrankaCubeLiftEnv(RLTaskEnv):
                    "rover_lift_terms")
         return outs
 
-    def render(self):
-        """``"rgb_array"``: the (H, W, 3) uint8 frame of the current state (a numpy view of a host copy, as ORBIT returns
-        ``rgb_data[:, :, :3]``); otherwise None."""
-        if self.render_mode != "rgb_array":
-            return None
-        return self.render_rgb().cpu().numpy()[:, :, :3]
-
     def _viewer_native(self):
         return lift_viewer_native(self.cfg.viewer, self.num_envs, self.cfg.scene.env_spacing, self.cfg.ee_offset_z)
 
-    def _viewer_workspace(self, vc):
-        """The viewer's workspace (per-frame primitives of every env and the overflow list), allocated on the first render."""
-        if getattr(self, "_viewer_ws", None) is None:
-            nb = int(self._lib.rover_lift_viewer_workspace_bytes(self.num_envs, C.byref(vc)))
-            if nb == 0:
-                raise _lib.RoverHipError("rover_lift_viewer_workspace_bytes: invalid viewer config")
-            self._viewer_ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=self.device)
-            self._viewer_ws_bytes = nb
-            self._viewer_buf = []
-            self._viewer_cur = 0
-        return self._viewer_ws
-
-    def render_frame(self, depth: bool = False, object_id: bool = False):
-        """A fresh viewer frame of the current state in new device buffers: (rgba (H, W, 4) uint8, depth (H, W) fp32 or None,
-        object_id (H, W) int32 or None), asynchronous on the current stream."""
-        vc = self._viewer_native()
-        ws = self._viewer_workspace(vc)
-        h, w = vc.height, vc.width
-        rgba = torch.empty(h, w, 4, dtype=torch.uint8, device=self.device)
-        dep = torch.empty(h, w, dtype=torch.float32, device=self.device) if depth else None
-        ids = torch.empty(h, w, dtype=torch.int32, device=self.device) if object_id else None
-        self._viewer_render(vc, ws, rgba, dep, ids)
-        return rgba, dep, ids
+    def _viewer_bytes(self, vc):
+        """Bytes of the viewer's workspace (per-frame primitives of every env and the overflow list)."""
+        nb = int(self._lib.rover_lift_viewer_workspace_bytes(self.num_envs, C.byref(vc)))
+        if nb == 0:
+            raise _lib.RoverHipError("rover_lift_viewer_workspace_bytes: invalid viewer config")
+        return nb
 
     def _viewer_render(self, vc, ws, rgba, dep=None, ids=None):
         with torch.cuda.device(self.device):
             _lib.check(self._lib.rover_lift_viewer_render(_ptr(self.state), self.num_envs, C.byref(vc), _ptr(ws), self._viewer_ws_bytes,
                                                           _ptr(rgba), _ptr(dep), _ptr(ids), self._stream()), "rover_lift_viewer_render")
-
-    def render_rgb(self) -> torch.Tensor:
-        """The viewer frame of the current state as a device (H, W, 4) uint8 RGBA tensor, without a host synchronisation.  Two
-        buffers rotate, so the frame one call returns stays valid through the next call."""
-        vc = self._viewer_native()
-        ws = self._viewer_workspace(vc)
-        shape = (vc.height, vc.width, 4)
-        if not self._viewer_buf or tuple(self._viewer_buf[0].shape) != shape:
-            self._viewer_buf = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(2)]
-        self._viewer_cur ^= 1
-        buf = self._viewer_buf[self._viewer_cur]
-        self._viewer_render(vc, ws, buf)
-        return buf
 
     def get_state(self) -> torch.Tensor:
         return self.state.t().contiguous()

@@ -29,6 +29,7 @@ from .._fused import stream
 from ..cfg import OBS_ORDER, REWARD_ORDER, TERMINATION_ORDER, RoverEnvCfg
 from ..terrain import Terrain, make_flat_terrain, make_procedural_terrain
 from ._logdict import LogDict
+from ._viewer import ViewerMixin, resolve_render_mode
 
 try:  # gymnasium is what the reference uses (robots/aau_rover/__init__.py:3); optional here
     import gymnasium as gym
@@ -248,7 +249,7 @@ LOG_KEYS = ([f"Episode Reward/{k}" for k in REWARD_ORDER] + [f"Episode Terminati
             + ["Metrics/target_pose/error_pos", "Metrics/target_pose/error_heading"])
 
 
-class RoverEnv(RLTaskEnv):
+class RoverEnv(ViewerMixin, RLTaskEnv):
     """MI355X-native ``AAURoverEnv-v0``.  ``RoverEnv(cfg)`` / ``gym.make("AAURoverEnv-v0", cfg=cfg)``.
 
     ``render_mode="rgb_array"`` (or the reference's ``viewport=True``): ``render()`` returns the (H, W, 3) uint8 frame of the camera
@@ -256,8 +257,7 @@ class RoverEnv(RLTaskEnv):
     metadata = {"render_modes": [None, "rgb_array"]}
 
     def __init__(self, cfg: RoverEnvCfg | None = None, terrain: Terrain | None = None, render_mode=None, **kwargs):
-        if render_mode is None and kwargs.pop("viewport", False):
-            render_mode = "rgb_array"          # what the reference passes viewport=args_cli.video for (train.py:123-125)
+        render_mode = resolve_render_mode(render_mode, kwargs)
         if cfg is not None and not isinstance(cfg, RoverEnvCfg):
             # a reference-style cfg (the reference's AAURoverEnvCfg on ORBIT / compat configclasses): translate it
             from ..compat.convert import from_reference_cfg, is_reference_cfg
@@ -922,59 +922,23 @@ class RoverEnv(RLTaskEnv):
         self.obs_buf = self._obs_dicts[self._cur]
         return self.obs_buf
 
-    def render(self):
-        """``"rgb_array"``: the (H, W, 3) uint8 frame of the current state (a numpy view of a host copy, as ORBIT returns
-        ``rgb_data[:, :, :3]``); otherwise None."""
-        if self.render_mode != "rgb_array":
-            return None
-        return self.render_rgb().cpu().numpy()[:, :, :3]
-
     def _viewer_native(self):
         return self.cfg.viewer.to_native(self.num_envs)
 
-    def _viewer_workspace(self, vc):
-        """The viewer's workspace (terrain pyramid + per-frame bins), allocated and prepared on the first render."""
-        if getattr(self, "_viewer_ws", None) is None:
-            with torch.cuda.device(self.device):
-                nb = int(self._lib.rover_viewer_workspace_bytes(self._h, C.byref(vc)))
-                if nb == 0:
-                    raise _lib.RoverHipError("rover_viewer_workspace_bytes: no terrain bound or invalid viewer config")
-                ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=self.device)
-                _lib.check(self._lib.rover_viewer_prepare(self._h, C.byref(vc), _ptr(ws), nb, self._stream()), "rover_viewer_prepare")
-            self._viewer_ws = ws
-            self._viewer_buf = []
-            self._viewer_cur = 0
-        return self._viewer_ws
+    def _viewer_bytes(self, vc):
+        """Bytes of the viewer's workspace (terrain pyramid + per-frame bins)."""
+        nb = int(self._lib.rover_viewer_workspace_bytes(self._h, C.byref(vc)))
+        if nb == 0:
+            raise _lib.RoverHipError("rover_viewer_workspace_bytes: no terrain bound or invalid viewer config")
+        return nb
 
-    def render_frame(self, depth: bool = False, object_id: bool = False):
-        """A fresh viewer frame of the current state in new device buffers: (rgba (H, W, 4) uint8, depth (H, W) fp32 or None,
-        object_id (H, W) int32 or None), asynchronous on the current stream."""
-        vc = self._viewer_native()
-        ws = self._viewer_workspace(vc)
-        h, w = vc.height, vc.width
-        rgba = torch.empty(h, w, 4, dtype=torch.uint8, device=self.device)
-        dep = torch.empty(h, w, dtype=torch.float32, device=self.device) if depth else None
-        ids = torch.empty(h, w, dtype=torch.int32, device=self.device) if object_id else None
-        self._viewer_render(vc, ws, rgba, dep, ids)
-        return rgba, dep, ids
+    def _viewer_prepare(self, vc, ws, nb):
+        _lib.check(self._lib.rover_viewer_prepare(self._h, C.byref(vc), _ptr(ws), nb, self._stream()), "rover_viewer_prepare")
 
     def _viewer_render(self, vc, ws, rgba, dep=None, ids=None):
         with torch.cuda.device(self.device):
             _lib.check(self._lib.rover_viewer_render(self._h, C.byref(vc), _ptr(ws), _ptr(rgba), _ptr(dep), _ptr(ids),
                                                      self._stream()), "rover_viewer_render")
-
-    def render_rgb(self) -> torch.Tensor:
-        """The viewer frame of the current state as a device (H, W, 4) uint8 RGBA tensor, without a host synchronisation.  Two
-        buffers rotate, so the frame one call returns stays valid through the next call."""
-        vc = self._viewer_native()
-        ws = self._viewer_workspace(vc)
-        shape = (vc.height, vc.width, 4)
-        if not self._viewer_buf or tuple(self._viewer_buf[0].shape) != shape:
-            self._viewer_buf = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(2)]
-        self._viewer_cur ^= 1
-        buf = self._viewer_buf[self._viewer_cur]
-        self._viewer_render(vc, ws, buf)
-        return buf
 
     def close(self):
         if not self._closed and getattr(self, "_h", None):

@@ -10,6 +10,7 @@ Comparison rule (kernel vs reference, per pixel) -- the rule of test_gpu_viewer.
 """
 import ctypes as C
 import dataclasses
+import math
 import os
 import time
 
@@ -299,3 +300,28 @@ def test_4096_envs_world_view():
     assert len(np.unique((ids[ids >= lr.ID_ENV0] - lr.ID_ENV0) // lr.IDS_PER_ENV)) > 1       # more than one env is visible
     assert (rgba.cpu().numpy()[..., 3] == 255).all()
     env.close()
+
+
+def test_one_camera_with_the_rover_viewer():
+    """The two renderers agree on the camera, the sky and the packing: an all-sky view (the eye 5 m up, every ray at least 40 deg
+    above the horizon, nothing either scene draws reaches z = 5) is the same bytes from both and is viewer_reference's sky formula,
+    at sizes with one pixel, a whole tile and ragged tiles in either direction."""
+    import test_gpu_viewer as rover
+    import viewer_reference as vr
+    eye, lookat = (0.0, 0.0, 5.0), (1.0, 0.0, 9.0)
+    lift = _env(1)
+    lift.reset()
+    rov = rover._env(rover._terrain("flat", (64, 64)), 1)
+    rov.reset()
+    for w, h in ((1, 1), (8, 8), (9, 5), (17, 3)):
+        lift.cfg.viewer = rov.cfg.viewer = ViewerCfg(eye=eye, lookat=lookat, resolution=(w, h))
+        la, ld, li = _frame(lift)
+        ra, rd, ri = (t.cpu().numpy() for t in rov.render_frame(depth=True, object_id=True))
+        d = vr.camera_rays(eye, lookat, w, h)
+        assert d[..., 2].min() > math.sin(math.radians(40.0))
+        sky = np.asarray(vr.SKY_HORIZON) + (np.asarray(vr.SKY_ZENITH) - np.asarray(vr.SKY_HORIZON)) * np.maximum(d[..., 2:3], 0.0)
+        assert la.shape == (h, w, 4) and la.tobytes() == ra.tobytes(), f"{w} x {h}"
+        assert np.array_equal(la[..., :3], vr._byte(sky)) and (la[..., 3] == 255).all(), f"{w} x {h}"
+        assert np.isposinf(ld).all() and np.isposinf(rd).all() and not li.any() and not ri.any(), f"{w} x {h}"
+    lift.close()
+    rov.close()

@@ -265,3 +265,16 @@ def test_record_video_needs_rgb_array(tmp_path):
     env.render_mode = None
     with pytest.raises(ValueError):
         _MiniGym().wrappers.RecordVideo(env, video_folder=str(tmp_path))
+
+
+def test_the_envs_share_one_viewer_host_path():
+    """Both envs take render / render_frame / render_rgb and the viewport switch from envs/_viewer.py, and the lift's C config
+    begins with the rover's (lift_viewer_native copies it member by member)."""
+    from isaac_rover_orbit_amd import _lib
+    from isaac_rover_orbit_amd.envs import _viewer, lift_env, rover_env
+    for name in ("render", "render_frame", "render_rgb"):
+        shared = getattr(_viewer.ViewerMixin, name)
+        assert getattr(rover_env.RoverEnv, name) is shared and getattr(lift_env.FrankaCubeLiftEnv, name) is shared
+    assert lift_env.resolve_render_mode is _viewer.resolve_render_mode is rover_env.resolve_render_mode
+    base = _lib.ViewerConfig._fields_
+    assert _lib.LiftViewerConfig._fields_[:len(base)] == base
