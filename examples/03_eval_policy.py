@@ -9,6 +9,12 @@
 only, through the sensor model of ``--depth_range`` / ``--depth_sigma`` / ``--depth_dropout``:
 
     python examples/03_eval_policy.py --checkpoint best_agent.pt --scan_source elevation --depth_range 0.3 8 --depth_dropout 0.01 0.4
+
+``--map_source lidar`` builds that map from a scanning lidar on the mast instead (``RoverEnvCfg.lidar``, ``ElevationMapCfg.source``):
+it sees all round, so the printed known share of the scan is close to 1 from the first frame on where the camera's stays low:
+
+    python examples/03_eval_policy.py --checkpoint best_agent.pt --scan_source elevation --map_source lidar --lidar_channels 64 \
+        --lidar_vfov -85 -20 --lidar_hres 1.5
 """
 import argparse
 import os
@@ -37,16 +43,27 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--depth_dropout", type=float, nargs=2, default=None, metavar=("P", "P_EDGE"),
                     help="probability that a pixel loses its data, off and on a depth edge")
     ap.add_argument("--map_alpha", type=float, default=1.0, help="weight of the newest frame on a cell the map already knows")
+    ap.add_argument("--map_source", choices=("camera", "lidar"), default="camera",
+                    help="the sensor that feeds the elevation map: the depth camera, or a scanning lidar on the mast")
+    ap.add_argument("--lidar_channels", type=int, default=32, help="rings of the lidar")
+    ap.add_argument("--lidar_vfov", type=float, nargs=2, default=(-60.0, -10.0), metavar=("LO", "HI"),
+                    help="elevation angles of the lowest and the highest ring (degrees)")
+    ap.add_argument("--lidar_hres", type=float, default=2.0, help="degrees of azimuth between two rays of a ring")
     return ap
 
 
 def make_cfg(args) -> RoverEnvCfg:
     """The env cfg of the flags: with ``--scan_source elevation`` the camera, its sensor model (None without a --depth_* flag) and
-    the map; otherwise exactly the default."""
+    the map -- or, with ``--map_source lidar``, the lidar of the ``--lidar_*`` flags and the map behind it; otherwise exactly the
+    default."""
     cfg = RoverEnvCfg()
     cfg.scene.num_envs = args.num_envs
     cfg.terrain.kind = "custom"
-    if args.scan_source == "elevation":
+    if args.scan_source == "elevation" and args.map_source == "lidar":
+        from isaac_rover_orbit_amd.cfg import ElevationMapCfg, LidarCfg
+        cfg.lidar = LidarCfg(channels=args.lidar_channels, vertical_fov_range=tuple(args.lidar_vfov), horizontal_res=args.lidar_hres)
+        cfg.elevation = ElevationMapCfg(alpha=args.map_alpha, source="lidar")
+    elif args.scan_source == "elevation":
         from isaac_rover_orbit_amd.cfg import CameraCfg, DepthSensorCfg, ElevationMapCfg
         cfg.camera = CameraCfg()
         if any(v is not None for v in (args.depth_range, args.depth_sigma, args.depth_dropout)):

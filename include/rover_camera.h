@@ -48,7 +48,9 @@ size_t rover_camera_config_bytes(void);
 size_t rover_camera_workspace_bytes(const struct rover_sim *sim, const rover_camera_config *cfg);
 
 /* Build the max-height pyramid of the terrain currently bound to `sim` into `ws` (`bytes` >= rover_camera_workspace_bytes).
- * Call again after every rover_set_terrain* on `sim`.  Replaces the scene set-up of rover_camera_env.py:58-71. */
+ * Call again after every rover_set_terrain* on `sim`.  Replaces the scene set-up of rover_camera_env.py:58-71.
+ * rover_lidar_prepare (rover_lidar.h) builds the same pyramid and writes the same record in the handle: one prepared workspace
+ * serves rover_camera_render and rover_lidar_cast alike, whichever call prepared it, and the last prepare wins. */
 int rover_camera_prepare(struct rover_sim *sim, const rover_camera_config *cfg, void *ws, size_t bytes, void *stream);
 
 /* depth (num_envs, height, width) fp32, row-major: Euclidean distance from the optical centre to the first hit of each pixel's

@@ -25,8 +25,8 @@
  *     uniform   column c takes word c % 4: u = ((w >> 9) + 0.5) * 2^-23
  *     gaussian  words (0, 1) give columns 4 q (cosine branch) and 4 q + 1 (sine branch) by Box-Muller, words (2, 3) give
  *               4 q + 2 and 4 q + 3: rho = sqrtf(-2 logf(u(w_a))), (e_cos, e_sin) = rho * sincospif(2 u(w_b))
- * Tags: ROVER_OBS_POST_STREAM_ROW for observation rows, ROVER_OBS_POST_STREAM_DEPTH for depth images; neither shares its high half
- * with another draw of this library.  There is no state: the caller's (seed, env_id_offset, counter) is the checkpoint.
+ * Tags: ROVER_OBS_POST_STREAM_ROW for observation rows, ROVER_OBS_POST_STREAM_DEPTH for depth images (and rover_lidar.h's
+ * ROVER_LIDAR_STREAM_NOISE for lidar frames); none shares its high half with another draw of this library.  There is no state: the caller's (seed, env_id_offset, counter) is the checkpoint.
  *
  * Conventions as in rover_scaler.h: plain C, caller-owned DEVICE buffers, int return codes (ROVER_ERR_INVALID for a bad argument,
  * with no launch), rover_last_error() for the text, asynchronous on `stream` and run on the device `rows` lives on.  No

@@ -77,6 +77,7 @@ EXPORTS = [
     "rover_obs_post_segment_bytes", "rover_obs_post_apply",  # rover_obs_post.h
     "rover_depth_sensor_cfg_bytes", "rover_depth_sensor_apply",  # rover_depth_sensor.h
     "rover_elevation_cfg_bytes", "rover_elevation_step", "rover_elevation_scan",  # rover_elevation.h
+    "rover_lidar_config_bytes", "rover_lidar_workspace_bytes", "rover_lidar_prepare", "rover_lidar_cast",  # rover_lidar.h
 ]
 POLICY_MAX_LAYERS = 8
 ACT_NONE, ACT_LEAKY_RELU, ACT_TANH, ACT_ELU = 0, 1, 2, 3
@@ -260,10 +261,11 @@ def scaler_workspace_bytes(width: int, max_rows: int) -> int:
 OBS_POST_MAX_SEGMENTS, OBS_POST_MAX_WIDTH = 8, 262144
 OBS_POST_NONE, OBS_POST_UNIFORM, OBS_POST_GAUSSIAN, OBS_POST_CONSTANT = 0, 1, 2, 3
 # Word 3 of the Philox counter of the post-processing draws: the HIGH HALF names the stream ("OP": observation rows, "OD": depth
-# images), the low half carries the column quad.  td3_explore.TAGS is the table of the streams named by their upper 24 bits; these
-# two are checked against it by tests/test_obs_post.py.
+# images, "OL": lidar frames), the low half carries the column quad.  td3_explore.TAGS is the table of the streams named by their
+# upper 24 bits; the first two are checked against it by tests/test_obs_post.py, the lidar's by tests/test_lidar.py.
 OBS_POST_STREAM_ROW = 0x4F500000
 OBS_POST_STREAM_DEPTH = 0x4F440000
+OBS_POST_STREAM_LIDAR = 0x4F4C0000     # "OL": lidar frames (ROVER_LIDAR_STREAM_NOISE, include/rover_lidar.h)
 
 
 class ObsPostSegment(C.Structure):
@@ -294,6 +296,12 @@ class ElevationCfg(C.Structure):
     _fields_ = [("cell", C.c_float), ("inv_cell", C.c_float), ("grid", C.c_int32), ("range_min", C.c_float),
                 ("range_max", C.c_float), ("alpha", C.c_float), ("mount_pos", C.c_float * 3), ("height_offset", C.c_float),
                 ("unknown_value", C.c_float)]
+
+
+class LidarConfig(C.Structure):
+    """Mirror of ``struct rover_lidar_config`` (include/rover_lidar.h)."""
+    _fields_ = [("rays", C.c_int32), ("mount_pos", C.c_float * 3), ("near_clip", C.c_float), ("far_clip", C.c_float),
+                ("attach_yaw_only", C.c_int32)]
 
 
 class RoverHipError(RuntimeError):
@@ -392,7 +400,7 @@ _MIRRORS = [("rover_config_bytes", RoverConfig), ("rover_lift_config_bytes", Lif
             ("rover_trace_stream_bytes", TraceStream), ("rover_lift_viewer_config_bytes", LiftViewerConfig),
             ("rover_dagger_hparams_bytes", DaggerHparams), ("rover_dagger_state_bytes", DaggerState),
             ("rover_obs_post_segment_bytes", ObsPostSegment), ("rover_depth_sensor_cfg_bytes", DepthSensorCfg),
-            ("rover_elevation_cfg_bytes", ElevationCfg)]
+            ("rover_elevation_cfg_bytes", ElevationCfg), ("rover_lidar_config_bytes", LidarConfig)]
 
 
 def load():
@@ -661,6 +669,11 @@ def load():
                                          vp, vp, vp, i32, vp, i32, vp, C.c_int64, vp, vp, i32, vp]
     lib.rover_elevation_scan.argtypes = [C.POINTER(ElevationCfg), vp, vp, C.c_int64, C.c_int64, vp, vp, vp, i32, vp, i32, vp,
                                          C.c_int64, vp, vp, i32, vp]
+    lib.rover_lidar_config_bytes.restype = C.c_size_t
+    lib.rover_lidar_workspace_bytes.argtypes = [vp]
+    lib.rover_lidar_workspace_bytes.restype = C.c_size_t
+    lib.rover_lidar_prepare.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.rover_lidar_cast.argtypes = [vp, C.POINTER(LidarConfig), vp, vp, vp, C.c_int64, vp, vp]
     lib.rover_last_error.restype = C.c_char_p
     lib.rover_version.restype = C.c_char_p
     for name in EXPORTS:

@@ -20,7 +20,7 @@ SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("rover_kernels.hip", "terrain
                                                             "lift_viewer_kernels.hip", "dagger_kernels.hip",
                                                             "dagger_collect_kernels.hip", "dagger_conv_kernels.hip",
                                                             "obs_post_kernels.hip", "depth_sensor_kernels.hip",
-                                                            "elevation_kernels.hip")]
+                                                            "elevation_kernels.hip", "lidar_kernels.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "rover_model.hpp"), os.path.join(_PKG, "csrc", "rover_internal.hpp"),
            os.path.join(_PKG, "csrc", "terrain_march.hpp"), os.path.join(_PKG, "csrc", "rover_render.hpp"),
            os.path.join(_PKG, "csrc", "td3_actor_tile.hpp"), os.path.join(_PKG, "csrc", "offpolicy_net.hpp"),
@@ -55,7 +55,8 @@ HEADERS = [os.path.join(_PKG, "csrc", "rover_model.hpp"), os.path.join(_PKG, "cs
            os.path.join(os.path.dirname(_PKG), "include", "rover_dagger_conv.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_obs_post.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_depth_sensor.h"),
-           os.path.join(os.path.dirname(_PKG), "include", "rover_elevation.h")]
+           os.path.join(os.path.dirname(_PKG), "include", "rover_elevation.h"),
+           os.path.join(os.path.dirname(_PKG), "include", "rover_lidar.h")]
 OBJ_DIR = os.path.join(os.path.dirname(_PKG), "build", "obj")
 OUTPUT = os.path.join(_PKG, "librover_hip.so")
 # fp32 parity with the CPU oracle: no contraction, no fast-math (correctly rounded div / sqrt are hipcc defaults)

@@ -171,10 +171,14 @@ class ElevationMapCfg:
     range_max: float = 5.0
     alpha: float = 1.0                                 # 1 = the newest frame replaces a cell's height
     unknown_value: float = 0.0
+    # which sensor feeds the map: "camera" (cfg.camera's depth image) or "lidar" (cfg.lidar's range frame; full attitude only)
+    source: str = "camera"
 
     def check(self):
         """ValueError for what the library refuses, on the values as the fp32 struct holds them."""
         f32 = lambda x: C.c_float(float(x)).value      # noqa: E731
+        if self.source not in ("camera", "lidar"):
+            raise ValueError("elevation source must be 'camera' or 'lidar'")
         g = int(self.grid)
         if g != self.grid or g < _lib.ELEVATION_MIN_GRID or g > _lib.ELEVATION_MAX_GRID or g & (g - 1):
             raise ValueError(f"elevation grid must be a power of two in [{_lib.ELEVATION_MIN_GRID}, {_lib.ELEVATION_MAX_GRID}]")
@@ -278,6 +282,82 @@ class CameraCfg:
         for i in range(4):
             c.mount_quat[i] = self.orientation[i]
         c.near_clip, c.far_clip = self.near_clip, self.far_clip
+        return c
+
+
+@dataclass
+class LidarCfg:
+    """A scanning lidar on the Body link in the vocabulary of ORBIT's ``patterns.LidarPatternCfg`` (include/rover_lidar.h,
+    lidar.py): ``channels`` rings between the two ``vertical_fov_range`` angles (inclusive), each with one ray every
+    ``horizontal_res`` degrees from ``horizontal_fov_range[0]`` on; the end of the span is left out when the span is a full circle
+    and kept otherwise.  The default pattern is a free choice (a downward fan that covers the policy's 3 m x 3 m scan from the
+    mast), not a particular instrument."""
+    channels: int = 32
+    vertical_fov_range: tuple = (-60.0, -10.0)         # degrees, elevation above the sensor's x-y plane
+    horizontal_fov_range: tuple = (-180.0, 180.0)      # degrees, azimuth about the sensor's +z, 0 = +x
+    horizontal_res: float = 2.0                        # degrees
+    position: tuple = CameraCfg.position               # m, Body frame: the camera's mast
+    orientation: tuple = (1.0, 0.0, 0.0, 0.0)          # (w, x, y, z) Body <- sensor; folded into the ray table
+    near_clip: float = 0.0                             # m
+    max_distance: float = 100.0                        # m, ORBIT's RayCasterCfg.max_distance; may be inf
+    attach_yaw_only: bool = False                      # the table turns with the yaw frame only (ORBIT's RayCasterCfg switch)
+    every_n_steps: int = 1                             # cast on steps with common_step_counter % every_n_steps == 0
+    hits: bool = False                                 # extras["lidar_hits_w"]: ORBIT's ray_hits_w
+    # noise on the ranges, then a clip (obs_post.py under the lidar's own stream tag, draws keyed as the camera's); both None =
+    # the ranges as cast, nothing launched.  Misses stay +inf unless a clip brings them to its upper bound.
+    noise: Any = None
+    clip: Any = None
+
+    @property
+    def azimuth_angles(self) -> list:
+        """The azimuths of one ring in degrees (float64): h0 + res * k."""
+        h0, h1, res = float(self.horizontal_fov_range[0]), float(self.horizontal_fov_range[1]), float(self.horizontal_res)
+        if not (math.isfinite(h0) and math.isfinite(h1) and math.isfinite(res) and res > 0.0 and h1 >= h0):
+            raise ValueError("lidar horizontal_fov_range must be finite with min <= max and horizontal_res finite and > 0")
+        n = int(math.floor((h1 - h0) / res + 1e-9)) + 1
+        full = abs((h1 - h0) - 360.0) < 1e-9
+        return [h0 + res * k for k in range(n) if not (full and h0 + res * k >= h1 - 1e-9)]
+
+    @property
+    def azimuths(self) -> int:
+        return len(self.azimuth_angles)
+
+    @property
+    def rays(self) -> int:
+        return int(self.channels) * self.azimuths
+
+    def validate(self):
+        """The checks of rover_lidar_cast (lidar_kernels.hip), on the values as the fp32 struct holds them."""
+        f32 = lambda x: C.c_float(float(x)).value      # noqa: E731
+        if int(self.channels) != self.channels or int(self.channels) < 1:
+            raise ValueError("lidar channels must be an integer >= 1")
+        if len(tuple(self.vertical_fov_range)) != 2 or not all(math.isfinite(float(v)) for v in self.vertical_fov_range):
+            raise ValueError("lidar vertical_fov_range must be two finite angles")
+        if self.rays < 1 or self.rays > 0x7FFFFFFF:
+            raise ValueError("the lidar pattern must hold at least one ray")
+        if len(tuple(self.position)) != 3 or not all(math.isfinite(f32(v)) for v in self.position):
+            raise ValueError("lidar position must be three finite values")
+        if len(tuple(self.orientation)) != 4 or not all(math.isfinite(float(q)) for q in self.orientation) or \
+                not any(float(q) != 0.0 for q in self.orientation):
+            raise ValueError("lidar orientation must be a finite, non-zero (w, x, y, z) quaternion")
+        if not (0 <= f32(self.near_clip) < f32(self.max_distance)):
+            raise ValueError("lidar range must satisfy 0 <= near_clip < max_distance (max_distance may be inf)")
+        if int(self.every_n_steps) < 1:
+            raise ValueError("lidar every_n_steps must be >= 1")
+        if self.noise is not None or self.clip is not None:
+            from .obs_post import lidar_segments
+            if self.rays > _lib.OBS_POST_MAX_WIDTH:
+                raise ValueError(f"lidar noise / clip need at most {_lib.OBS_POST_MAX_WIDTH} rays")
+            lidar_segments(self)                       # ValueError for a noise object or clip the kernel cannot run
+
+    def to_native(self) -> "_lib.LidarConfig":
+        self.validate()
+        c = _lib.LidarConfig()
+        c.rays = self.rays
+        for i in range(3):
+            c.mount_pos[i] = self.position[i]
+        c.near_clip, c.far_clip = self.near_clip, self.max_distance
+        c.attach_yaw_only = 1 if self.attach_yaw_only else 0
         return c
 
 
@@ -424,6 +504,9 @@ class RoverEnvCfg:
     # a rolling elevation map fed by the camera (elevation.py): None = no map, nothing launched.  With one, extras["elevation_scan"]
     # is the height scan read out of the map, beside extras["elevation_known"] and extras["elevation_count"]
     elevation: ElevationMapCfg | None = None
+    # a scanning lidar (lidar.py): None = no lidar, no key, buffer or launch.  With one, extras["lidar_range"] is the
+    # (num_envs, channels, azimuths) range frame, +inf on a miss; cfg.elevation.source = "lidar" builds the map from it
+    lidar: LidarCfg | None = None
     # the rgb_array viewer's camera (render_mode="rgb_array"): ORBIT's ViewerCfg defaults
     viewer: ViewerCfg = field(default_factory=ViewerCfg)
 
@@ -471,7 +554,22 @@ class RoverEnvCfg:
             raise ValueError("simple_heading=True is not supported (the reference cfg uses False, rover_env_cfg.py:195)")
         if self.camera is not None:
             self.camera.validate()
-        if self.elevation is not None:
+        if self.lidar is not None:
+            self.lidar.validate()
+        if self.elevation is not None and self.elevation.source not in ("camera", "lidar"):
+            raise ValueError("elevation source must be 'camera' or 'lidar'")
+        if self.elevation is not None and self.elevation.source == "lidar":
+            if self.lidar is None:
+                raise ValueError("cfg.elevation.source = 'lidar' needs cfg.lidar: the map is built from the range frame")
+            if self.lidar.attach_yaw_only:
+                raise ValueError("an elevation map from the lidar needs attach_yaw_only = False: the map unprojects with the full attitude")
+            if self.lidar.rays > _lib.ELEVATION_MAX_PIXELS:
+                raise ValueError(f"an elevation map needs at most {_lib.ELEVATION_MAX_PIXELS} lidar rays")
+            nx, ny = self.height_scanner.grid
+            if nx * ny > _lib.ELEVATION_MAX_RAYS:
+                raise ValueError(f"an elevation map needs at most {_lib.ELEVATION_MAX_RAYS} scan rays")
+            self.elevation.to_native(self.lidar.position, self.height_scanner.height_offset)
+        elif self.elevation is not None:
             if self.camera is None:
                 raise ValueError("cfg.elevation needs cfg.camera: the map is built from the depth image")
             if int(self.camera.width) * int(self.camera.height) > _lib.ELEVATION_MAX_PIXELS:

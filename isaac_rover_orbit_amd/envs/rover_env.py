@@ -431,7 +431,10 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
         self._elevation = None
         for key in ("elevation_scan", "elevation_known", "elevation_count"):
             self.extras.pop(key, None)
+        # cfg.elevation.source = "lidar": the map hangs behind the lidar's cast (_init_lidar), the camera chain leaves it alone
+        self._elev_from_lidar = self.cfg.elevation is not None and getattr(self.cfg.elevation, "source", "camera") == "lidar"
         if cam is None:
+            self._init_lidar()
             return
         self._camera_cfg = cam.to_native()
         self._camera_every = int(cam.every_n_steps)
@@ -458,18 +461,88 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
         self.extras["rgb"] = None          # what the reference's listener reports without RGB data (rover_camera_env.py:94-98)
         if self._depth_sensor is not None:
             self.extras["depth_valid"] = self._depth_valid[0]
-        if self.cfg.elevation is not None:                     # the rolling elevation map: one launch behind the camera chain
+        if self.cfg.elevation is not None and not self._elev_from_lidar:   # the rolling elevation map: one launch behind the camera chain
             from ..elevation import ElevationMap
-            em = self._elevation = ElevationMap(self.cfg.elevation, cam, self.cfg.height_scanner, self.num_envs, self.device)
-            with torch.cuda.device(self.device):
-                self._elev_out = [(torch.full((self.num_envs, em.columns), float(self.cfg.elevation.unknown_value),
-                                              dtype=torch.float32, device=self.device),
-                                   torch.zeros((self.num_envs, em.columns), dtype=torch.uint8, device=self.device),
-                                   torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)) for _ in range(self._nbuf)]
-                self._elev_mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
-            self._elev_cur = 0
-            self._elev_pose = (self.state[_lib.POS:_lib.POS + 3].t(), self.state[_lib.QUAT:_lib.QUAT + 4].t())
-            self.extras["elevation_scan"], self.extras["elevation_known"], self.extras["elevation_count"] = self._elev_out[0]
+            self._init_elevation(ElevationMap(self.cfg.elevation, cam, self.cfg.height_scanner, self.num_envs, self.device))
+        self._init_lidar()
+
+    def _init_elevation(self, em):
+        """The map's rotating output sets, the reset mask and the pose views of ``em``, whichever sensor feeds it."""
+        self._elevation = em
+        with torch.cuda.device(self.device):
+            self._elev_out = [(torch.full((self.num_envs, em.columns), float(self.cfg.elevation.unknown_value),
+                                          dtype=torch.float32, device=self.device),
+                               torch.zeros((self.num_envs, em.columns), dtype=torch.uint8, device=self.device),
+                               torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)) for _ in range(self._nbuf)]
+            self._elev_mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
+        self._elev_cur = 0
+        self._elev_pose = (self.state[_lib.POS:_lib.POS + 3].t(), self.state[_lib.QUAT:_lib.QUAT + 4].t())
+        self.extras["elevation_scan"], self.extras["elevation_known"], self.extras["elevation_count"] = self._elev_out[0]
+
+    def _init_lidar(self):
+        """``cfg.lidar``: the ray table, the workspace (the camera's where there is one: the pyramid is built once) and two range
+        buffers that rotate like the depth buffers; with ``cfg.elevation.source = "lidar"`` the elevation map behind them."""
+        lid = getattr(self.cfg, "lidar", None)
+        self._lidar = None
+        self._lidar_post = None
+        self.extras.pop("lidar_range", None)
+        self.extras.pop("lidar_hits_w", None)
+        if lid is None:
+            return
+        from ..lidar import Lidar, elevation_geometry
+        self._lidar = Lidar(lid, self, workspace=self._camera_ws if self._camera_cfg is not None else None)
+        if self._lidar.workspace is None:
+            self._lidar.prepare()
+        self._lidar_every = int(lid.every_n_steps)
+        if lid.noise is not None or lid.clip is not None:      # range noise / clip: one launch behind every cast
+            from ..obs_post import LIDAR_TAG, ObsPost, lidar_segments
+            self._lidar_post = ObsPost(lidar_segments(lid), self._lidar.rays, seed=int(self.cfg.seed),
+                                       env_id_offset=int(self.cfg.env_id_offset), tag=LIDAR_TAG)
+        n, L = self.num_envs, self._lidar
+        with torch.cuda.device(self.device):
+            self._lidar_range = [torch.full((n, L.channels, L.azimuths), float("inf"), dtype=torch.float32, device=self.device)
+                                 for _ in range(self._nbuf)]
+            self._lidar_hits = [torch.full((n, L.rays, 3), float("inf"), dtype=torch.float32, device=self.device)
+                                for _ in range(self._nbuf)] if lid.hits else None
+        self._lidar_cur = 0
+        self.extras["lidar_range"] = self._lidar_range[0]
+        if lid.hits:
+            self.extras["lidar_hits_w"] = self._lidar_hits[0]
+        if self._elev_from_lidar:                              # the map: one launch behind the lidar chain, fed the lidar's own table
+            from ..elevation import ElevationMap
+            self._init_elevation(ElevationMap(self.cfg.elevation, elevation_geometry(lid), self.cfg.height_scanner, self.num_envs,
+                                              self.device, rays=L._rays32))
+
+    def _cast_into(self, buf: torch.Tensor, hits: torch.Tensor | None = None):
+        """The lidar frame of the current state into the (N, channels, azimuths) ``buf``, then ``cfg.lidar``'s noise and clip in
+        place, the draws keyed by the call counter of the launch that left the state (as the camera's)."""
+        self._lidar.cast(buf, hits)
+        if self._lidar_post is not None:
+            self._lidar_post.apply(buf, self._launch_counter())
+
+    def _lidar_update(self, force: bool = False, reset=(None, None)):
+        """Cast from the pose the step (or reset) left behind into the next range buffer.  With ``cfg.elevation.source = "lidar"``
+        the map is then updated on every call, without a frame on a step that casts nothing."""
+        buf = None
+        if force or self.common_step_counter % self._lidar_every == 0:
+            self._lidar_cur = (self._lidar_cur + 1) % self._nbuf
+            buf = self._lidar_range[self._lidar_cur]
+            hits = None if self._lidar_hits is None else self._lidar_hits[self._lidar_cur]
+            self._cast_into(buf, hits)
+            self.extras["lidar_range"] = buf
+            if hits is not None:
+                self.extras["lidar_hits_w"] = hits
+        if self._elev_from_lidar:
+            self._elevation_update(buf, reset)
+
+    def cast_lidar(self) -> torch.Tensor:
+        """A fresh lidar frame of the current state, (num_envs, channels, azimuths) fp32 in a new buffer.  With ``cfg.lidar.noise``
+        a re-cast of the same state repeats its noise (the draws are keyed by the call counter, not by the number of casts)."""
+        if self._lidar is None:
+            raise RuntimeError("cast_lidar needs a lidar (cfg.lidar)")
+        buf = torch.empty(self.num_envs, self._lidar.channels, self._lidar.azimuths, dtype=torch.float32, device=self.device)
+        self._cast_into(buf)
+        return buf
 
     def _render_into(self, buf: torch.Tensor, valid: torch.Tensor | None = None):
         """The depth image of the current state into the row-major (N, H, W) ``buf``, then ``cfg.camera``'s sensor model (its
@@ -485,11 +558,15 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
     def _camera_update(self, force: bool = False, reset=(None, None)):
         """Render the pose the step (or reset) left behind into the next depth buffer: extras["depth"] is its (N, W, H) view.
         With ``cfg.elevation`` the map is then updated on every call, without a frame on a step that renders nothing; ``reset``:
-        the step's terminated and time-out buffers, whose envs start their maps over."""
+        the step's terminated and time-out buffers, whose envs start their maps over.  ``cfg.lidar``'s chain runs first, on the
+        same occasions."""
+        if self._lidar is not None:                            # the lidar's chain (and the map, where the lidar feeds it)
+            self._lidar_update(force, reset)
         if self._camera_cfg is None:
             return
+        elevation = None if self._elev_from_lidar else self._elevation
         if not (force or self.common_step_counter % self._camera_every == 0):
-            if self._elevation is not None:
+            if elevation is not None:
                 self._elevation_update(None, reset)
             return
         self._depth_cur = (self._depth_cur + 1) % self._nbuf
@@ -500,7 +577,7 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
             self._render_into(buf, self._depth_valid[self._depth_cur])
             self.extras["depth_valid"] = self._depth_valid[self._depth_cur]
         self.extras["depth"] = buf.permute(0, 2, 1)
-        if self._elevation is not None:
+        if elevation is not None:
             self._elevation_update(buf, reset)
 
     def _elevation_update(self, depth, reset):
@@ -570,7 +647,8 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
             self._native_cfg.seed_lo, self._native_cfg.seed_hi = lo, hi
             _lib.check(self._lib.rover_set_seed(self._h, lo, hi), "rover_set_seed")
             self._obs_gen.manual_seed(seed)      # the observation-noise draws of plain (non-ORBIT) noise objects
-            for post in (self._obs_fused, getattr(self, "_depth_post", None), getattr(self, "_depth_sensor", None)):
+            for post in (self._obs_fused, getattr(self, "_depth_post", None), getattr(self, "_depth_sensor", None),
+                         getattr(self, "_lidar_post", None)):
                 if post is not None:             # the fused backend's draws are keyed by the same seed
                     post.seed = seed
         return int(self.cfg.seed)
@@ -619,6 +697,8 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
         if self._elevation is not None:                   # the masked envs' maps start over with a frame of their new pose
             self._elev_mask.fill_(1) if mask_d is None else self._elev_mask.copy_(mask_d)
             self._camera_update(force=True, reset=(self._elev_mask, None))
+        elif self._lidar is not None:                     # a frame of the poses the masked envs were reset to
+            self._lidar_update(force=True)
         return self.obs_buf, self.extras
 
     def _check_action(self, action: torch.Tensor) -> torch.Tensor:

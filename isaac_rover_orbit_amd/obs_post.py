@@ -24,6 +24,7 @@ from . import _fused, _lib
 from .rollout import philox4x32, rollout_counter, unit_uniform
 
 ROW_TAG, DEPTH_TAG = _lib.OBS_POST_STREAM_ROW, _lib.OBS_POST_STREAM_DEPTH
+LIDAR_TAG = _lib.OBS_POST_STREAM_LIDAR             # lidar frames (LidarCfg.noise / clip)
 NONE, UNIFORM, GAUSSIAN, CONSTANT = _lib.OBS_POST_NONE, _lib.OBS_POST_UNIFORM, _lib.OBS_POST_GAUSSIAN, _lib.OBS_POST_CONSTANT
 _MASK = 0xFFFFFFFF
 
@@ -82,6 +83,13 @@ def image_segments(camera) -> list:
     if camera.noise is None and camera.clip is None:
         return []
     return [segment(0, int(camera.height) * int(camera.width), noise=camera.noise, clip=camera.clip, what="camera")]
+
+
+def lidar_segments(lidar) -> list:
+    """``LidarCfg.noise`` / ``LidarCfg.clip`` as one segment over the frame's rays; empty when both are None."""
+    if lidar.noise is None and lidar.clip is None:
+        return []
+    return [segment(0, int(lidar.rays), noise=lidar.noise, clip=lidar.clip, what="lidar")]
 
 
 # ------------------------------------------------------------------------------------------------------------------ the draws (spec)
