@@ -48,6 +48,28 @@ def holds(name: str, t, shape) -> None:
         raise ValueError(f"{name} must hold {shape} values")
 
 
+def layout_pitch(shape, stride, contiguous: bool, width: int, rows: int | None = None):
+    """The layout half of ``row_pitch``: the pitch of a tensor of this shape, strides and contiguity, or None where it is refused."""
+    if len(shape) < 2 or (rows is not None and shape[0] != rows):
+        return None
+    if len(shape) == 2 and shape[1] == width and stride[1] == 1 and (shape[0] == 1 or stride[0] >= width):
+        return stride[0] if shape[0] > 1 else width
+    return width if contiguous and math.prod(shape) == shape[0] * width else None
+
+
+def row_pitch(name: str, t, width: int, rows: int | None = None, device=None) -> int:
+    """The row pitch, in floats, of a float32 cuda tensor that holds ``width`` consecutive values per row: 2-D ``(n, width)`` with
+    unit column stride and any pitch >= width (one row: any), or contiguous ``(n, ...)``; ``rows`` and ``device`` are checked where
+    given.  The one statement of the rule for the observation post-processing, the depth sensor, the elevation map and the lidar."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or (device is not None and t.device != device):
+        raise ValueError(f"{name} must be a float32 cuda tensor" + ("" if device is None else f" on {device}"))
+    pitch = layout_pitch(tuple(t.shape), t.stride(), t.is_contiguous(), width, rows)
+    if pitch is None:
+        raise ValueError(f"{name} must hold {width} consecutive values per row" + ("" if rows is None else f", {rows} rows")
+                         + ": (n, width) with unit column stride or contiguous (n, ...)")
+    return int(pitch)
+
+
 def check_tensor(t: torch.Tensor, name: str, dtype=torch.float32) -> None:
     if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
         raise ValueError(f"{name} must be a contiguous {dtype} cuda tensor")

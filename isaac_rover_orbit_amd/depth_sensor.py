@@ -134,14 +134,7 @@ class DepthSensor(_DepthSensorBase):
         return cls(native_cfg(camera), camera.height, camera.width, seed, env_id_offset)
 
     def _pitch(self, t: torch.Tensor, name: str) -> int:
-        hw = self.pixels
-        if not t.is_cuda or t.dtype != torch.float32 or t.dim() < 2:
-            raise ValueError(f"{name} must be a float32 cuda tensor of at least two dimensions")
-        if t.dim() == 2 and t.shape[1] == hw and t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) >= hw):
-            return t.stride(0) if t.shape[0] > 1 else hw
-        if t.is_contiguous() and t.numel() == t.shape[0] * hw:
-            return hw
-        raise ValueError(f"{name} must hold {hw} consecutive values per image")
+        return _fused.row_pitch(name, t, self.pixels)
 
     def apply(self, buf: torch.Tensor, counter: int, out: torch.Tensor | None = None, valid_out: torch.Tensor | None = None):
         pitch = self._pitch(buf, "buf")

@@ -285,14 +285,8 @@ class ElevationMap(_ElevationBase):
 
     def _f32(self, t, name: str, cols: int):
         """(pointer, row pitch) of a float32 cuda ``(n, cols)`` tensor with unit column stride."""
-        n = self.num_envs
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.device != self.map.device:
-            raise ValueError(f"{name} must be a float32 cuda tensor on the map's device")
-        if t.dim() > 2 and t.is_contiguous() and t.shape[0] == n and t.numel() == n * cols:
-            return t.data_ptr(), cols
-        if t.dim() == 2 and tuple(t.shape) == (n, cols) and t.stride(1) == 1 and (n == 1 or t.stride(0) >= cols):
-            return t.data_ptr(), (t.stride(0) if n > 1 else cols)
-        raise ValueError(f"{name} must hold {cols} consecutive values per env, {n} envs")
+        pitch = _fused.row_pitch(name, t, cols, rows=self.num_envs, device=self.map.device)
+        return t.data_ptr(), pitch
 
     def _pose(self, pos, quat):
         n = self.num_envs

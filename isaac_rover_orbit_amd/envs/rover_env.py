@@ -29,6 +29,7 @@ from .._fused import stream
 from ..cfg import OBS_ORDER, REWARD_ORDER, TERMINATION_ORDER, RoverEnvCfg
 from ..terrain import Terrain, make_flat_terrain, make_procedural_terrain
 from ._logdict import LogDict
+from ._sensors import SensorRig
 from ._viewer import ViewerMixin, resolve_render_mode
 
 try:  # gymnasium is what the reference uses (robots/aau_rover/__init__.py:3); optional here
@@ -414,189 +415,20 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
         self.action_space = _spaces.Box(-np.inf, np.inf, (n, 2), np.float32)
         self._step_args = None
         self._closed = False
-        self._init_camera()
+        self.sensors = SensorRig.for_env(self)       # cfg.camera / cfg.lidar / cfg.elevation; inert without them
         if getattr(self.cfg, "roctx_markers", False):
             self.set_markers(True)
-
-    def _init_camera(self):
-        """``cfg.camera``: the workspace (max-height pyramid of the terrain, built here) and two depth buffers that rotate like
-        the observation buffers, so the image handed out by one render stays valid through the next."""
-        cam = self.cfg.camera
-        self._camera_cfg = None
-        self._depth_post = None
-        self._depth_sensor = None
-        self.extras.pop("depth", None)
-        self.extras.pop("rgb", None)
-        self.extras.pop("depth_valid", None)
-        self._elevation = None
-        for key in ("elevation_scan", "elevation_known", "elevation_count"):
-            self.extras.pop(key, None)
-        # cfg.elevation.source = "lidar": the map hangs behind the lidar's cast (_init_lidar), the camera chain leaves it alone
-        self._elev_from_lidar = self.cfg.elevation is not None and getattr(self.cfg.elevation, "source", "camera") == "lidar"
-        if cam is None:
-            self._init_lidar()
-            return
-        self._camera_cfg = cam.to_native()
-        self._camera_every = int(cam.every_n_steps)
-        if cam.sensor is not None:                             # the sensor model: one launch behind every render, ahead of noise / clip
-            from ..depth_sensor import DepthSensor
-            self._depth_sensor = DepthSensor.from_camera(cam, seed=int(self.cfg.seed), env_id_offset=int(self.cfg.env_id_offset))
-        if cam.noise is not None or cam.clip is not None:      # sensor noise / clip: one launch behind every render
-            from ..obs_post import DEPTH_TAG, ObsPost, image_segments
-            self._depth_post = ObsPost(image_segments(cam), int(cam.height) * int(cam.width), seed=int(self.cfg.seed),
-                                       env_id_offset=int(self.cfg.env_id_offset), tag=DEPTH_TAG)
-        with torch.cuda.device(self.device):
-            nb = int(self._lib.rover_camera_workspace_bytes(self._h, C.byref(self._camera_cfg)))
-            if nb == 0:
-                raise _lib.RoverHipError("rover_camera_workspace_bytes: no terrain bound or invalid camera config")
-            self._camera_ws = torch.zeros((nb + 3) // 4, dtype=torch.float32, device=self.device)
-            self._depth = [torch.full((self.num_envs, cam.height, cam.width), float("inf"), dtype=torch.float32, device=self.device)
-                           for _ in range(self._nbuf)]
-            if self._depth_sensor is not None:                 # each depth buffer's count of pixels that carry data
-                self._depth_valid = [torch.zeros(self.num_envs, dtype=torch.int32, device=self.device) for _ in range(self._nbuf)]
-            _lib.check(self._lib.rover_camera_prepare(self._h, C.byref(self._camera_cfg), _ptr(self._camera_ws), nb, self._stream()),
-                       "rover_camera_prepare")
-        self._depth_cur = 0
-        self.extras["depth"] = self._depth[0].permute(0, 2, 1)
-        self.extras["rgb"] = None          # what the reference's listener reports without RGB data (rover_camera_env.py:94-98)
-        if self._depth_sensor is not None:
-            self.extras["depth_valid"] = self._depth_valid[0]
-        if self.cfg.elevation is not None and not self._elev_from_lidar:   # the rolling elevation map: one launch behind the camera chain
-            from ..elevation import ElevationMap
-            self._init_elevation(ElevationMap(self.cfg.elevation, cam, self.cfg.height_scanner, self.num_envs, self.device))
-        self._init_lidar()
-
-    def _init_elevation(self, em):
-        """The map's rotating output sets, the reset mask and the pose views of ``em``, whichever sensor feeds it."""
-        self._elevation = em
-        with torch.cuda.device(self.device):
-            self._elev_out = [(torch.full((self.num_envs, em.columns), float(self.cfg.elevation.unknown_value),
-                                          dtype=torch.float32, device=self.device),
-                               torch.zeros((self.num_envs, em.columns), dtype=torch.uint8, device=self.device),
-                               torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)) for _ in range(self._nbuf)]
-            self._elev_mask = torch.zeros(self.num_envs, dtype=torch.uint8, device=self.device)
-        self._elev_cur = 0
-        self._elev_pose = (self.state[_lib.POS:_lib.POS + 3].t(), self.state[_lib.QUAT:_lib.QUAT + 4].t())
-        self.extras["elevation_scan"], self.extras["elevation_known"], self.extras["elevation_count"] = self._elev_out[0]
-
-    def _init_lidar(self):
-        """``cfg.lidar``: the ray table, the workspace (the camera's where there is one: the pyramid is built once) and two range
-        buffers that rotate like the depth buffers; with ``cfg.elevation.source = "lidar"`` the elevation map behind them."""
-        lid = getattr(self.cfg, "lidar", None)
-        self._lidar = None
-        self._lidar_post = None
-        self.extras.pop("lidar_range", None)
-        self.extras.pop("lidar_hits_w", None)
-        if lid is None:
-            return
-        from ..lidar import Lidar, elevation_geometry
-        self._lidar = Lidar(lid, self, workspace=self._camera_ws if self._camera_cfg is not None else None)
-        if self._lidar.workspace is None:
-            self._lidar.prepare()
-        self._lidar_every = int(lid.every_n_steps)
-        if lid.noise is not None or lid.clip is not None:      # range noise / clip: one launch behind every cast
-            from ..obs_post import LIDAR_TAG, ObsPost, lidar_segments
-            self._lidar_post = ObsPost(lidar_segments(lid), self._lidar.rays, seed=int(self.cfg.seed),
-                                       env_id_offset=int(self.cfg.env_id_offset), tag=LIDAR_TAG)
-        n, L = self.num_envs, self._lidar
-        with torch.cuda.device(self.device):
-            self._lidar_range = [torch.full((n, L.channels, L.azimuths), float("inf"), dtype=torch.float32, device=self.device)
-                                 for _ in range(self._nbuf)]
-            self._lidar_hits = [torch.full((n, L.rays, 3), float("inf"), dtype=torch.float32, device=self.device)
-                                for _ in range(self._nbuf)] if lid.hits else None
-        self._lidar_cur = 0
-        self.extras["lidar_range"] = self._lidar_range[0]
-        if lid.hits:
-            self.extras["lidar_hits_w"] = self._lidar_hits[0]
-        if self._elev_from_lidar:                              # the map: one launch behind the lidar chain, fed the lidar's own table
-            from ..elevation import ElevationMap
-            self._init_elevation(ElevationMap(self.cfg.elevation, elevation_geometry(lid), self.cfg.height_scanner, self.num_envs,
-                                              self.device, rays=L._rays32))
-
-    def _cast_into(self, buf: torch.Tensor, hits: torch.Tensor | None = None):
-        """The lidar frame of the current state into the (N, channels, azimuths) ``buf``, then ``cfg.lidar``'s noise and clip in
-        place, the draws keyed by the call counter of the launch that left the state (as the camera's)."""
-        self._lidar.cast(buf, hits)
-        if self._lidar_post is not None:
-            self._lidar_post.apply(buf, self._launch_counter())
-
-    def _lidar_update(self, force: bool = False, reset=(None, None)):
-        """Cast from the pose the step (or reset) left behind into the next range buffer.  With ``cfg.elevation.source = "lidar"``
-        the map is then updated on every call, without a frame on a step that casts nothing."""
-        buf = None
-        if force or self.common_step_counter % self._lidar_every == 0:
-            self._lidar_cur = (self._lidar_cur + 1) % self._nbuf
-            buf = self._lidar_range[self._lidar_cur]
-            hits = None if self._lidar_hits is None else self._lidar_hits[self._lidar_cur]
-            self._cast_into(buf, hits)
-            self.extras["lidar_range"] = buf
-            if hits is not None:
-                self.extras["lidar_hits_w"] = hits
-        if self._elev_from_lidar:
-            self._elevation_update(buf, reset)
 
     def cast_lidar(self) -> torch.Tensor:
         """A fresh lidar frame of the current state, (num_envs, channels, azimuths) fp32 in a new buffer.  With ``cfg.lidar.noise``
         a re-cast of the same state repeats its noise (the draws are keyed by the call counter, not by the number of casts)."""
-        if self._lidar is None:
-            raise RuntimeError("cast_lidar needs a lidar (cfg.lidar)")
-        buf = torch.empty(self.num_envs, self._lidar.channels, self._lidar.azimuths, dtype=torch.float32, device=self.device)
-        self._cast_into(buf)
-        return buf
-
-    def _render_into(self, buf: torch.Tensor, valid: torch.Tensor | None = None):
-        """The depth image of the current state into the row-major (N, H, W) ``buf``, then ``cfg.camera``'s sensor model (its
-        per-env count of valid pixels into ``valid``), then its noise and clip, all in place.  The draws are keyed by the call
-        counter of the launch that left the state, so a re-render of the same state repeats its noise."""
-        _lib.check(self._lib.rover_camera_render(self._h, C.byref(self._camera_cfg), _ptr(self._camera_ws), _ptr(buf), self._stream()),
-                   "rover_camera_render")
-        if self._depth_sensor is not None:
-            self._depth_sensor.apply(buf, self._launch_counter(), valid_out=valid)
-        if self._depth_post is not None:
-            self._depth_post.apply(buf, self._launch_counter())
-
-    def _camera_update(self, force: bool = False, reset=(None, None)):
-        """Render the pose the step (or reset) left behind into the next depth buffer: extras["depth"] is its (N, W, H) view.
-        With ``cfg.elevation`` the map is then updated on every call, without a frame on a step that renders nothing; ``reset``:
-        the step's terminated and time-out buffers, whose envs start their maps over.  ``cfg.lidar``'s chain runs first, on the
-        same occasions."""
-        if self._lidar is not None:                            # the lidar's chain (and the map, where the lidar feeds it)
-            self._lidar_update(force, reset)
-        if self._camera_cfg is None:
-            return
-        elevation = None if self._elev_from_lidar else self._elevation
-        if not (force or self.common_step_counter % self._camera_every == 0):
-            if elevation is not None:
-                self._elevation_update(None, reset)
-            return
-        self._depth_cur = (self._depth_cur + 1) % self._nbuf
-        buf = self._depth[self._depth_cur]
-        if self._depth_sensor is None:
-            self._render_into(buf)
-        else:
-            self._render_into(buf, self._depth_valid[self._depth_cur])
-            self.extras["depth_valid"] = self._depth_valid[self._depth_cur]
-        self.extras["depth"] = buf.permute(0, 2, 1)
-        if elevation is not None:
-            self._elevation_update(buf, reset)
-
-    def _elevation_update(self, depth, reset):
-        """One ``rover_elevation_step`` launch into the next set of output buffers (they rotate as the depth buffers do)."""
-        self._elev_cur = (self._elev_cur + 1) % self._nbuf
-        scan, known, count = self._elev_out[self._elev_cur]
-        pos, quat = self._elev_pose
-        self._elevation.update(depth, pos, quat, reset=reset, scan_out=scan, known_out=known, count_out=count)
-        self.extras["elevation_scan"], self.extras["elevation_known"], self.extras["elevation_count"] = scan, known, count
+        return self.sensors.cast_lidar()
 
     def render_depth(self) -> torch.Tensor:
         """A fresh depth image of the current state, (num_envs, width, height) fp32: the permuted view of a new row-major
         (num_envs, height, width) buffer, the layout of ``extras["depth"]``.  With ``cfg.camera.noise`` a re-render of the same
         state repeats its noise (the draws are keyed by the call counter, not by the number of renders)."""
-        if self._camera_cfg is None:
-            raise RuntimeError("render_depth needs a camera (cfg.camera)")
-        buf = torch.empty(self.num_envs, self.cfg.camera.height, self.cfg.camera.width, dtype=torch.float32, device=self.device)
-        self._render_into(buf)
-        return buf.permute(0, 2, 1)
+        return self.sensors.render_depth()
 
     # ------------------------------------------------------------------------------------------------------------
     @property
@@ -647,10 +479,9 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
             self._native_cfg.seed_lo, self._native_cfg.seed_hi = lo, hi
             _lib.check(self._lib.rover_set_seed(self._h, lo, hi), "rover_set_seed")
             self._obs_gen.manual_seed(seed)      # the observation-noise draws of plain (non-ORBIT) noise objects
-            for post in (self._obs_fused, getattr(self, "_depth_post", None), getattr(self, "_depth_sensor", None),
-                         getattr(self, "_lidar_post", None)):
-                if post is not None:             # the fused backend's draws are keyed by the same seed
-                    post.seed = seed
+            if self._obs_fused is not None:      # the fused backend's draws are keyed by the same seed
+                self._obs_fused.seed = seed
+            self.sensors.reseed(seed)
         return int(self.cfg.seed)
 
     def reset(self, seed: int | None = None, options=None):
@@ -667,9 +498,9 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
         if self._obs_post:
             self._post_observations(obs)
         self.obs_buf = {"policy": obs}
-        if self._elevation is not None:
-            self._elevation.clear()
-        self._camera_update(force=True)
+        if self.sensors.active:
+            self.sensors.clear()
+            self.sensors.update(force=True)
         return self.obs_buf, self.extras
 
     def reset_with_draws(self, mask, spawn_row, yaw_u, theta_u, heading_u):
@@ -694,11 +525,8 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
         if self._obs_post:
             self._post_observations(obs)
         self.obs_buf = {"policy": obs}
-        if self._elevation is not None:                   # the masked envs' maps start over with a frame of their new pose
-            self._elev_mask.fill_(1) if mask_d is None else self._elev_mask.copy_(mask_d)
-            self._camera_update(force=True, reset=(self._elev_mask, None))
-        elif self._lidar is not None:                     # a frame of the poses the masked envs were reset to
-            self._lidar_update(force=True)
+        if self.sensors.active:                           # the masked envs' maps start over with a frame of their new pose
+            self.sensors.update_after_draws(mask_d)
         return self.obs_buf, self.extras
 
     def _check_action(self, action: torch.Tensor) -> torch.Tensor:
@@ -720,18 +548,27 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
                                   self._stream())
         if rc != 0:
             _lib.check(rc, "rover_step")
+        self._step_counted(k)
+        self._step_tail(k)
+        return self.obs_buf, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
+
+    def _step_counted(self, k: int):
+        """What follows the launch that ran the physics: the counter mirror, the step count and this step's reward / flag buffers."""
         self._bump_counter()
         self.common_step_counter += 1
+        self.reward_buf = self._rew[k]
+        self.reset_terminated = self._term_b[k]
+        self.reset_time_outs = self._trunc_b[k]
+
+    def _step_tail(self, k: int):
+        """What follows the launch that wrote the observation row: the log flags, the row and its post-processing, the sensors."""
         self._log_pending = self._log_deferred
         self._log_host_stale = True
         self.obs_buf = self._obs_dicts[k]
         if self._obs_post:
             self._post_observations(self.obs_buf["policy"])
-        self.reward_buf = self._rew[k]
-        self.reset_terminated = self._term_b[k]
-        self.reset_time_outs = self._trunc_b[k]
-        self._camera_update(reset=(self._term[k], self._trunc[k]))
-        return self.obs_buf, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
+        if self.sensors.active:
+            self.sensors.update(reset=(self._term[k], self._trunc[k]))
 
     def _fresh_scan(self) -> torch.Tensor:
         """Height scan of the pose the physics left (slow path, once per step, only if a user term asks for the ray hits)."""
@@ -754,11 +591,7 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
         st = self._stream()
         _lib.check(self._lib.rover_step_begin(self._h, C.c_void_p(action.data_ptr()), self._rew_ptr[k], self._term_ptr[k],
                                               self._trunc_ptr[k], self._force_ptr, st), "rover_step_begin")
-        self._bump_counter()
-        self.common_step_counter += 1
-        self.reward_buf = self._rew[k]
-        self.reset_terminated = self._term_b[k]
-        self.reset_time_outs = self._trunc_b[k]
+        self._step_counted(k)       # the user's terms see the counters and the buffers of this step
         self._in_user_terms, self._scan_cache = True, None
         try:
             dones = []
@@ -788,12 +621,8 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
             self._user_log[nr + i] = torch.where(any_reset, torch.logical_and(v, mask_b).sum().to(torch.float32), self._user_log[nr + i])
         _lib.check(self._lib.rover_step_finish(self._h, _ptr(self._reset_mask), self._obs_ptr[k], self._force_ptr, self._log_ptr, st),
                    "rover_step_finish")
-        self._log_pending = False        # the second half reduces the built-in log eagerly
-        self._log_host_stale = True
-        self.obs_buf = self._obs_dicts[k]
-        if self._obs_post:
-            self._post_observations(self.obs_buf["policy"])
-        self._camera_update(reset=(self._term[k], self._trunc[k]))
+        self._step_tail(k)
+        self._log_pending = False        # the second half reduces the built-in log eagerly (nothing read the tail's value in between)
         return self.obs_buf, self.reward_buf, self.reset_terminated, self.reset_time_outs, self.extras
 
     def _post_observations(self, obs: torch.Tensor):
@@ -865,17 +694,8 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
         _lib.check(self._lib.rover_profile_step(self._h, C.c_void_p(action.data_ptr()), self._obs_ptr[k], self._rew_ptr[k],
                                                 self._term_ptr[k], self._trunc_ptr[k], self._force_ptr, self._log_ptr,
                                                 self._stream(), C.byref(a), C.byref(b)), "rover_profile_step")
-        self._bump_counter()
-        self.common_step_counter += 1
-        self._log_pending = self._log_deferred
-        self._log_host_stale = True
-        self.obs_buf = self._obs_dicts[k]
-        if self._obs_post:
-            self._post_observations(self.obs_buf["policy"])
-        self.reward_buf = self._rew[k]
-        self.reset_terminated = self._term_b[k]
-        self.reset_time_outs = self._trunc_b[k]
-        self._camera_update(reset=(self._term[k], self._trunc[k]))
+        self._step_counted(k)
+        self._step_tail(k)
         return a.value, b.value
 
     def profile_event_overhead(self, reps: int = 100) -> float:
@@ -980,8 +800,7 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
               "common_step_counter": int(self.common_step_counter), "call_counter": self.call_counter,
               # the Philox key: an env re-seeded with seed() / reset(seed=) must be restored with ITS key
               "seed_lo": int(self._native_cfg.seed_lo), "seed_hi": int(self._native_cfg.seed_hi)}
-        if self._elevation is not None:                        # the map is state of its own: what the camera saw earlier
-            sd.update(self._elevation.state_dict())
+        sd.update(self.sensors.state_dict())                   # the map is state of its own: what its sensor saw earlier
         return sd
 
     def load_state_dict(self, sd: dict):
@@ -997,8 +816,7 @@ class RoverEnv(ViewerMixin, RLTaskEnv):
             self.seed(int(sd["seed_lo"]) | (int(sd["seed_hi"]) << 32))
         _lib.check(self._lib.rover_set_counter(self._h, int(sd.get("call_counter", 0))), "rover_set_counter")
         self._sync_counter()                                   # the struct mirror follows the handle
-        if self._elevation is not None and "elevation_map" in sd:
-            self._elevation.load_state_dict(sd)
+        self.sensors.load_state_dict(sd)
         self.obs_buf = self._obs_dicts[self._cur]
         return self.obs_buf
 
@@ -1050,4 +868,4 @@ class RoverEnvCamera(RoverEnv):
         if self.cfg.camera is None:         # a translated reference cfg
             from ..cfg import CameraCfg
             self.cfg.camera = CameraCfg()
-            self._init_camera()
+            self.sensors = SensorRig.for_env(self)

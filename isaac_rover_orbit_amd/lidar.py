@@ -231,18 +231,10 @@ class Lidar(_LidarBase):
         n, R = self.num_envs, self.rays
         if self.workspace is None:
             raise RuntimeError("Lidar.cast needs prepare() (or an adopted workspace) first")
-        t = range_out
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.device != self.table.device:
-            raise ValueError("range_out must be a float32 cuda tensor on the lidar's device")
-        if t.dim() == 2 and tuple(t.shape) == (n, R) and t.stride(1) == 1 and (n == 1 or t.stride(0) >= R):
-            pitch = t.stride(0) if n > 1 else R
-        elif t.is_contiguous() and t.shape[0] == n and t.numel() == n * R:
-            pitch = R
-        else:
-            raise ValueError(f"range_out must hold {R} consecutive values per env, {n} envs")
+        pitch = _fused.row_pitch("range_out", range_out, R, rows=n, device=self.table.device)
         if hits_out is not None:
             _fused.f32_cuda("hits_out", hits_out, self.table.device, "the lidar's device")
             _fused.holds("hits_out", hits_out, (n, R, 3))
         _fused.launch("rover_lidar_cast", self.device, self._h, C.byref(self.native), self.workspace.data_ptr(),
-                      self.table.data_ptr(), t.data_ptr(), int(pitch), _fused.ptr(hits_out))
+                      self.table.data_ptr(), range_out.data_ptr(), pitch, _fused.ptr(hits_out))
         return range_out

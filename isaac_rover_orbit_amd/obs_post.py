@@ -202,14 +202,7 @@ class ObsPost(_ObsPostBase):
         self._segs = (_lib.ObsPostSegment * len(self.segments))(*self.segments)
 
     def apply(self, rows: torch.Tensor, counter: int) -> torch.Tensor:
-        if not rows.is_cuda or rows.dtype != torch.float32 or rows.dim() < 2:
-            raise ValueError("rows must be a float32 cuda tensor of at least two dimensions")
-        if rows.dim() == 2 and rows.stride(1) == 1 and rows.shape[1] == self.width and (rows.shape[0] == 1 or rows.stride(0) >= self.width):
-            pitch = rows.stride(0) if rows.shape[0] > 1 else self.width
-        elif rows.is_contiguous() and rows.numel() == rows.shape[0] * self.width:
-            pitch = self.width
-        else:
-            raise ValueError(f"rows must hold {self.width} consecutive values per row")
-        _fused.launch("rover_obs_post_apply", rows.device, self._segs, len(self.segments), rows.data_ptr(), self.width, int(pitch),
+        pitch = _fused.row_pitch("rows", rows, self.width)
+        _fused.launch("rover_obs_post_apply", rows.device, self._segs, len(self.segments), rows.data_ptr(), self.width, pitch,
                       int(rows.shape[0]), self.seed & 0xFFFFFFFFFFFFFFFF, self.env_id_offset, int(counter), self.tag)
         return rows

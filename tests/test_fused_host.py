@@ -147,3 +147,43 @@ def test_require_gpu_keeps_each_callers_wording(monkeypatch):
                        match=r"^RolloutCollector needs a ROCm GPU \(no CPU fallback; TorchRollout is the CPU specification\)$"):
         _fused.require_gpu("RolloutCollector", "TorchRollout is the CPU specification")
 
+
+
+# ------------------------------------------------------------------------------------------------------------------- row pitch
+def _layout(t, width, rows=None):
+    from isaac_rover_orbit_amd import _fused
+    return _fused.layout_pitch(tuple(t.shape), t.stride(), t.is_contiguous(), width, rows)
+
+
+def test_row_pitch_is_one_rule_for_padded_rows_and_contiguous_images():
+    """``_fused.row_pitch``: the layout half on CPU tensors' own shapes and strides, the dtype / device half as far as it runs
+    without a GPU, and the whole of it on the device where there is one."""
+    from isaac_rover_orbit_amd import _fused
+    base = torch.zeros(64)
+    strided = lambda shape, stride: base.as_strided(shape, stride)      # noqa: E731
+    # accepted: plain rows, a padded pitch, one row with any row stride, a contiguous image
+    assert _layout(torch.zeros(3, 6), 6) == 6 and _layout(torch.zeros(3, 6), 6, rows=3) == 6
+    assert _layout(strided((3, 6), (10, 1)), 6) == 10 and _layout(torch.zeros(3, 10)[:, 2:8], 6) == 10
+    assert _layout(strided((1, 6), (2, 1)), 6) == 6 and _layout(strided((1, 6), (40, 1)), 6, rows=1) == 6
+    assert _layout(torch.zeros(3, 2, 3), 6) == 6 and _layout(torch.zeros(3, 2, 3), 6, rows=3) == 6
+    assert _layout(torch.zeros(0, 6), 6) == 6
+    # refused: rows that overlap, a column stride of 2, a wrong width, a wrong row count, one dimension, a permuted image
+    assert _layout(strided((3, 6), (4, 1)), 6) is None
+    assert _layout(strided((3, 6), (12, 2)), 6) is None and _layout(strided((1, 6), (12, 2)), 6) is None
+    assert _layout(torch.zeros(3, 6), 5) is None and _layout(torch.zeros(3, 6), 7) is None and _layout(torch.zeros(3, 2, 3), 5) is None
+    assert _layout(torch.zeros(3, 6), 6, rows=2) is None and _layout(torch.zeros(3, 2, 3), 6, rows=4) is None
+    assert _layout(torch.zeros(6), 6) is None and _layout(torch.zeros(6), 6, rows=6) is None and _layout(torch.zeros(1), 1, rows=1) is None
+    assert _layout(torch.zeros(3, 3, 2).permute(0, 2, 1), 6) is None
+    for bad in (torch.zeros(3, 6), np.zeros((3, 6), np.float32), None):           # not on the device: refused by name
+        with pytest.raises(ValueError, match="^scan_out must be a float32 cuda tensor"):
+            _fused.row_pitch("scan_out", bad, 6)
+    if not torch.cuda.is_available():
+        return
+    dev = torch.device("cuda", torch.cuda.current_device())
+    pad = torch.zeros(3, 10, device=dev)
+    assert _fused.row_pitch("rows", pad[:, :6], 6, rows=3, device=dev) == 10 and _fused.row_pitch("rows", pad[:1, 4:], 6) == 6
+    assert _fused.row_pitch("rows", torch.zeros(3, 2, 3, device=dev), 6) == 6
+    for bad, kw in ((pad[:, ::2], {}), (pad[:, :6], {"rows": 4}), (pad[0, :6], {}), (pad.double()[:, :6], {}), (pad[:, :5], {}),
+                    (pad[:, :6], {"device": torch.device("cpu")})):
+        with pytest.raises(ValueError, match="^depth must "):
+            _fused.row_pitch("depth", bad, 6, **kw)

@@ -231,8 +231,8 @@ def test_render_refuses_a_terrain_rebound_without_prepare(rocky):
     env.reset()
     lib, h = env._lib, env._h
     buf = torch.empty(4, 90, 160, device="cuda:0")
-    cfg = env._camera_cfg
-    ws = C.c_void_p(env._camera_ws.data_ptr())
+    cfg = env.sensors.camera_cfg
+    ws = C.c_void_p(env.sensors.workspace.data_ptr())
     assert lib.rover_camera_render(h, C.byref(cfg), ws, C.c_void_p(buf.data_ptr()), None) == 0
     H, W = rocky.shape
     assert lib.rover_set_terrain(h, C.c_void_p(env._height_dev.data_ptr()), C.c_void_p(env._obstacle_dev.data_ptr()),

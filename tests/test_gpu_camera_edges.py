@@ -555,7 +555,7 @@ def test_render_between_step_begin_and_finish_is_refused():
     env = _env(ter, n, CameraCfg())
     env.reset()
     lib, h = env._lib, env._h
-    cfg, ws = env._camera_cfg, _ptr(env._camera_ws)
+    cfg, ws = env.sensors.camera_cfg, _ptr(env.sensors.workspace)
     st = C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
     buf = torch.empty(n, 90, 160, device=DEV)
     a = torch.zeros(n, 2, device=DEV)
@@ -571,7 +571,7 @@ def test_render_between_step_begin_and_finish_is_refused():
     assert lib.rover_step_finish(h, _ptr(mask), _ptr(obs), _ptr(force), _ptr(log), st) == 0
     assert lib.rover_camera_render(h, C.byref(cfg), ws, _ptr(buf), st) == 0
     # a workspace other than the prepared one
-    other = torch.zeros_like(env._camera_ws)
+    other = torch.zeros_like(env.sensors.workspace)
     assert lib.rover_camera_render(h, C.byref(cfg), _ptr(other), _ptr(buf), st) == ERR_STATE
     assert b"prepare" in lib.rover_last_error()
     torch.cuda.synchronize()
@@ -590,7 +590,7 @@ def test_invalid_configs_are_refused_by_the_library_and_the_cfg():
     env = _env(_flat_terrain(), 8, CameraCfg())
     env.reset()
     lib, h = env._lib, env._h
-    nb = int(env._camera_ws.numel() * 4)
+    nb = int(env.sensors.workspace.numel() * 4)
     st = C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
     buf = torch.empty(8, 90, 160, device=DEV)
     for field, value in _BAD:
@@ -601,8 +601,8 @@ def test_invalid_configs_are_refused_by_the_library_and_the_cfg():
         else:
             setattr(cfg, field, value)
         assert lib.rover_camera_workspace_bytes(h, C.byref(cfg)) == 0, field
-        assert lib.rover_camera_prepare(h, C.byref(cfg), _ptr(env._camera_ws), nb, st) == ERR_INVALID, (field, value)
-        assert lib.rover_camera_render(h, C.byref(cfg), _ptr(env._camera_ws), _ptr(buf), st) == ERR_INVALID, (field, value)
+        assert lib.rover_camera_prepare(h, C.byref(cfg), _ptr(env.sensors.workspace), nb, st) == ERR_INVALID, (field, value)
+        assert lib.rover_camera_render(h, C.byref(cfg), _ptr(env.sensors.workspace), _ptr(buf), st) == ERR_INVALID, (field, value)
         cam = CameraCfg()
         setattr(cam, _CFG_NAME.get(field, field), value)
         with pytest.raises(ValueError):

@@ -243,7 +243,7 @@ def test_env_sensor_against_the_specification(terrain, which):
     from isaac_rover_orbit_amd.depth_sensor import TorchDepthSensor, native_cfg
     twin, env, again = _env(terrain, _camera(which)), _env(terrain, _camera(which, _sensor_cfg())), _env(terrain, _camera(which, _sensor_cfg()))
     lo, hi = _env(terrain, _camera(which, _sensor_cfg()), n=8, offset=0), _env(terrain, _camera(which, _sensor_cfg()), n=8, offset=8)
-    assert twin._depth_sensor is None and "depth_valid" not in twin.extras and env._depth_sensor is not None and env._depth_post is None
+    assert twin.sensors.depth_sensor is None and "depth_valid" not in twin.extras and env.sensors.depth_sensor is not None and env.sensors.depth_post is None
     cam = env.cfg.camera
     spec = TorchDepthSensor(native_cfg(cam), cam.height, cam.width, seed=7)
     g = torch.Generator(device="cuda").manual_seed(2)
@@ -294,7 +294,7 @@ def test_env_sensor_runs_ahead_of_the_clip_and_its_noise_is_bounded(terrain):
     from isaac_rover_orbit_amd.depth_sensor import NORMAL_TAG, TorchDepthSensor, native_cfg
     sensor = _sensor_cfg(sigma=(0.002, 0.001, 0.003), disparity_step=0.0)
     twin, env = _env(terrain, _camera("student"), n=4), _env(terrain, _camera("student", sensor, clip=(0.5, 4.0)), n=4)
-    assert env._depth_sensor is not None and env._depth_post is not None
+    assert env.sensors.depth_sensor is not None and env.sensors.depth_post is not None
     cam = env.cfg.camera
     twin.reset(); env.reset()
     clean, got = _image(twin), _image(env)

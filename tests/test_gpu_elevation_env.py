@@ -95,8 +95,8 @@ def test_every_step_is_the_spec_on_the_env_s_own_images():
         want = spec.update(depth, *_pose(env), reset=flags)
         for g, w, key in zip(_extras(env), want, KEYS):
             assert np.array_equal(_i32(g), _i32(w.reshape(g.shape))), (s, key)
-        assert np.array_equal(_i32(env._elevation.map.cpu().numpy()), _i32(spec.map)), s
-        assert np.array_equal(env._elevation.origin.cpu().numpy(), spec.origin), s
+        assert np.array_equal(_i32(env.sensors.elevation.map.cpu().numpy()), _i32(spec.map)), s
+        assert np.array_equal(env.sensors.elevation.origin.cpu().numpy(), spec.origin), s
     env.close()
 
 
@@ -108,7 +108,7 @@ def test_a_forced_reset_starts_one_map_over():
         env.reset()
         for _ in range(3):
             _zero(env)
-    assert torch.equal(a._elevation.map.view(torch.int32), b._elevation.map.view(torch.int32))
+    assert torch.equal(a.sensors.elevation.map.view(torch.int32), b.sensors.elevation.map.view(torch.int32))
     mask = np.array([0, 0, 1, 0], np.uint8)
     a.reset_with_draws(mask, *_draws(a, [0, 1, 5, 3]))
     pos, quat = _pose(a)
@@ -117,12 +117,12 @@ def test_a_forced_reset_starts_one_map_over():
     _, _, want = spec.update(a.extras["depth"].permute(0, 2, 1).contiguous().cpu().numpy(), pos, quat)
     scan, known, count = _extras(a)
     assert count[2] == want[2] > 0 and count[2] == known[2].sum()
-    assert np.array_equal(_i32(a._elevation.map[2].cpu().numpy()), _i32(spec.map[2]))
+    assert np.array_equal(_i32(a.sensors.elevation.map[2].cpu().numpy()), _i32(spec.map[2]))
     others = [0, 1, 3]
-    assert torch.equal(a._elevation.map[others].view(torch.int32), b._elevation.map[others].view(torch.int32))
+    assert torch.equal(a.sensors.elevation.map[others].view(torch.int32), b.sensors.elevation.map[others].view(torch.int32))
     assert (count[others] > want[others]).any()                    # they remember more than one frame shows
     _zero(a), _zero(b)
-    assert torch.equal(a._elevation.map[others].view(torch.int32), b._elevation.map[others].view(torch.int32))
+    assert torch.equal(a.sensors.elevation.map[others].view(torch.int32), b.sensors.elevation.map[others].view(torch.int32))
     for x, y in zip(_extras(a), _extras(b)):
         assert np.array_equal(_i32(x[others]), _i32(y[others]))
     a.close(), b.close()
@@ -134,14 +134,14 @@ def test_a_step_without_a_render_scrolls_and_scans_only():
     spec = _spec(env)
     env.reset()
     _zero(env), _zero(env)                                         # steps 1 (no render) and 2 (render)
-    spec.load_state_dict(env._elevation.state_dict())
+    spec.load_state_dict(env.sensors.elevation.state_dict())
     depth_before = env.extras["depth"]
     _, _, term, trunc, extras = _zero(env)                         # step 3: no render
     assert extras["depth"] is depth_before or extras["depth"].data_ptr() == depth_before.data_ptr()
     want = spec.update(None, *_pose(env), reset=(term.cpu().numpy(), trunc.cpu().numpy()))
     for g, w, key in zip(_extras(env), want, KEYS):
         assert np.array_equal(_i32(g), _i32(w.reshape(g.shape))), key
-    assert np.array_equal(_i32(env._elevation.map.cpu().numpy()), _i32(spec.map)) and want[2].min() >= 91
+    assert np.array_equal(_i32(env.sensors.elevation.map.cpu().numpy()), _i32(spec.map)) and want[2].min() >= 91
     env.close()
 
 
@@ -149,7 +149,7 @@ def test_without_a_map_nothing_changes():
     env = _env(elevation=False)
     _, extras = env.reset()
     _, _, _, _, extras = _zero(env)
-    assert not any(k in extras for k in KEYS) and "depth" in extras and env._elevation is None
+    assert not any(k in extras for k in KEYS) and "depth" in extras and env.sensors.elevation is None
     assert set(env.state_dict()) == {"state", "obs", "log", "num_envs", "common_step_counter", "call_counter", "seed_lo", "seed_hi"}
     env.close()
     cfg = RoverEnvCfg(elevation=ElevationMapCfg())
@@ -171,6 +171,6 @@ def test_checkpoint_round_trip():
     _zero(a), _zero(b)
     for x, y in zip(_extras(a), _extras(b)):
         assert np.array_equal(_i32(x), _i32(y))
-    assert torch.equal(a._elevation.map.view(torch.int32), b._elevation.map.view(torch.int32))
-    assert torch.equal(a._elevation.origin, b._elevation.origin) and torch.isfinite(a._elevation.map).sum() > 1000
+    assert torch.equal(a.sensors.elevation.map.view(torch.int32), b.sensors.elevation.map.view(torch.int32))
+    assert torch.equal(a.sensors.elevation.origin, b.sensors.elevation.origin) and torch.isfinite(a.sensors.elevation.map).sum() > 1000
     a.close(), b.close()

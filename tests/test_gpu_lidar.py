@@ -179,7 +179,7 @@ def test_state_refusals_and_one_workspace_for_both_sensors():
     c = cfg.to_native()
     tab = torch.from_numpy(lidar.pattern_rays(cfg)).to(DEV)
     out = torch.full((n, cfg.rays), float("nan"), device=DEV)
-    cam, cws = env._camera_cfg, ptr(env._camera_ws)
+    cam, cws = env.sensors.camera_cfg, ptr(env.sensors.workspace)
     img = torch.empty(n, 9, 16, device=DEV)
 
     def cast(ws):

@@ -71,7 +71,7 @@ def test_keys_shapes_ranges_and_hits_on_flat_ground():
     _, extras = env.reset()
     r, h = extras["lidar_range"], extras["lidar_hits_w"]
     assert r.shape == (N, 32, 180) and r.dtype == torch.float32 and h.shape == (N, 5760, 3)
-    assert "depth" not in extras and "elevation_scan" not in extras and env._camera_cfg is None      # a lidar alone works
+    assert "depth" not in extras and "elevation_scan" not in extras and env.sensors.camera_cfg is None      # a lidar alone works
     torch.cuda.synchronize()
     o, d, got = _plane(env, r)
     with np.errstate(all="ignore"):
@@ -136,20 +136,20 @@ def test_noise_repeats_on_a_recast_and_moves_with_the_counter():
 def test_no_lidar_adds_nothing_and_both_sensors_share_one_pyramid():
     env = _env(None, camera=CameraCfg(width=16, height=9))
     _, extras = env.reset()
-    assert env._lidar is None and not any(k.startswith("lidar") for k in extras)
+    assert env.sensors.lidar is None and not any(k.startswith("lidar") for k in extras)
     with pytest.raises(RuntimeError):
         env.cast_lidar()
     depth_alone = extras["depth"].clone()
     env.close()
     env = _env(LidarCfg(), camera=CameraCfg(width=16, height=9), elevation=ElevationMapCfg())
     _, extras = env.reset()
-    assert env._lidar.workspace is env._camera_ws                               # one prepared workspace serves both
+    assert env.sensors.lidar.workspace is env.sensors.workspace                               # one prepared workspace serves both
     assert extras["lidar_range"].shape == (N, 32, 180) and extras["depth"].shape == (N, 16, 9)
     assert "lidar_hits_w" not in extras
     torch.cuda.synchronize()
     assert torch.equal(extras["depth"], depth_alone)      # the camera's path is untouched
     _plane(env, extras["lidar_range"])
-    assert env._elevation.pixels == 16 * 9                                      # source = "camera": the map hangs behind the camera
+    assert env.sensors.elevation.pixels == 16 * 9                                      # source = "camera": the map hangs behind the camera
     _zero(env)
     env.close()
 
@@ -180,7 +180,7 @@ def test_one_dense_frame_fills_the_scan_and_reads_what_the_oracle_reads():
     own column within 1e-4 * range_max + 1e-4 m (section 36's bound)."""
     env = _map_env()
     obs, extras = env.reset()
-    assert env._camera_cfg is None and extras["elevation_scan"].shape == (M, 961)
+    assert env.sensors.camera_cfg is None and extras["elevation_scan"].shape == (M, 961)
     scan, known, count = _extras(env)
     print("known columns per env after one dense frame:", count.tolist())
     assert (count >= 955).all() and np.array_equal(count, known.sum(1).astype(np.int32))
@@ -215,8 +215,8 @@ def test_every_step_is_the_spec_on_the_env_s_own_frames():
         want = spec.update(frame, *_pose(env), reset=flags)
         for g, w, key in zip(_extras(env), want, KEYS):
             assert np.array_equal(_i32(g), _i32(w.reshape(g.shape))), (s, key)
-        assert np.array_equal(_i32(env._elevation.map.cpu().numpy()), _i32(spec.map)), s
-        assert np.array_equal(env._elevation.origin.cpu().numpy(), spec.origin), s
+        assert np.array_equal(_i32(env.sensors.elevation.map.cpu().numpy()), _i32(spec.map)), s
+        assert np.array_equal(env.sensors.elevation.origin.cpu().numpy(), spec.origin), s
     assert restarted                                                            # an in-step reset started env 1's map over
     env.close()
 
@@ -230,7 +230,7 @@ def test_resets_start_a_map_over_and_a_checkpoint_round_trips():
         env.reset()
         for _ in range(3):
             _zero(env)
-    assert torch.equal(a._elevation.map.view(torch.int32), b._elevation.map.view(torch.int32))
+    assert torch.equal(a.sensors.elevation.map.view(torch.int32), b.sensors.elevation.map.view(torch.int32))
     a.reset_with_draws(np.array([0, 0, 1, 0], np.uint8), *_draws(a, [0, 1, 5, 3]))
     pos, quat = _pose(a)
     assert not np.array_equal(pos[2], _pose(b)[0][2])
@@ -238,9 +238,9 @@ def test_resets_start_a_map_over_and_a_checkpoint_round_trips():
     _, _, want = spec.update(a.extras["lidar_range"].cpu().numpy(), pos, quat)
     scan, known, count = _extras(a)
     assert count[2] == want[2] > 0
-    assert np.array_equal(_i32(a._elevation.map[2].cpu().numpy()), _i32(spec.map[2]))
+    assert np.array_equal(_i32(a.sensors.elevation.map[2].cpu().numpy()), _i32(spec.map[2]))
     others = [0, 1, 3]
-    assert torch.equal(a._elevation.map[others].view(torch.int32), b._elevation.map[others].view(torch.int32))
+    assert torch.equal(a.sensors.elevation.map[others].view(torch.int32), b.sensors.elevation.map[others].view(torch.int32))
     sd = a.state_dict()
     assert {"elevation_map", "elevation_origin"} <= set(sd)
     c = _map_env(LidarCfg())
@@ -249,8 +249,8 @@ def test_resets_start_a_map_over_and_a_checkpoint_round_trips():
     _zero(a), _zero(c)
     for x, y in zip(_extras(a), _extras(c)):
         assert np.array_equal(_i32(x), _i32(y))
-    assert torch.equal(a._elevation.map.view(torch.int32), c._elevation.map.view(torch.int32))
-    assert torch.equal(a._elevation.origin, c._elevation.origin) and torch.isfinite(a._elevation.map).sum() > 1000
+    assert torch.equal(a.sensors.elevation.map.view(torch.int32), c.sensors.elevation.map.view(torch.int32))
+    assert torch.equal(a.sensors.elevation.origin, c.sensors.elevation.origin) and torch.isfinite(a.sensors.elevation.map).sum() > 1000
     a.close(), b.close(), c.close()
 
 

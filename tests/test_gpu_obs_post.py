@@ -274,7 +274,7 @@ def test_camera_noise_and_clip(terrain, which):
         return c
 
     twin, env = _env(terrain, None, n=4, post=False, camera=cam(False)), _env(terrain, None, n=4, post=False, camera=cam(True))
-    assert twin._depth_post is None and env._depth_post is not None
+    assert twin.sensors.depth_post is None and env.sensors.depth_post is not None
     h, w = env.cfg.camera.height, env.cfg.camera.width
     spec = TorchObsPost(image_segments(env.cfg.camera), h * w, seed=7, tag=obs_post.DEPTH_TAG)
     twin.reset(); env.reset()

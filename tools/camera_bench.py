@@ -60,11 +60,11 @@ def main():
     cam = on.cfg.camera
     buf = torch.empty(n, cam.height, cam.width, dtype=torch.float32, device="cuda:0")
     for _ in range(a.warm):
-        on._render_into(buf)
+        on.sensors.render_into(buf)
     torch.cuda.synchronize()
     if a.trace_only:
         for _ in range(a.renders):
-            on._render_into(buf)
+            on.sensors.render_into(buf)
         torch.cuda.synchronize()
         print(json.dumps({"trace_renders": a.renders, "envs": n}))
         return
@@ -73,7 +73,7 @@ def main():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(a.renders):
-            on._render_into(buf)
+            on.sensors.render_into(buf)
         e1.record()
         e1.synchronize()
         ms.append(e0.elapsed_time(e1) / a.renders)

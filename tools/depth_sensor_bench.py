@@ -122,24 +122,24 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(0)
     actions = torch.rand(256, n, 2, device="cuda", generator=g) * 2 - 1
     env.reset()
-    cam.every_n_steps, env._camera_every = 1 << 30, 1 << 30      # the pre-roll renders nothing
+    cam.every_n_steps, env.sensors.camera_every = 1 << 30, 1 << 30      # the pre-roll renders nothing
     for k in range(args.preroll):
         env.step(actions[(k * 7) % 256])
-    sensor, post = env._depth_sensor, env._depth_post
-    env._depth_sensor = env._depth_post = None                   # the launches are made by hand below
+    sensor, post = env.sensors.depth_sensor, env.sensors.depth_post
+    env.sensors.depth_sensor = env.sensors.depth_post = None                   # the launches are made by hand below
     assert isinstance(sensor, DepthSensor) and isinstance(post, ObsPost)
     buf = torch.empty(n, cam.height, cam.width, device="cuda")
     valid = torch.empty(n, dtype=torch.int32, device="cuda")
 
     def render():
-        env._render_into(buf)
+        env.sensors.render_into(buf)
 
     def render_sensor():
-        env._render_into(buf)
+        env.sensors.render_into(buf)
         sensor.apply(buf, 0, valid_out=valid)
 
     def render_noise_clip():
-        env._render_into(buf)
+        env.sensors.render_into(buf)
         post.apply(buf, 0)
 
     items = (("render", render), ("render_sensor", render_sensor), ("render_noise_clip", render_noise_clip))

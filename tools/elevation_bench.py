@@ -114,9 +114,9 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(0)
     actions = torch.rand(256, n, 2, device="cuda", generator=g) * 2 - 1
     env.reset()
-    cam.every_n_steps, env._camera_every = 1 << 30, 1 << 30      # the pre-roll renders nothing
-    em, sensor = env._elevation, env._depth_sensor
-    env._elevation = env._depth_sensor = None                    # the launches are made by hand below
+    cam.every_n_steps, env.sensors.camera_every = 1 << 30, 1 << 30      # the pre-roll renders nothing
+    em, sensor = env.sensors.elevation, env.sensors.depth_sensor
+    env.sensors.elevation = env.sensors.depth_sensor = None                    # the launches are made by hand below
     for k in range(args.preroll):
         env.step(actions[(k * 7) % 256])
     raw = torch.empty(n, cam.height, cam.width, device="cuda")
@@ -125,7 +125,7 @@ def main():
     pos_c, quat_c = pos.contiguous(), quat.contiguous()
     outs = (torch.empty(n, em.columns, device="cuda"), torch.empty(n, em.columns, dtype=torch.uint8, device="cuda"),
             torch.empty(n, dtype=torch.int32, device="cuda"))
-    env._render_into(raw)
+    env.sensors.render_into(raw)
     sensor.apply(raw, 0, out=img)
     em.update(img, pos, quat, scan_out=outs[0], known_out=outs[1], count_out=outs[2])       # the maps hold one frame
     t_map, t_origin = em.map.clone(), em.origin.clone()
@@ -137,7 +137,7 @@ def main():
              # torch rounds the unprojection its own way (bmm, rsqrt): a point on a cell border may land in the neighbour cell
              "share_of_known_columns_off_by_more_than_1e-4_m": float(((outs[0] - t_scan)[both].abs() > 1e-4).float().mean())}
 
-    items = (("render", lambda: env._render_into(raw)),
+    items = (("render", lambda: env.sensors.render_into(raw)),
              ("sensor", lambda: sensor.apply(raw, 0, out=img)),
              ("elevation_step", lambda: em.update(img, pos, quat, scan_out=outs[0], known_out=outs[1], count_out=outs[2])),
              ("elevation_step_no_frame", lambda: em.update(None, pos, quat, scan_out=outs[0], known_out=outs[1], count_out=outs[2])),

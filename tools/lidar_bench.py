@@ -65,13 +65,13 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(0)
     actions = torch.rand(256, n, 2, device="cuda", generator=g) * 2 - 1
     env.reset()
-    cam.every_n_steps, env._camera_every = 1 << 30, 1 << 30      # the pre-roll renders nothing
+    cam.every_n_steps, env.sensors.camera_every = 1 << 30, 1 << 30      # the pre-roll renders nothing
     for k in range(args.preroll):
         env.step(actions[(k * 7) % 256])
     # the three tables; every Lidar adopts the camera's prepared workspace (one pyramid per handle)
     default_cfg = LidarCfg()
     dense_cfg = LidarCfg(channels=64, vertical_fov_range=(-85.0, -20.0), horizontal_res=1.5)
-    default, dense, shuffled = (Lidar(c, env, workspace=env._camera_ws) for c in (default_cfg, dense_cfg, dense_cfg))
+    default, dense, shuffled = (Lidar(c, env, workspace=env.sensors.workspace) for c in (default_cfg, dense_cfg, dense_cfg))
     perm = np.random.default_rng(0).permutation(dense.rays)
     shuffled.table = torch.from_numpy(np.ascontiguousarray(pattern_rays(dense_cfg)[perm])).cuda()
     r_default = torch.empty(n, default.rays, device="cuda")
@@ -96,7 +96,7 @@ def main():
     items = (("lidar_default", lambda: default.cast(r_default), n * default.rays),
              ("lidar_dense", lambda: dense.cast(r_dense), n * dense.rays),
              ("lidar_dense_shuffled", lambda: shuffled.cast(r_shuffled), n * dense.rays),
-             ("camera_render", lambda: env._render_into(image), n * cam.height * cam.width),
+             ("camera_render", lambda: env.sensors.render_into(image), n * cam.height * cam.width),
              ("elevation_step", lambda: em.update(r_dense, pos, quat, scan_out=outs[0], known_out=outs[1], count_out=outs[2]),
               n * dense.rays))
     for _, fn, _ in items:

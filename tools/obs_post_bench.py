@@ -172,15 +172,15 @@ def main():
         cam = noisy_camera()
         env = make_env(ter, n, None, camera=cam)
         env.reset()
-        post, env._depth_post = env._depth_post, None           # the launches are made by hand below
+        post, env.sensors.depth_post = env.sensors.depth_post, None           # the launches are made by hand below
         assert isinstance(post, ObsPost) and post.tag == DEPTH_TAG and len(image_segments(cam)) == 1
         buf = torch.empty(n, cam.height, cam.width, device="cuda")
 
         def render():
-            env._render_into(buf)
+            env.sensors.render_into(buf)
 
         def render_post():
-            env._render_into(buf)
+            env.sensors.render_into(buf)
             post.apply(buf, 0)
 
         for fn in (render, render_post):
