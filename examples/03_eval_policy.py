@@ -15,6 +15,12 @@ it sees all round, so the printed known share of the scan is close to 1 from the
 
     python examples/03_eval_policy.py --checkpoint best_agent.pt --scan_source elevation --map_source lidar --lidar_channels 64 \
         --lidar_vfov -85 -20 --lidar_hres 1.5
+
+``--map_fill min`` inpaints the map behind every update (``ElevationMapCfg.fill``): unknown cells take the minimum of their known
+neighbours at most ``--map_fill_iterations`` cells far, the actor reads ``extras["elevation_scan_filled"]``, and the summary adds
+the mean measured and filled column counts:
+
+    python examples/03_eval_policy.py --checkpoint best_agent.pt --scan_source elevation --map_fill min --map_fill_iterations 20
 """
 import argparse
 import os
@@ -45,6 +51,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--map_alpha", type=float, default=1.0, help="weight of the newest frame on a cell the map already knows")
     ap.add_argument("--map_source", choices=("camera", "lidar"), default="camera",
                     help="the sensor that feeds the elevation map: the depth camera, or a scanning lidar on the mast")
+    ap.add_argument("--map_fill", choices=("none", "min"), default="none",
+                    help="inpaint the map behind every update: unknown cells take the minimum of their known neighbours, and the actor "
+                         "reads the filled scan")
+    ap.add_argument("--map_fill_iterations", type=int, default=32, metavar="N", help="how many cells far a height is carried at the most")
     ap.add_argument("--lidar_channels", type=int, default=32, help="rings of the lidar")
     ap.add_argument("--lidar_vfov", type=float, nargs=2, default=(-60.0, -10.0), metavar=("LO", "HI"),
                     help="elevation angles of the lowest and the highest ring (degrees)")
@@ -75,25 +85,33 @@ def make_cfg(args) -> RoverEnvCfg:
             if args.depth_dropout is not None:
                 s.p_drop, s.p_edge = args.depth_dropout
         cfg.elevation = ElevationMapCfg(alpha=args.map_alpha)
+    if cfg.elevation is not None:
+        cfg.elevation.fill, cfg.elevation.fill_iterations = args.map_fill, args.map_fill_iterations
     return cfg
 
 
 def eval_on_map(env, actor, steps: int):
-    """The loop of ``main`` with the actor on ``policy_rows(obs, extras["elevation_scan"])``; also the mean known share."""
+    """The loop of ``main`` with the actor on ``policy_rows(obs, extras["elevation_scan"])`` -- under ``--map_fill min`` on
+    ``extras["elevation_scan_filled"]``; also the mean known share and the mean measured and filled column counts (the last
+    ``None`` without a fill)."""
     from isaac_rover_orbit_amd.elevation import policy_rows
     obs, info = env.reset()
-    counts, episodes, known = torch.zeros(4), 0.0, 0.0
+    counts, episodes, known, filled = torch.zeros(4), 0.0, 0.0, 0.0
     rows = torch.empty_like(obs["policy"])
+    key = "elevation_scan_filled" if "elevation_scan_filled" in info else "elevation_scan"
     for _ in range(steps):
         torch.nan_to_num_(obs["policy"], neginf=0.0)
-        policy_rows(obs["policy"], info["elevation_scan"], out=rows)
+        policy_rows(obs["policy"], info[key], out=rows)
         obs, rew, terminated, truncated, info = env.step(actor.act(rows))
         log = env.episode_log_vector.cpu()
-        known += float(info["elevation_count"].float().mean()) / (rows.shape[1] - 4)
+        known += float(info["elevation_count"].float().mean())
+        if "elevation_filled_count" in info:
+            filled += float(info["elevation_filled_count"].float().mean())
         if log[13] > 0:
             episodes += float(log[13])
             counts += log[7:11]
-    return episodes, counts, known / max(steps, 1)
+    steps = max(steps, 1)
+    return episodes, counts, known / steps / (rows.shape[1] - 4), (known / steps, filled / steps if "elevation_filled_count" in info else None)
 
 
 def main():
@@ -103,9 +121,11 @@ def main():
     env = RoverEnv(make_cfg(args), terrain=terrain)
     actor = RoverNet.from_checkpoint(args.checkpoint, role="policy")
     if args.scan_source == "elevation":
-        episodes, counts, known = eval_on_map(env, actor, args.steps)
+        episodes, counts, known, (measured, filled) = eval_on_map(env, actor, args.steps)
         print(f"episodes finished: {episodes:.0f}; terminations (time_out, success, far, collision): {counts.tolist()}; "
               f"mean known share of the scan: {known:.3f}")
+        if filled is not None:
+            print(f"mean measured columns per scan: {measured:.1f}; mean columns after the min-fill: {filled:.1f}")
         env.close()
         return
     obs, _ = env.reset()

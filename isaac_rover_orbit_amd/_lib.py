@@ -77,6 +77,7 @@ EXPORTS = [
     "rover_obs_post_segment_bytes", "rover_obs_post_apply",  # rover_obs_post.h
     "rover_depth_sensor_cfg_bytes", "rover_depth_sensor_apply",  # rover_depth_sensor.h
     "rover_elevation_cfg_bytes", "rover_elevation_step", "rover_elevation_scan",  # rover_elevation.h
+    "rover_elevation_fill_cfg_bytes", "rover_elevation_fill",  # rover_elevation_fill.h
     "rover_lidar_config_bytes", "rover_lidar_workspace_bytes", "rover_lidar_prepare", "rover_lidar_cast",  # rover_lidar.h
 ]
 POLICY_MAX_LAYERS = 8
@@ -298,6 +299,14 @@ class ElevationCfg(C.Structure):
                 ("unknown_value", C.c_float)]
 
 
+ELEVATION_FILL_MAX_ITERATIONS = 254
+
+
+class ElevationFillCfg(C.Structure):
+    """Mirror of ``struct rover_elevation_fill_cfg`` (include/rover_elevation_fill.h)."""
+    _fields_ = [("iterations", C.c_int32)]
+
+
 class LidarConfig(C.Structure):
     """Mirror of ``struct rover_lidar_config`` (include/rover_lidar.h)."""
     _fields_ = [("rays", C.c_int32), ("mount_pos", C.c_float * 3), ("near_clip", C.c_float), ("far_clip", C.c_float),
@@ -400,7 +409,8 @@ _MIRRORS = [("rover_config_bytes", RoverConfig), ("rover_lift_config_bytes", Lif
             ("rover_trace_stream_bytes", TraceStream), ("rover_lift_viewer_config_bytes", LiftViewerConfig),
             ("rover_dagger_hparams_bytes", DaggerHparams), ("rover_dagger_state_bytes", DaggerState),
             ("rover_obs_post_segment_bytes", ObsPostSegment), ("rover_depth_sensor_cfg_bytes", DepthSensorCfg),
-            ("rover_elevation_cfg_bytes", ElevationCfg), ("rover_lidar_config_bytes", LidarConfig)]
+            ("rover_elevation_cfg_bytes", ElevationCfg), ("rover_elevation_fill_cfg_bytes", ElevationFillCfg),
+            ("rover_lidar_config_bytes", LidarConfig)]
 
 
 def load():
@@ -669,6 +679,9 @@ def load():
                                          vp, vp, vp, i32, vp, i32, vp, C.c_int64, vp, vp, i32, vp]
     lib.rover_elevation_scan.argtypes = [C.POINTER(ElevationCfg), vp, vp, C.c_int64, C.c_int64, vp, vp, vp, i32, vp, i32, vp,
                                          C.c_int64, vp, vp, i32, vp]
+    lib.rover_elevation_fill_cfg_bytes.restype = C.c_size_t
+    lib.rover_elevation_fill.argtypes = [C.POINTER(ElevationCfg), C.POINTER(ElevationFillCfg), vp, vp, C.c_int64, C.c_int64, vp, vp,
+                                         vp, i32, vp, i32, vp, C.c_int64, vp, vp, vp, vp, i32, vp]
     lib.rover_lidar_config_bytes.restype = C.c_size_t
     lib.rover_lidar_workspace_bytes.argtypes = [vp]
     lib.rover_lidar_workspace_bytes.restype = C.c_size_t

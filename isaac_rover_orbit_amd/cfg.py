@@ -173,12 +173,21 @@ class ElevationMapCfg:
     unknown_value: float = 0.0
     # which sensor feeds the map: "camera" (cfg.camera's depth image) or "lidar" (cfg.lidar's range frame; full attitude only)
     source: str = "camera"
+    # inpainting behind every map update (include/rover_elevation_fill.h): "none", or "min" -- unknown cells take the minimum of
+    # their known neighbours, ring by ring, at most ``fill_iterations`` cells far; published next to the raw scan, never in its place
+    fill: str = "none"
+    fill_iterations: int = 32
 
     def check(self):
         """ValueError for what the library refuses, on the values as the fp32 struct holds them."""
         f32 = lambda x: C.c_float(float(x)).value      # noqa: E731
         if self.source not in ("camera", "lidar"):
             raise ValueError("elevation source must be 'camera' or 'lidar'")
+        if self.fill not in ("none", "min"):
+            raise ValueError("elevation fill must be 'none' or 'min'")
+        it = self.fill_iterations
+        if isinstance(it, bool) or not isinstance(it, int) or not 1 <= it <= _lib.ELEVATION_FILL_MAX_ITERATIONS:
+            raise ValueError(f"elevation fill_iterations must be an integer in [1, {_lib.ELEVATION_FILL_MAX_ITERATIONS}]")
         g = int(self.grid)
         if g != self.grid or g < _lib.ELEVATION_MIN_GRID or g > _lib.ELEVATION_MAX_GRID or g & (g - 1):
             raise ValueError(f"elevation grid must be a power of two in [{_lib.ELEVATION_MIN_GRID}, {_lib.ELEVATION_MAX_GRID}]")

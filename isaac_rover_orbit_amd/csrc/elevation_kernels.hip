@@ -1,7 +1,7 @@
 // elevation_kernels.hip -- the rolling elevation map from the depth camera (scroll, unproject, reduce, fuse, scan) as one launch
 // (gfx950 / CDNA4, wave64).
 //
-// See include/rover_elevation.h for the contract and the operation order.  Two kernels:
+// See include/rover_elevation.h and include/rover_elevation_fill.h for the contracts and the operation order.  Three kernels:
 //   elevation_step_kernel<G>  one workgroup of 512 threads per env, so the env index -- and with it the pose, the reset flag and
 //                             the old origin -- is uniform over the workgroup.  One G x G LDS array of 32-bit words serves three
 //                             times: cleared to 0 it takes the frame's keys (pass 1: depth in 16-byte loads where the image and
@@ -11,16 +11,19 @@
 //                             LDS word; the scan then looks its columns up in LDS.  A slot is read and written by the same thread
 //                             in pass 2, so the map is updated in place without a second copy.
 //   elevation_scan_kernel     step 8 alone, the map read from global memory.
-// Both run scan_rows(), so they agree on the bits.  The known count is a ballot / popcount per wave into one LDS int per wave,
+//   elevation_fill_kernel<G>  the min-fill of the window and step 8 on the filled window (described at the kernel).
+// All run scan_rows(), so they agree on the bits.  The known count is a ballot / popcount per wave into one LDS int per wave,
 // summed by thread 0: no atomics on global memory, no float atomics.
 // LDS: 4 G^2 bytes of map + 8 wave counters (32 bytes): 65568 bytes at G = 128 (two workgroups per CU), 16416 at G = 64.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/rover_hip.h"
 #include "../../include/rover_elevation.h"
+#include "../../include/rover_elevation_fill.h"
 #include "rover_internal.hpp"
 
 namespace {
@@ -94,11 +97,16 @@ __device__ __forceinline__ void splat(uint32_t *keys, const ElevArgs &A, const P
     atomicMax(&keys[((gy & (G - 1)) << log_g) | (gx & (G - 1))], key_of(wz));      // slot < G * G: both terms are masked
 }
 
+struct NoDist {};                 // scan_rows' `dist_of` of the step and scan kernels: no fill distance, no bytes written
+
 // Step 8 for the env of this workgroup: `load(slot)` is the map's float at a slot < G * G, (cx, cy) the centre of its window.
-template <class Load>
+// With a `dist_of` other than NoDist (the fill kernel), `dist_row[col]` (where `dist_row` is not NULL) takes dist_of(slot) of a known
+// column and 255 of any other.
+template <class Load, class DistOf = NoDist>
 __device__ __forceinline__ void scan_rows(const ElevArgs &A, const Pose &P, int e, int G, int log_g, int cx, int cy, bool usable,
-                                          int *wave_known, Load load)
+                                          int *wave_known, Load load, uint8_t *dist_row = nullptr, DistOf dist_of = DistOf())
 {
+    constexpr bool WITH_DIST = !std::is_same<DistOf, NoDist>::value;
     const rover_elevation_cfg &c = A.cfg;
     const int tid = threadIdx.x, cols = A.nx * A.ny;
     float *row = A.scan_out + (size_t)e * (size_t)A.scan_pitch;
@@ -118,6 +126,7 @@ __device__ __forceinline__ void scan_rows(const ElevArgs &A, const Pose &P, int 
         bool known = false;
         if (col < cols) {
             float out = c.unknown_value;
+            uint8_t dist = 255;
             if (usable) {
                 const int i = col / A.nx, j = col - i * A.nx;
                 const float ox = A.ray_x[j], oy = A.ray_y[i];
@@ -126,16 +135,21 @@ __device__ __forceinline__ void scan_rows(const ElevArgs &A, const Pose &P, int 
                 if (finite_f(x) && finite_f(y)) {
                     const int gx = cell_of(x, c.inv_cell), gy = cell_of(y, c.inv_cell);
                     if ((uint32_t)gx - (uint32_t)lo_x < (uint32_t)G && (uint32_t)gy - (uint32_t)lo_y < (uint32_t)G) {
-                        const float h = load(((gy & (G - 1)) << log_g) | (gx & (G - 1)));
+                        const int slot = ((gy & (G - 1)) << log_g) | (gx & (G - 1));
+                        const float h = load(slot);
                         if (h == h) {
                             known = true;
                             out = __fsub_rn(__fsub_rn(P.pz, h), c.height_offset);
+                            if constexpr (WITH_DIST) dist = dist_of(slot);
                         }
                     }
                 }
             }
             row[col] = out;
             if (known_row) known_row[col] = known ? 1 : 0;
+            if constexpr (WITH_DIST) {
+                if (dist_row) dist_row[col] = dist;
+            }
         }
         count += __popcll(__ballot(known));
     }
@@ -247,6 +261,131 @@ __global__ __launch_bounds__(TT) void elevation_scan_kernel(ElevArgs A)
     const Pose P = load_pose(A, e);
     const float *map = A.map + ((size_t)e << (2 * A.log_g));
     scan_rows(A, P, e, G, A.log_g, A.origin[2 * e], A.origin[2 * e + 1], P.ok, wave_known, [=](int s) { return map[s]; });
+}
+
+// ---- the min-fill (include/rover_elevation_fill.h)
+struct FillArgs {
+    ElevArgs A;                   // depth, ray_b, reset_*, known_out NULL; map and origin only read
+    float *filled_out;
+    uint8_t *dist_out, *scan_dist_out;
+    int iterations;
+};
+
+// One workgroup per env.  LDS: the window's heights (G x G floats) and fill distances (G x G bytes), both in WINDOW order (row i
+// over y, column j over x), and two copies of a bit image of the window, one bit per cell and ROWW 32-bit words per row: "this
+// cell had a height before the sweep began".  A thread owns a run of RUN consecutive cells of one row, all within one word of
+// the bit image.  In sweep k it reads the words over its run, and the last and first bit of the words beside it, for the rows
+// i - 1, i, i + 1 of the image of sweep k - 1 (3 to 9 LDS reads, whatever the run's length); OR-ed and widened by one bit to
+// either side they say which of its unknown cells have a neighbour that counts, and only those cells (each once in the launch)
+// read their neighbours' heights.  No bit is set outside the window, so no sweep tests a bound, and rows of the image do not
+// wrap: the seam is no neighbourhood.  The heights and distances are updated in place: a cell written in sweep k has its bit in
+// the OTHER image only (the thread ORs this sweep's and the last sweep's new bits into it, which makes it the state after sweep
+// k), so readers of sweep k pass over it and one barrier per sweep orders everything.  `last[k & 1] = k` is the vote "sweep k
+// filled something": written before barrier k, read behind it, and written again in sweep k + 2 at the earliest.
+template <int G>
+__global__ __launch_bounds__(TT) void elevation_fill_kernel(FillArgs F)
+{
+    constexpr int LOG_G = G == 8 ? 3 : G == 16 ? 4 : G == 32 ? 5 : G == 64 ? 6 : 7;
+    constexpr int CELLS = G * G, RUN = CELLS >= TT ? CELLS / TT : 1, ROWW = G >= 32 ? G / 32 : 1;
+    static_assert(RUN <= 32 && (RUN & (RUN - 1)) == 0 && RUN <= G, "a run lies within one word of one row");
+    __shared__ __attribute__((aligned(16))) float hgt[CELLS];
+    __shared__ __attribute__((aligned(4))) uint8_t dst[CELLS];
+    __shared__ uint32_t had[2][G * ROWW];
+    __shared__ int wave_known[WAVES];
+    __shared__ int last[2];
+    const ElevArgs &A = F.A;
+    const int tid = threadIdx.x, e = blockIdx.x;
+    const int cx = A.origin[2 * e], cy = A.origin[2 * e + 1];
+    const int lo_x = cx - G / 2, lo_y = cy - G / 2;
+    const float *map = A.map + (size_t)e * CELLS;
+
+    for (int p = tid; p < 2 * G * ROWW; p += TT) (&had[0][0])[p] = 0u;
+    if (tid == 0) last[0] = last[1] = 0;
+    for (int s = tid; s < CELLS; s += TT) {                          // slot order in global memory, window order in LDS
+        const int j = ((s & (G - 1)) - lo_x) & (G - 1), i = ((s >> LOG_G) - lo_y) & (G - 1);
+        const float v = map[s];
+        hgt[(i << LOG_G) | j] = v;
+        dst[(i << LOG_G) | j] = v != v ? 255 : 0;
+    }
+    __syncthreads();
+
+    // this thread's run: cells first ... first + RUN - 1 of row i, bits `mine` of word w of that row
+    const bool owner = tid * RUN < CELLS;                            // G = 8, 16: fewer cells than threads
+    const int first = owner ? tid * RUN : 0, i = first >> LOG_G, j0 = first & (G - 1), w = j0 >> 5;
+    const uint32_t mine = (uint32_t)((1ull << RUN) - 1ull) << (j0 & 31);
+    uint32_t unknown = 0u;
+    if (owner) {
+        uint32_t bits = 0u;
+#pragma unroll
+        for (int r = 0; r < RUN; ++r)
+            if (dst[first + r] == 0) bits |= 1u << ((j0 + r) & 31);
+        unknown = mine & ~bits;
+        if (bits) {
+            atomicOr(&had[0][i * ROWW + w], bits);
+            atomicOr(&had[1][i * ROWW + w], bits);
+        }
+    }
+    __syncthreads();
+
+    uint32_t fresh = 0u;                                             // the bits this thread set in the sweep before
+    for (int k = 1; k <= F.iterations; ++k) {                        // uniform: the bound is an argument, the exit a vote
+        const uint32_t *cur = had[(k - 1) & 1];
+        uint32_t *next = had[k & 1];
+        uint32_t made = 0u;
+        if (unknown) {
+            // per row i - 1, i, i + 1: bit b + 1 of x[.] is the cell of bit b of word w; bits 0 and 33 are the cells beside the word
+            uint64_t x[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const int row = i + r - 1;
+                uint64_t v = 0;
+                if (row >= 0 && row < G) {
+                    const uint32_t *rw = cur + row * ROWW;
+                    v = (uint64_t)rw[w] << 1;
+                    if (ROWW > 1 && w > 0) v |= rw[w - 1] >> 31;
+                    if (ROWW > 1 && w < ROWW - 1) v |= (uint64_t)(rw[w + 1] & 1u) << 33;
+                }
+                x[r] = v;
+            }
+            const uint64_t any = x[0] | x[1] | x[2];
+            for (uint32_t m = unknown & (uint32_t)((any | (any >> 1) | (any >> 2)) & 0xFFFFFFFFu); m != 0u; m &= m - 1u) {
+                const int b = __ffs((int)m) - 1, c = (i << LOG_G) | ((w << 5) + b);
+                uint32_t best = 0xFFFFFFFFu;                         // above the key of every float that is not a NaN
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const uint32_t t = (uint32_t)(x[r] >> b) & 7u;   // the cells left of, at and right of column b in this row
+#pragma unroll
+                    for (int q = 0; q < 3; ++q)
+                        if (t & (1u << q)) best = min(best, key_of(hgt[c + (r - 1) * G + (q - 1)]));
+                }
+                hgt[c] = value_of(best);
+                dst[c] = (uint8_t)k;
+                made |= 1u << b;
+            }
+            unknown &= ~made;
+        }
+        if (made | fresh) atomicOr(&next[i * ROWW + w], made | fresh);
+        fresh = made;
+        if (made) last[k & 1] = k;
+        __syncthreads();
+        if (last[k & 1] != k) break;
+    }
+
+    if (F.filled_out || F.dist_out) {                                // kernel arguments: uniform
+        float *filled = F.filled_out ? F.filled_out + (size_t)e * CELLS : nullptr;
+        uint8_t *dist = F.dist_out ? F.dist_out + (size_t)e * CELLS : nullptr;
+        for (int s = tid; s < CELLS; s += TT) {
+            const int j = ((s & (G - 1)) - lo_x) & (G - 1), r = ((s >> LOG_G) - lo_y) & (G - 1);
+            if (filled) filled[s] = hgt[(r << LOG_G) | j];
+            if (dist) dist[s] = dst[(r << LOG_G) | j];
+        }
+    }
+    if (!A.scan_out) return;
+    const Pose Q = load_pose(A, e);
+    auto at = [=](int s) { return ((((s >> LOG_G) - lo_y) & (G - 1)) << LOG_G) | (((s & (G - 1)) - lo_x) & (G - 1)); };
+    scan_rows(A, Q, e, G, LOG_G, cx, cy, Q.ok, wave_known,
+              [&](int s) { const int c = at(s); return dst[c] < 255 ? hgt[c] : __uint_as_float(QNAN); },
+              F.scan_dist_out ? F.scan_dist_out + (size_t)e * (size_t)(A.nx * A.ny) : nullptr, [&](int s) { return dst[at(s)]; });
 }
 
 bool pos_ok(float v) { return std::isfinite(v) && v > 0.0f; }
@@ -385,6 +524,60 @@ int rover_elevation_scan(const rover_elevation_cfg *cfg, const float *pos, const
     A.hw = 0; A.nx = nx; A.ny = ny; A.log_g = log2_of(cfg->grid);
     hipLaunchKernelGGL(elevation_scan_kernel, dim3((unsigned)n), dim3(TT), 0, static_cast<hipStream_t>(stream), A);
     return launched("elevation_scan_kernel launch: %s");
+}
+
+size_t rover_elevation_fill_cfg_bytes(void) { return sizeof(rover_elevation_fill_cfg); }
+
+int rover_elevation_fill(const rover_elevation_cfg *cfg, const rover_elevation_fill_cfg *fill, const float *pos, const float *quat,
+                         int64_t comp_stride, int64_t env_stride, const float *map, const int32_t *origin, const float *ray_x,
+                         int32_t nx, const float *ray_y, int32_t ny, float *scan_out, int64_t scan_pitch, uint8_t *scan_dist_out,
+                         int32_t *count_out, float *filled_out, uint8_t *dist_out, int32_t n, void *stream)
+{
+    static const char who[] = "rover_elevation_fill: %s";
+    auto refuse = [](const char *why) { return rover_internal_fail(ROVER_ERR_INVALID, who, why); };
+    if (!fill) return refuse("NULL argument");
+    if (!scan_out && !filled_out) return refuse("NULL argument (one of scan_out and filled_out is required)");
+    if (!scan_out && map) {                                          // no scan: the ray tables are not read and may be NULL
+        ray_x = ray_x ? ray_x : map;
+        ray_y = ray_y ? ray_y : map;
+    }
+    if (int rc = check_common(who, cfg, pos, quat, comp_stride, env_stride, map, origin, ray_x, nx, ray_y, ny, scan_out, scan_pitch,
+                              count_out, n))
+        return rc;
+    if (fill->iterations < 1 || fill->iterations > ROVER_ELEVATION_FILL_MAX_ITERATIONS) return refuse("iterations must be in [1, 254]");
+    if (reinterpret_cast<uintptr_t>(filled_out) & 3) return refuse("float and int32 pointers must be 4-byte aligned");
+    if (filled_out) {
+        const uint64_t map_bytes = (uint64_t)n * (uint64_t)cfg->grid * (uint64_t)cfg->grid * 4u;
+        if (overlap(map, map_bytes, filled_out, map_bytes)) return refuse("map and filled_out overlap");
+        if (scan_out) {
+            const uint64_t scan_bytes = ((uint64_t)(n - 1) * (uint64_t)scan_pitch + (uint64_t)nx * (uint64_t)ny) * 4u;
+            if (overlap(filled_out, map_bytes, scan_out, scan_bytes)) return refuse("filled_out and scan_out overlap");
+        }
+    }
+    int dev;
+    if (int rc = device_of(map, &dev, true)) return rc;
+    DeviceGuard guard(dev);
+    FillArgs F;
+    ElevArgs &A = F.A;
+    A.cfg = *cfg;
+    A.depth = nullptr; A.ray_b = nullptr; A.pos = pos; A.quat = quat; A.ray_x = ray_x; A.ray_y = ray_y;
+    A.reset_a = nullptr; A.reset_b = nullptr;
+    A.map = const_cast<float *>(map); A.origin = const_cast<int32_t *>(origin);
+    A.scan_out = scan_out; A.known_out = nullptr; A.count_out = scan_out ? count_out : nullptr;
+    A.pitch = 0; A.comp_stride = (long long)comp_stride; A.env_stride = (long long)env_stride;
+    A.scan_pitch = (long long)scan_pitch;
+    A.hw = 0; A.nx = nx; A.ny = ny; A.log_g = log2_of(cfg->grid);
+    F.filled_out = filled_out; F.dist_out = dist_out; F.scan_dist_out = scan_out ? scan_dist_out : nullptr;
+    F.iterations = fill->iterations;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (cfg->grid) {
+    case 8:   hipLaunchKernelGGL(elevation_fill_kernel<8>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+    case 16:  hipLaunchKernelGGL(elevation_fill_kernel<16>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+    case 32:  hipLaunchKernelGGL(elevation_fill_kernel<32>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+    case 64:  hipLaunchKernelGGL(elevation_fill_kernel<64>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+    default:  hipLaunchKernelGGL(elevation_fill_kernel<128>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+    }
+    return launched("elevation_fill_kernel launch: %s");
 }
 
 }  // extern "C"

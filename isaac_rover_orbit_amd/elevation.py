@@ -8,6 +8,8 @@ depth image with a caller-supplied table of Body-frame rays, reduce the points t
 the map and read the scan out of the result.  ``RoverEnv`` runs it behind the camera's render -> sensor -> noise / clip chain when
 ``cfg.elevation`` is set and publishes ``extras["elevation_scan"]`` / ``["elevation_known"]`` / ``["elevation_count"]``;
 ``policy_rows`` puts such a scan into observation rows, so a trained actor can be evaluated on what the camera can see.
+``ElevationMap.fill`` is the inpainting pass behind it (``include/rover_elevation_fill.h``): one more launch that fills the unknown
+cells of the window with the minimum of their known neighbours, ring by ring, and reports how far each value was carried.
 
 ``TorchElevationMap`` is the same interface in plain numpy on float32, every operation in the header's order: the specification
 of the kernel, compared bit for bit, and it runs on the CPU.
@@ -165,8 +167,9 @@ class TorchElevationMap(_ElevationBase):
             valid &= np.isfinite(wx) & np.isfinite(wy) & np.isfinite(wz)
         return valid, wx, wy, wz
 
-    def _read(self, mp, origin, pos, quat, ok):
-        """Step 8 on ``mp`` / ``origin``: (scan (n, ny * nx), known uint8, count int32)."""
+    def _read(self, mp, origin, pos, quat, ok, dist=None):
+        """Step 8 on ``mp`` / ``origin``: (scan (n, ny * nx), known uint8, count int32).  With ``dist`` (the fill's bytes per slot) a
+        cell is known where its dist is below 255, and the middle result is the columns' dist, 255 where unknown."""
         ft, n, G = self.ft, self.num_envs, self.grid
         with np.errstate(all="ignore"):
             w, x, y, z = (quat[:, i] for i in range(4))
@@ -183,12 +186,14 @@ class TorchElevationMap(_ElevationBase):
         lo = origin.astype(np.int64) - G // 2
         dx, dy = gx - lo[:, 0, None, None], gy - lo[:, 1, None, None]
         inside = fin & (dx >= 0) & (dx < G) & (dy >= 0) & (dy < G)
-        h = mp[np.arange(n)[:, None, None], gy & (G - 1), gx & (G - 1)]
-        known = inside & ~np.isnan(h)
+        at = (np.arange(n)[:, None, None], gy & (G - 1), gx & (G - 1))
+        h = mp[at]
+        known = inside & (~np.isnan(h) if dist is None else dist[at] < 255)
         with np.errstate(all="ignore"):
             out = np.where(known, (pos[:, 2, None, None] - h) - self.height_offset, self.unknown_value).astype(ft)
+        mid = known.astype(np.uint8) if dist is None else np.where(known, dist[at], 255).astype(np.uint8)
         known = known.reshape(n, -1)
-        return out.reshape(n, -1), known.astype(np.uint8), known.sum(1).astype(np.int32)
+        return out.reshape(n, -1), mid.reshape(n, -1), known.sum(1).astype(np.int32)
 
     # --------------------------------------------------------------------------------------------------------- methods
     def update(self, depth, pos, quat, reset=(None, None), scan_out=None, known_out=None, count_out=None):
@@ -237,9 +242,46 @@ class TorchElevationMap(_ElevationBase):
         pos, quat, ok = self._pose(pos, quat)
         return self._emit(self._read(self.map, self.origin, pos, quat, ok), scan_out, known_out, count_out)
 
+    def fill_window(self, iterations: int):
+        """Steps 1 - 3 of include/rover_elevation_fill.h on ``map`` / ``origin``, which stay as they are: (filled (n, G, G) float32,
+        dist (n, G, G) uint8), both in the map's slot order."""
+        if self.float64:
+            raise ValueError("the fill is specified on float32 (its minimum is one of key bits)")
+        if not 1 <= int(iterations) <= _lib.ELEVATION_FILL_MAX_ITERATIONS:
+            raise ValueError(f"iterations must be in [1, {_lib.ELEVATION_FILL_MAX_ITERATIONS}]")
+        n, G = self.num_envs, self.grid
+        lo = self.origin.astype(np.int64) - G // 2
+        w = np.arange(G, dtype=np.int64)
+        at = (np.arange(n)[:, None, None], ((lo[:, 1, None] + w) & (G - 1))[:, :, None], ((lo[:, 0, None] + w) & (G - 1))[:, None, :])
+        h = self.map[at]                                                     # window order: [e, i over y, j over x]
+        dist = np.where(np.isnan(h), 255, 0).astype(np.int64)
+        none = np.uint32(0xFFFFFFFF)                                         # above the key of every float that is not a NaN
+        for k in range(1, int(iterations) + 1):
+            framed = np.full((n, G + 2, G + 2), none, dtype=np.uint32)       # the frame: outside the window nothing counts
+            framed[:, 1:-1, 1:-1] = np.where(dist < k, self.keys(h), none)
+            best = np.minimum.reduce([framed[:, 1 + di:1 + di + G, 1 + dj:1 + dj + G]
+                                      for di in (-1, 0, 1) for dj in (-1, 0, 1) if di or dj])
+            take = (dist == 255) & (best != none)
+            if not take.any():
+                break
+            h = np.where(take, self.values(best), h)
+            dist = np.where(take, k, dist)
+        filled, cell_dist = np.empty_like(self.map), np.empty(self.map.shape, dtype=np.uint8)
+        filled[at], cell_dist[at] = h, dist
+        return filled, cell_dist
+
+    def fill(self, pos, quat, scan_out=None, dist_out=None, count_out=None, filled_out=None, cell_dist_out=None, iterations=None):
+        """The min-fill of the map's window and the scan of the filled window (include/rover_elevation_fill.h); ``iterations``
+        defaults to the cfg's ``fill_iterations``.  Returns (scan, dist (n, rays) uint8, count, filled (n, G, G), cell_dist
+        (n, G, G) uint8)."""
+        filled, cell_dist = self.fill_window(self.map_cfg.fill_iterations if iterations is None else iterations)
+        pos, quat, ok = self._pose(pos, quat)
+        res = (*self._read(filled, self.origin, pos, quat, ok, dist=cell_dist), filled, cell_dist)
+        return self._emit(res, scan_out, dist_out, count_out, filled_out, cell_dist_out)
+
     @staticmethod
-    def _emit(res, scan_out, known_out, count_out):
-        for src, dst in zip(res, (scan_out, known_out, count_out)):
+    def _emit(res, *outs):
+        for src, dst in zip(res, outs):
             if dst is not None:
                 (dst.numpy() if isinstance(dst, torch.Tensor) else dst)[...] = src.reshape(dst.shape)
         return res
@@ -342,6 +384,32 @@ class ElevationMap(_ElevationBase):
                       self.origin.data_ptr(), self.ray_x.data_ptr(), self.nx, self.ray_y.data_ptr(), self.ny, s_ptr, int(s_pitch),
                       _fused.ptr(outs[1]), _fused.ptr(outs[2]), self.num_envs)
         return outs
+
+    def fill(self, pos, quat, scan_out=None, dist_out=None, count_out=None, filled_out=None, cell_dist_out=None, iterations=None):
+        """One asynchronous ``rover_elevation_fill`` launch: the min-fill of the map's window, at most ``iterations`` cells far
+        (default: the cfg's ``fill_iterations``), and the scan of the filled window.  ``map`` and ``origin`` are only read.
+        ``scan_out`` / ``dist_out`` (uint8, 0 measured, k filled in sweep k, 255 unknown) / ``count_out`` as ``update``'s three,
+        allocated where the caller gives none.  ``filled_out`` (n, G, G) float32 and ``cell_dist_out`` (n, G, G) uint8, both
+        contiguous and in the map's slot order, are written only where given (``True``: allocated here).  Returns (scan, dist,
+        count, filled, cell_dist), the last two ``None`` where not asked for."""
+        n, G, dev = self.num_envs, self.grid, self.map.device
+        fc = _lib.ElevationFillCfg(int(self.map_cfg.fill_iterations if iterations is None else iterations))
+        if not 1 <= fc.iterations <= _lib.ELEVATION_FILL_MAX_ITERATIONS:
+            raise ValueError(f"iterations must be in [1, {_lib.ELEVATION_FILL_MAX_ITERATIONS}]")
+        p_ptr, q_ptr, cs, es = self._pose(pos, quat)
+        outs, s_ptr, s_pitch = self._outs(scan_out, dist_out, count_out)
+        if filled_out is True:
+            filled_out = torch.empty((n, G, G), dtype=torch.float32, device=dev)
+        if cell_dist_out is True:
+            cell_dist_out = torch.empty((n, G, G), dtype=torch.uint8, device=dev)
+        for t, dt, nm in ((filled_out, torch.float32, "filled_out"), (cell_dist_out, torch.uint8, "cell_dist_out")):
+            if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev or t.dtype != dt or
+                                  not t.is_contiguous() or t.numel() != n * G * G):
+                raise ValueError(f"{nm} must be a contiguous {dt} cuda tensor of {n * G * G} values on the map's device")
+        _fused.launch("rover_elevation_fill", dev, self.cfg, fc, p_ptr, q_ptr, cs, es, self.map.data_ptr(), self.origin.data_ptr(),
+                      self.ray_x.data_ptr(), self.nx, self.ray_y.data_ptr(), self.ny, s_ptr, int(s_pitch), _fused.ptr(outs[1]),
+                      _fused.ptr(outs[2]), _fused.ptr(filled_out), _fused.ptr(cell_dist_out), n)
+        return (*outs, filled_out, cell_dist_out)
 
     def clear(self, mask=None):
         """All maps (or those of ``mask``) back to unknown."""

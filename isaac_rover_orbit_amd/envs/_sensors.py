@@ -15,6 +15,7 @@ from ..lidar import Lidar, elevation_geometry
 from ..obs_post import DEPTH_TAG, LIDAR_TAG, ObsPost, image_segments, lidar_segments
 
 KEYS = ("depth", "depth_valid", "rgb", "lidar_range", "lidar_hits_w", "elevation_scan", "elevation_known", "elevation_count")
+FILL_KEYS = ("elevation_scan_filled", "elevation_fill_dist", "elevation_filled_count")      # only under ElevationMapCfg.fill
 
 
 class Rotating:
@@ -34,18 +35,20 @@ class Rotating:
 class SensorRig:
     """``host`` (the env) has ``extras``, ``common_step_counter`` and ``call_counter``; ``for_env`` builds the device parts, which
     are plain attributes: a bench switches a stage off by setting it to ``None``.  ``render(camera_cfg, workspace, buf)`` fills the
-    (N, H, W) ``buf``; ``image``: (H, W); ``pose``: the (pos, quat) views the map reads; ``map_source``: "camera" or "lidar"."""
+    (N, H, W) ``buf``; ``image``: (H, W); ``pose``: the (pos, quat) views the map reads; ``map_source``: "camera" or "lidar"; ``fill_iterations``: 0, or the sweeps
+    of the min-fill launch that follows every map launch (``elevation.fill``) into buffers of its own."""
 
     def __init__(self, host, device="cpu", num_envs: int = 0, nbuf: int = 2, render=None, camera_cfg=None, workspace=None, image=None,
                  depth_sensor=None, depth_post=None, camera_every: int = 1, lidar=None, lidar_post=None, lidar_hits: bool = False,
-                 lidar_every: int = 1, elevation=None, map_source: str = "camera", unknown_value: float = 0.0, pose=None):
+                 lidar_every: int = 1, elevation=None, map_source: str = "camera", unknown_value: float = 0.0, pose=None, fill_iterations: int = 0):
         self.host, self._render, self.camera_cfg, self.workspace = host, render, camera_cfg, workspace
         self.depth_sensor, self.depth_post, self.camera_every = depth_sensor, depth_post, int(camera_every)
         self.lidar, self.lidar_post, self.lidar_every = lidar, lidar_post, int(lidar_every)
         self.elevation, self.map_source, self._pose = elevation, map_source, pose
+        self.fill_iterations = int(fill_iterations) if elevation is not None else 0
         self.active = camera_cfg is not None or lidar is not None
         ex, n, inf = host.extras, int(num_envs), float("inf")
-        for key in KEYS:                                                   # what the rig before this one published
+        for key in KEYS + FILL_KEYS:                                       # what the rig before this one published
             ex.pop(key, None)
         full = lambda shape, value, dtype=torch.float32: torch.full(shape, value, dtype=dtype, device=device)      # noqa: E731
         if camera_cfg is not None:       # extras["depth"]: the (N, W, H) view of the row-major (N, H, W) image the kernels write
@@ -59,6 +62,9 @@ class SensorRig:
             self._maps = Rotating(ex, KEYS[5:], lambda: (full((n, elevation.columns), float(unknown_value)),
                                                          full((n, elevation.columns), 0, torch.uint8), full((n,), 0, torch.int32)), nbuf)
             self._mask = full((n,), 0, torch.uint8)                        # the envs of a partial reset
+        if self.fill_iterations:
+            self._fills = Rotating(ex, FILL_KEYS, lambda: (full((n, elevation.columns), float(unknown_value)),
+                                                           full((n, elevation.columns), 255, torch.uint8), full((n,), 0, torch.int32)), nbuf)
 
     @classmethod
     def for_env(cls, env) -> "SensorRig":
@@ -69,7 +75,8 @@ class SensorRig:
         keyed = {"seed": int(cfg.seed), "env_id_offset": int(cfg.env_id_offset)}
         kw = {"pose": (env.state[_lib.POS:_lib.POS + 3].t(), env.state[_lib.QUAT:_lib.QUAT + 4].t())}
         if emc is not None:
-            kw.update(map_source=getattr(emc, "source", "camera"), unknown_value=emc.unknown_value)
+            kw.update(map_source=getattr(emc, "source", "camera"), unknown_value=emc.unknown_value,
+                      fill_iterations=emc.fill_iterations if getattr(emc, "fill", "none") != "none" else 0)
         if cam is not None:
             native, noisy = cam.to_native(), cam.noise is not None or cam.clip is not None
             kw.update(camera_cfg=native, image=(int(cam.height), int(cam.width)), camera_every=cam.every_n_steps,
@@ -132,6 +139,9 @@ class SensorRig:
         """One map launch into the next set of outputs; ``frame`` None: scroll and scan only."""
         scan, known, count = self._maps.next()
         self.elevation.update(frame, *self._pose, reset=reset, scan_out=scan, known_out=known, count_out=count)
+        if self.fill_iterations:                                           # the same pose, the map the launch above left
+            scan, dist, count = self._fills.next()
+            self.elevation.fill(*self._pose, scan_out=scan, dist_out=dist, count_out=count, iterations=self.fill_iterations)
 
     def _lidar_update(self, force: bool, reset):
         buf = None
