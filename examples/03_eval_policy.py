@@ -21,6 +21,12 @@ neighbours at most ``--map_fill_iterations`` cells far, the actor reads ``extras
 the mean measured and filled column counts:
 
     python examples/03_eval_policy.py --checkpoint best_agent.pt --scan_source elevation --map_fill min --map_fill_iterations 20
+
+``--map_cost`` derives slope, step height, roughness and a traversability cost from the map (from the filled window under
+``--map_fill min``) over neighbourhoods of ``--map_cost_radius`` cells (``ElevationMapCfg.traverse``); the summary adds the mean
+cost under the scan's columns and the mean number of lethal columns.  The actor's input does not change:
+
+    python examples/03_eval_policy.py --checkpoint best_agent.pt --scan_source elevation --map_fill min --map_cost --map_cost_radius 2
 """
 import argparse
 import os
@@ -55,6 +61,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="inpaint the map behind every update: unknown cells take the minimum of their known neighbours, and the actor "
                          "reads the filled scan")
     ap.add_argument("--map_fill_iterations", type=int, default=32, metavar="N", help="how many cells far a height is carried at the most")
+    ap.add_argument("--map_cost", action="store_true",
+                    help="slope, step, roughness and cost layers behind every map update (needs --scan_source elevation); reported only")
+    ap.add_argument("--map_cost_radius", type=int, default=2, metavar="R", help="the layers' neighbourhood is (2 R + 1)^2 cells, R in [1, 4]")
     ap.add_argument("--lidar_channels", type=int, default=32, help="rings of the lidar")
     ap.add_argument("--lidar_vfov", type=float, nargs=2, default=(-60.0, -10.0), metavar=("LO", "HI"),
                     help="elevation angles of the lowest and the highest ring (degrees)")
@@ -66,6 +75,8 @@ def make_cfg(args) -> RoverEnvCfg:
     """The env cfg of the flags: with ``--scan_source elevation`` the camera, its sensor model (None without a --depth_* flag) and
     the map -- or, with ``--map_source lidar``, the lidar of the ``--lidar_*`` flags and the map behind it; otherwise exactly the
     default."""
+    if args.map_cost and args.scan_source != "elevation":
+        raise ValueError("--map_cost needs --scan_source elevation")
     cfg = RoverEnvCfg()
     cfg.scene.num_envs = args.num_envs
     cfg.terrain.kind = "custom"
@@ -87,16 +98,20 @@ def make_cfg(args) -> RoverEnvCfg:
         cfg.elevation = ElevationMapCfg(alpha=args.map_alpha)
     if cfg.elevation is not None:
         cfg.elevation.fill, cfg.elevation.fill_iterations = args.map_fill, args.map_fill_iterations
+        if args.map_cost:
+            from isaac_rover_orbit_amd.cfg import TraverseCfg
+            cfg.elevation.traverse = TraverseCfg(radius=args.map_cost_radius)
     return cfg
 
 
 def eval_on_map(env, actor, steps: int):
     """The loop of ``main`` with the actor on ``policy_rows(obs, extras["elevation_scan"])`` -- under ``--map_fill min`` on
     ``extras["elevation_scan_filled"]``; also the mean known share and the mean measured and filled column counts (the last
-    ``None`` without a fill)."""
+    ``None`` without a fill), and under ``--map_cost`` (mean cost of the columns that have one, mean lethal columns per scan), else
+    ``None``."""
     from isaac_rover_orbit_amd.elevation import policy_rows
     obs, info = env.reset()
-    counts, episodes, known, filled = torch.zeros(4), 0.0, 0.0, 0.0
+    counts, episodes, known, filled, cost, lethal = torch.zeros(4), 0.0, 0.0, 0.0, 0.0, 0.0
     rows = torch.empty_like(obs["policy"])
     key = "elevation_scan_filled" if "elevation_scan_filled" in info else "elevation_scan"
     for _ in range(steps):
@@ -107,11 +122,16 @@ def eval_on_map(env, actor, steps: int):
         known += float(info["elevation_count"].float().mean())
         if "elevation_filled_count" in info:
             filled += float(info["elevation_filled_count"].float().mean())
+        if "elevation_cost" in info:
+            judged = info["elevation_cost_class"] > 0
+            cost += float(info["elevation_cost"][judged].mean()) if bool(judged.any()) else 0.0
+            lethal += float(info["elevation_lethal_count"].float().mean())
         if log[13] > 0:
             episodes += float(log[13])
             counts += log[7:11]
     steps = max(steps, 1)
-    return episodes, counts, known / steps / (rows.shape[1] - 4), (known / steps, filled / steps if "elevation_filled_count" in info else None)
+    return (episodes, counts, known / steps / (rows.shape[1] - 4), (known / steps, filled / steps if "elevation_filled_count" in info else None),
+            (cost / steps, lethal / steps) if "elevation_cost" in info else None)
 
 
 def main():
@@ -121,11 +141,13 @@ def main():
     env = RoverEnv(make_cfg(args), terrain=terrain)
     actor = RoverNet.from_checkpoint(args.checkpoint, role="policy")
     if args.scan_source == "elevation":
-        episodes, counts, known, (measured, filled) = eval_on_map(env, actor, args.steps)
+        episodes, counts, known, (measured, filled), cost = eval_on_map(env, actor, args.steps)
         print(f"episodes finished: {episodes:.0f}; terminations (time_out, success, far, collision): {counts.tolist()}; "
               f"mean known share of the scan: {known:.3f}")
         if filled is not None:
             print(f"mean measured columns per scan: {measured:.1f}; mean columns after the min-fill: {filled:.1f}")
+        if cost is not None:
+            print(f"mean cost of the columns with a verdict: {cost[0]:.3f}; mean lethal columns per scan: {cost[1]:.1f}")
         env.close()
         return
     obs, _ = env.reset()

@@ -78,6 +78,7 @@ EXPORTS = [
     "rover_depth_sensor_cfg_bytes", "rover_depth_sensor_apply",  # rover_depth_sensor.h
     "rover_elevation_cfg_bytes", "rover_elevation_step", "rover_elevation_scan",  # rover_elevation.h
     "rover_elevation_fill_cfg_bytes", "rover_elevation_fill",  # rover_elevation_fill.h
+    "rover_elevation_traverse_cfg_bytes", "rover_elevation_traverse",  # rover_elevation_traverse.h
     "rover_lidar_config_bytes", "rover_lidar_workspace_bytes", "rover_lidar_prepare", "rover_lidar_cast",  # rover_lidar.h
 ]
 POLICY_MAX_LAYERS = 8
@@ -307,6 +308,16 @@ class ElevationFillCfg(C.Structure):
     _fields_ = [("iterations", C.c_int32)]
 
 
+ELEVATION_TRAVERSE_MAX_RADIUS = 4
+
+
+class ElevationTraverseCfg(C.Structure):
+    """Mirror of ``struct rover_elevation_traverse_cfg`` (include/rover_elevation_traverse.h)."""
+    _fields_ = [("radius", C.c_int32), ("min_support", C.c_int32), ("slope_crit", C.c_float), ("step_crit", C.c_float),
+                ("rough_crit", C.c_float), ("w_slope", C.c_float), ("w_step", C.c_float), ("w_rough", C.c_float),
+                ("unknown_cost", C.c_float)]
+
+
 class LidarConfig(C.Structure):
     """Mirror of ``struct rover_lidar_config`` (include/rover_lidar.h)."""
     _fields_ = [("rays", C.c_int32), ("mount_pos", C.c_float * 3), ("near_clip", C.c_float), ("far_clip", C.c_float),
@@ -410,6 +421,7 @@ _MIRRORS = [("rover_config_bytes", RoverConfig), ("rover_lift_config_bytes", Lif
             ("rover_dagger_hparams_bytes", DaggerHparams), ("rover_dagger_state_bytes", DaggerState),
             ("rover_obs_post_segment_bytes", ObsPostSegment), ("rover_depth_sensor_cfg_bytes", DepthSensorCfg),
             ("rover_elevation_cfg_bytes", ElevationCfg), ("rover_elevation_fill_cfg_bytes", ElevationFillCfg),
+            ("rover_elevation_traverse_cfg_bytes", ElevationTraverseCfg),
             ("rover_lidar_config_bytes", LidarConfig)]
 
 
@@ -682,6 +694,9 @@ def load():
     lib.rover_elevation_fill_cfg_bytes.restype = C.c_size_t
     lib.rover_elevation_fill.argtypes = [C.POINTER(ElevationCfg), C.POINTER(ElevationFillCfg), vp, vp, C.c_int64, C.c_int64, vp, vp,
                                          vp, i32, vp, i32, vp, C.c_int64, vp, vp, vp, vp, i32, vp]
+    lib.rover_elevation_traverse_cfg_bytes.restype = C.c_size_t
+    lib.rover_elevation_traverse.argtypes = [C.POINTER(ElevationCfg), C.POINTER(ElevationTraverseCfg), vp, vp, C.c_int64, C.c_int64,
+                                             vp, vp, vp, i32, vp, i32, vp, C.c_int64, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.rover_lidar_config_bytes.restype = C.c_size_t
     lib.rover_lidar_workspace_bytes.argtypes = [vp]
     lib.rover_lidar_workspace_bytes.restype = C.c_size_t

@@ -57,6 +57,7 @@ HEADERS = [os.path.join(_PKG, "csrc", "rover_model.hpp"), os.path.join(_PKG, "cs
            os.path.join(os.path.dirname(_PKG), "include", "rover_depth_sensor.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_elevation.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_elevation_fill.h"),
+           os.path.join(os.path.dirname(_PKG), "include", "rover_elevation_traverse.h"),
            os.path.join(os.path.dirname(_PKG), "include", "rover_lidar.h")]
 OBJ_DIR = os.path.join(os.path.dirname(_PKG), "build", "obj")
 OUTPUT = os.path.join(_PKG, "librover_hip.so")

@@ -160,6 +160,51 @@ class DepthSensorCfg:
 
 
 @dataclass
+class TraverseCfg:
+    """Slope, step height, roughness and a traversability cost from the elevation map (include/rover_elevation_traverse.h): per
+    cell over its (2 ``radius`` + 1)^2 neighbourhood.  A cell is lethal when one of the three reaches its ``*_crit``; otherwise its
+    cost is the weighted sum of the three ratios.  The defaults are the implementer's choice, not tuned values."""
+    radius: int = 2                                    # cells, in [1, 4]
+    min_support: int = 1                               # usable cells (centre included) a cell needs, in [1, (2 radius + 1)^2]
+    slope_crit: float = 0.577                          # a tangent: tan 30 deg
+    step_crit: float = 0.3                             # m
+    rough_crit: float = 0.1                            # m
+    w_slope: float = 0.4
+    w_step: float = 0.4
+    w_rough: float = 0.2
+    unknown_cost: float = 1.0                          # what a scan column without a cost reads
+
+    def check(self):
+        """ValueError for what the library refuses, on the values as the fp32 struct holds them."""
+        f32 = lambda x: C.c_float(float(x)).value      # noqa: E731
+        for name in ("radius", "min_support"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"traverse {name} must be an integer")
+        if not 1 <= self.radius <= _lib.ELEVATION_TRAVERSE_MAX_RADIUS:
+            raise ValueError(f"traverse radius must be in [1, {_lib.ELEVATION_TRAVERSE_MAX_RADIUS}]")
+        if not 1 <= self.min_support <= (2 * self.radius + 1) ** 2:
+            raise ValueError("traverse min_support must be in [1, (2 radius + 1)^2]")
+        for name in ("slope_crit", "step_crit", "rough_crit"):
+            v = f32(getattr(self, name))
+            if not (math.isfinite(v) and v > 0.0):
+                raise ValueError(f"traverse {name} must be finite and > 0")
+        w = [f32(getattr(self, name)) for name in ("w_slope", "w_step", "w_rough")]
+        if not all(math.isfinite(v) and v >= 0.0 for v in w):
+            raise ValueError("traverse weights must be finite and >= 0")
+        if not f32(f32(w[0] + w[1]) + w[2]) <= 1.0:
+            raise ValueError("traverse weights must sum to at most 1 (in fp32, (w_slope + w_step) + w_rough)")
+        if math.isnan(f32(self.unknown_cost)):
+            raise ValueError("traverse unknown_cost must not be a NaN")
+
+    def to_native(self) -> "_lib.ElevationTraverseCfg":
+        self.check()
+        return _lib.ElevationTraverseCfg(int(self.radius), int(self.min_support), float(self.slope_crit), float(self.step_crit),
+                                         float(self.rough_crit), float(self.w_slope), float(self.w_step), float(self.w_rough),
+                                         float(self.unknown_cost))
+
+
+@dataclass
 class ElevationMapCfg:
     """A rolling, robot-centric elevation map built from the depth camera (include/rover_elevation.h, elevation.py): ``grid`` x
     ``grid`` world-anchored cells of ``cell`` metres around the rover, fed by the pixels within ``[range_min, range_max]``, the
@@ -177,10 +222,14 @@ class ElevationMapCfg:
     # their known neighbours, ring by ring, at most ``fill_iterations`` cells far; published next to the raw scan, never in its place
     fill: str = "none"
     fill_iterations: int = 32
+    # slope / step / roughness / cost layers behind every map update, after the fill if there is one (TraverseCfg); None: no launch
+    traverse: TraverseCfg | None = None
 
     def check(self):
         """ValueError for what the library refuses, on the values as the fp32 struct holds them."""
         f32 = lambda x: C.c_float(float(x)).value      # noqa: E731
+        if self.traverse is not None:
+            self.traverse.check()
         if self.source not in ("camera", "lidar"):
             raise ValueError("elevation source must be 'camera' or 'lidar'")
         if self.fill not in ("none", "min"):

@@ -1,7 +1,8 @@
 // elevation_kernels.hip -- the rolling elevation map from the depth camera (scroll, unproject, reduce, fuse, scan) as one launch
 // (gfx950 / CDNA4, wave64).
 //
-// See include/rover_elevation.h and include/rover_elevation_fill.h for the contracts and the operation order.  Three kernels:
+// See include/rover_elevation.h, include/rover_elevation_fill.h and include/rover_elevation_traverse.h for the contracts and the
+// operation order.  Five kernels:
 //   elevation_step_kernel<G>  one workgroup of 512 threads per env, so the env index -- and with it the pose, the reset flag and
 //                             the old origin -- is uniform over the workgroup.  One G x G LDS array of 32-bit words serves three
 //                             times: cleared to 0 it takes the frame's keys (pass 1: depth in 16-byte loads where the image and
@@ -12,9 +13,12 @@
 //                             in pass 2, so the map is updated in place without a second copy.
 //   elevation_scan_kernel     step 8 alone, the map read from global memory.
 //   elevation_fill_kernel<G>  the min-fill of the window and step 8 on the filled window (described at the kernel).
+//   elevation_traverse_kernel<G>, elevation_traverse_sparse_kernel<G>  slope, step, roughness and cost of a height window and
+//                             step 8 on the cost: for every cell, or only under the scan's columns (at the kernels).
 // All run scan_rows(), so they agree on the bits.  The known count is a ballot / popcount per wave into one LDS int per wave,
 // summed by thread 0: no atomics on global memory, no float atomics.
-// LDS: 4 G^2 bytes of map + 8 wave counters (32 bytes): 65568 bytes at G = 128 (two workgroups per CU), 16416 at G = 64.
+// LDS: 4 G^2 bytes of map + 8 wave counters (32 bytes): 65568 bytes at G = 128 (two workgroups per CU), 16416 at G = 64; the
+// traverse kernel holds two such images, 131104 bytes at G = 128 (one workgroup per CU).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,6 +28,7 @@
 #include "../../include/rover_hip.h"
 #include "../../include/rover_elevation.h"
 #include "../../include/rover_elevation_fill.h"
+#include "../../include/rover_elevation_traverse.h"
 #include "rover_internal.hpp"
 
 namespace {
@@ -99,12 +104,24 @@ __device__ __forceinline__ void splat(uint32_t *keys, const ElevArgs &A, const P
 
 struct NoDist {};                 // scan_rows' `dist_of` of the step and scan kernels: no fill distance, no bytes written
 
+// What scan_rows makes of a known column's float `h` and byte: the height kernels read (pos.z - h) - height_offset, count the known
+// columns and give an unknown column the byte 255; the traverse kernel reads the cost image (CostRead, at its kernel).
+struct HeightRead {
+    static constexpr uint8_t NO_BYTE = 255;
+    static __device__ __forceinline__ float value(const Pose &P, const rover_elevation_cfg &c, float h)
+    {
+        return __fsub_rn(__fsub_rn(P.pz, h), c.height_offset);
+    }
+    static __device__ __forceinline__ bool counts(bool known, uint8_t) { return known; }
+};
+
 // Step 8 for the env of this workgroup: `load(slot)` is the map's float at a slot < G * G, (cx, cy) the centre of its window.
-// With a `dist_of` other than NoDist (the fill kernel), `dist_row[col]` (where `dist_row` is not NULL) takes dist_of(slot) of a known
-// column and 255 of any other.
-template <class Load, class DistOf = NoDist>
+// With a `dist_of` other than NoDist (the fill and traverse kernels), `dist_row[col]` (where `dist_row` is not NULL) takes
+// dist_of(slot, h) of a known column and Read::NO_BYTE of any other.
+template <class Load, class DistOf = NoDist, class Read = HeightRead>
 __device__ __forceinline__ void scan_rows(const ElevArgs &A, const Pose &P, int e, int G, int log_g, int cx, int cy, bool usable,
-                                          int *wave_known, Load load, uint8_t *dist_row = nullptr, DistOf dist_of = DistOf())
+                                          int *wave_known, Load load, uint8_t *dist_row = nullptr, DistOf dist_of = DistOf(),
+                                          Read = Read())
 {
     constexpr bool WITH_DIST = !std::is_same<DistOf, NoDist>::value;
     const rover_elevation_cfg &c = A.cfg;
@@ -123,10 +140,10 @@ __device__ __forceinline__ void scan_rows(const ElevArgs &A, const Pose &P, int 
     int count = 0;                                                   // wave-uniform
     for (int base = tid & ~63; base < cols; base += TT) {            // wave-uniform trip count
         const int col = base + (tid & 63);
-        bool known = false;
+        bool known = false, counted = false;
         if (col < cols) {
             float out = c.unknown_value;
-            uint8_t dist = 255;
+            uint8_t dist = Read::NO_BYTE;
             if (usable) {
                 const int i = col / A.nx, j = col - i * A.nx;
                 const float ox = A.ray_x[j], oy = A.ray_y[i];
@@ -139,8 +156,8 @@ __device__ __forceinline__ void scan_rows(const ElevArgs &A, const Pose &P, int 
                         const float h = load(slot);
                         if (h == h) {
                             known = true;
-                            out = __fsub_rn(__fsub_rn(P.pz, h), c.height_offset);
-                            if constexpr (WITH_DIST) dist = dist_of(slot);
+                            out = Read::value(P, c, h);
+                            if constexpr (WITH_DIST) dist = dist_of(slot, h);
                         }
                     }
                 }
@@ -150,8 +167,9 @@ __device__ __forceinline__ void scan_rows(const ElevArgs &A, const Pose &P, int 
             if constexpr (WITH_DIST) {
                 if (dist_row) dist_row[col] = dist;
             }
+            counted = Read::counts(known, dist);
         }
-        count += __popcll(__ballot(known));
+        count += __popcll(__ballot(counted));
     }
     if (A.count_out) {                                               // kernel argument: uniform over the workgroup
         if ((tid & 63) == 0) wave_known[tid >> 6] = count;
@@ -385,7 +403,209 @@ __global__ __launch_bounds__(TT) void elevation_fill_kernel(FillArgs F)
     auto at = [=](int s) { return ((((s >> LOG_G) - lo_y) & (G - 1)) << LOG_G) | (((s & (G - 1)) - lo_x) & (G - 1)); };
     scan_rows(A, Q, e, G, LOG_G, cx, cy, Q.ok, wave_known,
               [&](int s) { const int c = at(s); return dst[c] < 255 ? hgt[c] : __uint_as_float(QNAN); },
-              F.scan_dist_out ? F.scan_dist_out + (size_t)e * (size_t)(A.nx * A.ny) : nullptr, [&](int s) { return dst[at(s)]; });
+              F.scan_dist_out ? F.scan_dist_out + (size_t)e * (size_t)(A.nx * A.ny) : nullptr, [&](int s, float) { return dst[at(s)]; });
+}
+
+// ---- slope, step, roughness and cost (include/rover_elevation_traverse.h)
+struct TraverseArgs {
+    ElevArgs A;                   // depth, ray_b, reset_*, known_out NULL; map (the heights) and origin only read; cfg.unknown_value
+                                  // holds unknown_cost, scan_out the cost scan, count_out the lethal count
+    rover_elevation_traverse_cfg t;
+    uint8_t *class_out;
+    float *slope_out, *step_out, *rough_out, *cost_out;
+};
+
+// The cost image holds a cell's verdict in one float: NaN = no verdict (class 0), the cost (<= 1) of a class-1 cell, and LETHAL,
+// which no cost can be, for a class-2 cell, whose cost is 1.
+constexpr float LETHAL = 2.0f;
+
+struct CostRead {                 // scan_rows' Read over the cost image: the cost itself, class 0 for no column, the class-2 count
+    static constexpr uint8_t NO_BYTE = 0;
+    static __device__ __forceinline__ float value(const Pose &, const rover_elevation_cfg &, float v) { return fminf(v, 1.0f); }
+    static __device__ __forceinline__ bool counts(bool, uint8_t cls) { return cls == 2; }
+};
+
+__device__ __forceinline__ float one_sided(float lo, float mid, float hi, float inv_cell)
+{
+    const bool l = finite_f(lo), u = finite_f(hi);
+    if (l && u) return __fmul_rn(__fsub_rn(hi, lo), __fmul_rn(0.5f, inv_cell));
+    if (u) return __fmul_rn(__fsub_rn(hi, mid), inv_cell);
+    if (l) return __fmul_rn(__fsub_rn(mid, lo), inv_cell);
+    return 0.0f;
+}
+
+// Step 2 and 3 of the header for the CH cells (i, j0) ... (i, j0 + CH - 1) of the window image `hgt`, all inside the window.  Per
+// neighbourhood row the strip of CH + 2 R heights over the cells is read from LDS once and every cell takes its 2 R + 1 of them
+// from registers; a cell's accumulation order is the header's (di outer, dj inner) whatever CH is, so a cell's bits do not depend
+// on who computes it, or with which neighbours.  `verdict` takes the image's float (see LETHAL); a layer of a cell without a
+// verdict is the quiet NaN.
+template <int G, int CH, int R>
+__device__ __forceinline__ void traverse_cells(const float *hgt, const rover_elevation_cfg &c, const rover_elevation_traverse_cfg &t,
+                                               int i, int j0, float (&slope)[CH], float (&step)[CH], float (&rough)[CH],
+                                               float (&verdict)[CH])
+{
+    constexpr int LOG_G = G == 8 ? 3 : G == 16 ? 4 : G == 32 ? 5 : G == 64 ? 6 : 7;
+    const float nan = __uint_as_float(QNAN);
+    auto at = [&](int row, int col) {                                // outside the window nothing is usable
+        return ((uint32_t)row < (uint32_t)G && (uint32_t)col < (uint32_t)G) ? hgt[(row << LOG_G) | col] : nan;
+    };
+    float hc[CH + 2], gx[CH], gy[CH], acc[CH];
+    uint32_t kmin[CH], kmax[CH];
+    int support[CH];
+#pragma unroll
+    for (int q = 0; q < CH + 2; ++q) hc[q] = at(i, j0 - 1 + q);
+#pragma unroll
+    for (int q = 0; q < CH; ++q) {
+        gx[q] = one_sided(hc[q], hc[q + 1], hc[q + 2], c.inv_cell);
+        gy[q] = one_sided(at(i - 1, j0 + q), hc[q + 1], at(i + 1, j0 + q), c.inv_cell);
+        acc[q] = 0.0f;
+        kmin[q] = 0xFFFFFFFFu;
+        kmax[q] = 0u;
+        support[q] = 0;
+    }
+    for (int di = -R; di <= R; ++di) {
+        const int row = i + di;
+        if ((uint32_t)row >= (uint32_t)G) continue;
+        float s[CH + 2 * R];
+#pragma unroll
+        for (int q = 0; q < CH + 2 * R; ++q) s[q] = at(row, j0 - R + q);
+        const float dy = __fmul_rn((float)di, c.cell);
+#pragma unroll
+        for (int q = 0; q < CH; ++q) {
+            const float along_y = __fmul_rn(gy[q], dy);
+#pragma unroll
+            for (int dj = -R; dj <= R; ++dj) {
+                const float h = s[q + dj + R];
+                if (!finite_f(h)) continue;
+                const uint32_t k = key_of(h);
+                kmin[q] = min(kmin[q], k);
+                kmax[q] = max(kmax[q], k);
+                ++support[q];
+                if (dj != 0 || di != 0) {
+                    const float res = __fsub_rn(__fsub_rn(h, hc[q + 1]),
+                                                __fadd_rn(__fmul_rn(gx[q], __fmul_rn((float)dj, c.cell)), along_y));
+                    acc[q] = __fadd_rn(acc[q], __fmul_rn(res, res));
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < CH; ++q) {
+        const bool none = !finite_f(hc[q + 1]) || support[q] < t.min_support;      // then what follows is computed and dropped
+        const float sl = sqrtf(__fadd_rn(__fmul_rn(gx[q], gx[q]), __fmul_rn(gy[q], gy[q])));
+        const float st = __fsub_rn(value_of(kmax[q]), value_of(kmin[q]));
+        const int cnt = support[q] - 1;
+        const float ro = cnt == 0 ? 0.0f : sqrtf(acc[q] / (float)cnt);
+        const bool lethal = !(sl < t.slope_crit && st < t.step_crit && ro < t.rough_crit);
+        const float cost = fminf(__fadd_rn(__fadd_rn(__fmul_rn(t.w_slope, sl / t.slope_crit), __fmul_rn(t.w_step, st / t.step_crit)),
+                                           __fmul_rn(t.w_rough, ro / t.rough_crit)), 1.0f);
+        const uint32_t keep = none ? 0u : 0xFFFFFFFFu;              // each element assigned once: the arrays stay in registers
+        slope[q] = __uint_as_float((__float_as_uint(sl) & keep) | (QNAN & ~keep));
+        step[q] = __uint_as_float((__float_as_uint(st) & keep) | (QNAN & ~keep));
+        rough[q] = __uint_as_float((__float_as_uint(ro) & keep) | (QNAN & ~keep));
+        verdict[q] = __uint_as_float((__float_as_uint(lethal ? LETHAL : cost) & keep) | (QNAN & ~keep));
+    }
+}
+
+template <int G, int CH>
+__device__ __forceinline__ void traverse_chunk(const float *hgt, const rover_elevation_cfg &c, const rover_elevation_traverse_cfg &t,
+                                               int i, int j0, float (&slope)[CH], float (&step)[CH], float (&rough)[CH],
+                                               float (&verdict)[CH])
+{
+    switch (t.radius) {                                              // a kernel argument: uniform
+    case 1:  traverse_cells<G, CH, 1>(hgt, c, t, i, j0, slope, step, rough, verdict); break;
+    case 2:  traverse_cells<G, CH, 2>(hgt, c, t, i, j0, slope, step, rough, verdict); break;
+    case 3:  traverse_cells<G, CH, 3>(hgt, c, t, i, j0, slope, step, rough, verdict); break;
+    default: traverse_cells<G, CH, 4>(hgt, c, t, i, j0, slope, step, rough, verdict); break;
+    }
+}
+
+// ---- the two traverse kernels, one workgroup per env; both load the window as the fill does
+template <int G>
+__device__ __forceinline__ void load_window(const ElevArgs &A, int e, int lo_x, int lo_y, float *hgt)
+{
+    constexpr int LOG_G = G == 8 ? 3 : G == 16 ? 4 : G == 32 ? 5 : G == 64 ? 6 : 7;
+    const float *map = A.map + (size_t)e * (G * G);
+    for (int s = threadIdx.x; s < G * G; s += TT) {                  // slot order in global memory, window order in LDS
+        const int j = ((s & (G - 1)) - lo_x) & (G - 1), i = ((s >> LOG_G) - lo_y) & (G - 1);
+        hgt[(i << LOG_G) | j] = map[s];
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ uint8_t class_of(int, float v) { return (uint8_t)(v > 1.0f ? 2 : 1); }      // of a verdict that is no NaN
+
+// The dense form, launched when a window output is asked for.  LDS: the window's heights and the cost image (see LETHAL), G x G
+// floats each, both in WINDOW order.  A thread owns a run of RUN consecutive cells of one row, as in the fill, and takes them CH
+// at a time through traverse_cells: 8 at G = 64, where the strip slides along the whole run, and at G = 128, where it slides
+// along each quarter of it (the per-cell accumulators of 32 cells would not fit the registers); 1 below (at G = 32 a run is two
+// cells; hipcc 7.2's instruction selection crashes on chunks of two and of four cells).  The thread writes its cells' layers to
+// global memory itself, in slot order (a run is contiguous there but for the seam), and the verdicts into the cost image, which
+// the scan reads behind one barrier.
+template <int G>
+__global__ __launch_bounds__(TT) void elevation_traverse_kernel(TraverseArgs F)
+{
+    constexpr int LOG_G = G == 8 ? 3 : G == 16 ? 4 : G == 32 ? 5 : G == 64 ? 6 : 7;
+    constexpr int CELLS = G * G, RUN = CELLS >= TT ? CELLS / TT : 1, CH = RUN < 8 ? 1 : 8;
+    static_assert(RUN <= G && RUN % CH == 0, "a run lies within one row and is whole chunks");
+    __shared__ __attribute__((aligned(16))) float hgt[CELLS];
+    __shared__ __attribute__((aligned(16))) float cst[CELLS];
+    __shared__ int wave_known[WAVES];
+    const ElevArgs &A = F.A;
+    const int tid = threadIdx.x, e = blockIdx.x;
+    const int cx = A.origin[2 * e], cy = A.origin[2 * e + 1];
+    const int lo_x = cx - G / 2, lo_y = cy - G / 2;
+    load_window<G>(A, e, lo_x, lo_y, hgt);
+
+    if (tid * RUN < CELLS) {                                         // G = 8, 16: fewer cells than threads
+        const size_t base = (size_t)e * CELLS;
+        const int first = tid * RUN, i = first >> LOG_G, slot_row = ((lo_y + i) & (G - 1)) << LOG_G;
+        for (int j0 = first & (G - 1), end = j0 + RUN; j0 < end; j0 += CH) {
+            float slope[CH], step[CH], rough[CH], verdict[CH];
+            traverse_chunk<G, CH>(hgt, A.cfg, F.t, i, j0, slope, step, rough, verdict);
+#pragma unroll
+            for (int q = 0; q < CH; ++q) {
+                const size_t s = base + (size_t)(slot_row | ((lo_x + j0 + q) & (G - 1)));
+                const float v = verdict[q];
+                cst[(i << LOG_G) | (j0 + q)] = v;
+                if (F.slope_out) F.slope_out[s] = slope[q];
+                if (F.step_out) F.step_out[s] = step[q];
+                if (F.rough_out) F.rough_out[s] = rough[q];
+                if (F.cost_out) F.cost_out[s] = v != v ? v : fminf(v, 1.0f);
+            }
+        }
+    }
+    if (!A.scan_out) return;                                         // kernel argument: uniform
+    __syncthreads();
+    const Pose Q = load_pose(A, e);
+    auto at = [=](int s) { return ((((s >> LOG_G) - lo_y) & (G - 1)) << LOG_G) | (((s & (G - 1)) - lo_x) & (G - 1)); };
+    scan_rows(A, Q, e, G, LOG_G, cx, cy, Q.ok, wave_known, [&](int s) { return cst[at(s)]; },
+              F.class_out ? F.class_out + (size_t)e * (size_t)(A.nx * A.ny) : nullptr, class_of, CostRead());
+}
+
+// The sparse form, launched when no window output is asked for: only the cells under the scan's columns need a verdict, at most
+// nx * ny of the G x G.  Each column computes its cell's with CH = 1 through the same device function, so the bits are the dense
+// form's; there is no cost image, and the few registers of the one-cell form leave room for several workgroups per CU.
+template <int G>
+__global__ __launch_bounds__(TT) void elevation_traverse_sparse_kernel(TraverseArgs F)
+{
+    constexpr int LOG_G = G == 8 ? 3 : G == 16 ? 4 : G == 32 ? 5 : G == 64 ? 6 : 7;
+    __shared__ __attribute__((aligned(16))) float hgt[G * G];
+    __shared__ int wave_known[WAVES];
+    const ElevArgs &A = F.A;
+    const int e = blockIdx.x;
+    const int cx = A.origin[2 * e], cy = A.origin[2 * e + 1];
+    const int lo_x = cx - G / 2, lo_y = cy - G / 2;
+    load_window<G>(A, e, lo_x, lo_y, hgt);
+    const Pose Q = load_pose(A, e);
+    scan_rows(A, Q, e, G, LOG_G, cx, cy, Q.ok, wave_known,
+              [&](int s) {
+                  const int i = ((s >> LOG_G) - lo_y) & (G - 1), j = ((s & (G - 1)) - lo_x) & (G - 1);
+                  float slope[1], step[1], rough[1], verdict[1];
+                  traverse_chunk<G, 1>(hgt, A.cfg, F.t, i, j, slope, step, rough, verdict);
+                  return verdict[0];
+              },
+              F.class_out ? F.class_out + (size_t)e * (size_t)(A.nx * A.ny) : nullptr, class_of, CostRead());
 }
 
 bool pos_ok(float v) { return std::isfinite(v) && v > 0.0f; }
@@ -578,6 +798,89 @@ int rover_elevation_fill(const rover_elevation_cfg *cfg, const rover_elevation_f
     default:  hipLaunchKernelGGL(elevation_fill_kernel<128>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
     }
     return launched("elevation_fill_kernel launch: %s");
+}
+
+size_t rover_elevation_traverse_cfg_bytes(void) { return sizeof(rover_elevation_traverse_cfg); }
+
+int rover_elevation_traverse(const rover_elevation_cfg *cfg, const rover_elevation_traverse_cfg *t, const float *pos,
+                             const float *quat, int64_t comp_stride, int64_t env_stride, const float *heights, const int32_t *origin,
+                             const float *ray_x, int32_t nx, const float *ray_y, int32_t ny, float *cost_scan_out, int64_t scan_pitch,
+                             uint8_t *class_out, int32_t *lethal_count_out, float *slope_out, float *step_out, float *rough_out,
+                             float *cost_out, int32_t n, void *stream)
+{
+    static const char who[] = "rover_elevation_traverse: %s";
+    auto refuse = [](const char *why) { return rover_internal_fail(ROVER_ERR_INVALID, who, why); };
+    float *const layers[4] = {slope_out, step_out, rough_out, cost_out};
+    if (!t) return refuse("NULL argument");
+    if (!cost_scan_out && !slope_out && !step_out && !rough_out && !cost_out)
+        return refuse("NULL argument (cost_scan_out or one of the four window outputs is required)");
+    if (!cost_scan_out && heights) {                                 // no scan: the ray tables are not read and may be NULL
+        ray_x = ray_x ? ray_x : heights;
+        ray_y = ray_y ? ray_y : heights;
+    }
+    if (int rc = check_common(who, cfg, pos, quat, comp_stride, env_stride, heights, origin, ray_x, nx, ray_y, ny, cost_scan_out,
+                              scan_pitch, lethal_count_out, n))
+        return rc;
+    if (t->radius < 1 || t->radius > ROVER_ELEVATION_TRAVERSE_MAX_RADIUS) return refuse("radius must be in [1, 4]");
+    const int side = 2 * t->radius + 1;
+    if (t->min_support < 1 || t->min_support > side * side) return refuse("min_support must be in [1, (2 radius + 1)^2]");
+    if (!pos_ok(t->slope_crit) || !pos_ok(t->step_crit) || !pos_ok(t->rough_crit))
+        return refuse("slope_crit, step_crit and rough_crit must be finite and > 0");
+    for (float w : {t->w_slope, t->w_step, t->w_rough})
+        if (!(std::isfinite(w) && w >= 0.0f)) return refuse("w_slope, w_step and w_rough must be finite and >= 0");
+    {
+        volatile float two = t->w_slope + t->w_step;                 // each sum rounded to fp32, in this order
+        volatile float sum = two + t->w_rough;
+        if (!(sum <= 1.0f)) return refuse("the weights' sum (w_slope + w_step) + w_rough must be <= 1");
+    }
+    if (t->unknown_cost != t->unknown_cost) return refuse("unknown_cost must not be a NaN");
+    const uint64_t cells_bytes = (uint64_t)n * (uint64_t)cfg->grid * (uint64_t)cfg->grid * 4u;
+    for (float *p : layers) {
+        if (reinterpret_cast<uintptr_t>(p) & 3) return refuse("float and int32 pointers must be 4-byte aligned");
+        if (p && overlap(heights, cells_bytes, p, cells_bytes)) return refuse("heights and a window output overlap");
+    }
+    if (cost_scan_out) {                                             // heights and cost_scan_out: check_common
+        const uint64_t cols = (uint64_t)nx * (uint64_t)ny;
+        if (class_out && overlap(heights, cells_bytes, class_out, (uint64_t)n * cols)) return refuse("heights and class_out overlap");
+        if (lethal_count_out && overlap(heights, cells_bytes, lethal_count_out, (uint64_t)n * 4u))
+            return refuse("heights and lethal_count_out overlap");
+    }
+    int dev;
+    if (int rc = device_of(heights, &dev, true)) return rc;
+    DeviceGuard guard(dev);
+    TraverseArgs F;
+    ElevArgs &A = F.A;
+    A.cfg = *cfg;
+    A.cfg.unknown_value = t->unknown_cost;                           // what scan_rows gives a column without a cost
+    A.depth = nullptr; A.ray_b = nullptr; A.pos = pos; A.quat = quat; A.ray_x = ray_x; A.ray_y = ray_y;
+    A.reset_a = nullptr; A.reset_b = nullptr;
+    A.map = const_cast<float *>(heights); A.origin = const_cast<int32_t *>(origin);
+    A.scan_out = cost_scan_out; A.known_out = nullptr; A.count_out = cost_scan_out ? lethal_count_out : nullptr;
+    A.pitch = 0; A.comp_stride = (long long)comp_stride; A.env_stride = (long long)env_stride;
+    A.scan_pitch = (long long)scan_pitch;
+    A.hw = 0; A.nx = nx; A.ny = ny; A.log_g = log2_of(cfg->grid);
+    F.t = *t;
+    F.class_out = cost_scan_out ? class_out : nullptr;
+    F.slope_out = slope_out; F.step_out = step_out; F.rough_out = rough_out; F.cost_out = cost_out;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!slope_out && !step_out && !rough_out && !cost_out) {        // the scan alone: verdicts only under its columns
+        switch (cfg->grid) {
+        case 8:   hipLaunchKernelGGL(elevation_traverse_sparse_kernel<8>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+        case 16:  hipLaunchKernelGGL(elevation_traverse_sparse_kernel<16>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+        case 32:  hipLaunchKernelGGL(elevation_traverse_sparse_kernel<32>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+        case 64:  hipLaunchKernelGGL(elevation_traverse_sparse_kernel<64>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+        default:  hipLaunchKernelGGL(elevation_traverse_sparse_kernel<128>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+        }
+        return launched("elevation_traverse_sparse_kernel launch: %s");
+    }
+    switch (cfg->grid) {
+    case 8:   hipLaunchKernelGGL(elevation_traverse_kernel<8>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+    case 16:  hipLaunchKernelGGL(elevation_traverse_kernel<16>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+    case 32:  hipLaunchKernelGGL(elevation_traverse_kernel<32>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+    case 64:  hipLaunchKernelGGL(elevation_traverse_kernel<64>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+    default:  hipLaunchKernelGGL(elevation_traverse_kernel<128>, dim3((unsigned)n), dim3(TT), 0, st, F); break;
+    }
+    return launched("elevation_traverse_kernel launch: %s");
 }
 
 }  // extern "C"

@@ -10,6 +10,8 @@ the map and read the scan out of the result.  ``RoverEnv`` runs it behind the ca
 ``policy_rows`` puts such a scan into observation rows, so a trained actor can be evaluated on what the camera can see.
 ``ElevationMap.fill`` is the inpainting pass behind it (``include/rover_elevation_fill.h``): one more launch that fills the unknown
 cells of the window with the minimum of their known neighbours, ring by ring, and reports how far each value was carried.
+``ElevationMap.traverse`` (``include/rover_elevation_traverse.h``) derives from the map, or from the fill's window, where the rover
+may drive: slope, step height, roughness and a cost per cell, and the scan of the cost, again as one launch.
 
 ``TorchElevationMap`` is the same interface in plain numpy on float32, every operation in the header's order: the specification
 of the kernel, compared bit for bit, and it runs on the CPU.
@@ -167,9 +169,8 @@ class TorchElevationMap(_ElevationBase):
             valid &= np.isfinite(wx) & np.isfinite(wy) & np.isfinite(wz)
         return valid, wx, wy, wz
 
-    def _read(self, mp, origin, pos, quat, ok, dist=None):
-        """Step 8 on ``mp`` / ``origin``: (scan (n, ny * nx), known uint8, count int32).  With ``dist`` (the fill's bytes per slot) a
-        cell is known where its dist is below 255, and the middle result is the columns' dist, 255 where unknown."""
+    def _columns(self, origin, pos, quat, ok):
+        """Step 8's look-up: (inside (n, ny, nx) bool, the index triple of each column's slot)."""
         ft, n, G = self.ft, self.num_envs, self.grid
         with np.errstate(all="ignore"):
             w, x, y, z = (quat[:, i] for i in range(4))
@@ -186,7 +187,13 @@ class TorchElevationMap(_ElevationBase):
         lo = origin.astype(np.int64) - G // 2
         dx, dy = gx - lo[:, 0, None, None], gy - lo[:, 1, None, None]
         inside = fin & (dx >= 0) & (dx < G) & (dy >= 0) & (dy < G)
-        at = (np.arange(n)[:, None, None], gy & (G - 1), gx & (G - 1))
+        return inside, (np.arange(n)[:, None, None], gy & (G - 1), gx & (G - 1))
+
+    def _read(self, mp, origin, pos, quat, ok, dist=None):
+        """Step 8 on ``mp`` / ``origin``: (scan (n, ny * nx), known uint8, count int32).  With ``dist`` (the fill's bytes per slot) a
+        cell is known where its dist is below 255, and the middle result is the columns' dist, 255 where unknown."""
+        ft, n = self.ft, self.num_envs
+        inside, at = self._columns(origin, pos, quat, ok)
         h = mp[at]
         known = inside & (~np.isnan(h) if dist is None else dist[at] < 255)
         with np.errstate(all="ignore"):
@@ -278,6 +285,88 @@ class TorchElevationMap(_ElevationBase):
         pos, quat, ok = self._pose(pos, quat)
         res = (*self._read(filled, self.origin, pos, quat, ok, dist=cell_dist), filled, cell_dist)
         return self._emit(res, scan_out, dist_out, count_out, filled_out, cell_dist_out)
+
+    def _traverse_cfg(self, cfg):
+        cfg = self.map_cfg.traverse if cfg is None else cfg
+        if cfg is None:
+            raise ValueError("traverse needs a TraverseCfg (ElevationMapCfg.traverse or cfg=)")
+        return cfg.to_native()
+
+    def _heights(self, heights):
+        if heights is None:
+            return self.map
+        h = heights.numpy() if isinstance(heights, torch.Tensor) else np.asarray(heights)
+        if h.dtype != np.float32 or h.size != self.map.size:
+            raise ValueError(f"heights must be float32 of {self.map.size} values")
+        return h.reshape(self.map.shape)
+
+    def traverse_window(self, heights=None, cfg=None):
+        """Steps 1 - 4 of include/rover_elevation_traverse.h on ``heights`` ((n, G, G) float32 in slot order; ``None``: the map) and
+        ``origin``: (slope, step, rough, cost (n, G, G) float32, class (n, G, G) uint8), all in slot order."""
+        if self.float64:
+            raise ValueError("the traverse layers are specified on float32")
+        t, ft, n, G = self._traverse_cfg(cfg), np.float32, self.num_envs, self.grid
+        r, cell, inv_cell = int(t.radius), ft(self.cfg.cell), ft(self.cfg.inv_cell)
+        lo = self.origin.astype(np.int64) - G // 2
+        w = np.arange(G, dtype=np.int64)
+        at = (np.arange(n)[:, None, None], ((lo[:, 1, None] + w) & (G - 1))[:, :, None], ((lo[:, 0, None] + w) & (G - 1))[:, None, :])
+        h = self._heights(heights)[at]                                       # window order: [e, i over y, j over x]
+        nan = _QNAN.view(np.float32)
+        framed = np.full((n, G + 2 * r, G + 2 * r), nan, dtype=ft)           # the frame: outside the window nothing is usable
+        framed[:, r:r + G, r:r + G] = h
+        shifted = lambda di, dj: framed[:, r + di:r + di + G, r + dj:r + dj + G]      # noqa: E731
+        with np.errstate(all="ignore"):
+            def one_sided(lower, upper):
+                l, u = np.isfinite(lower), np.isfinite(upper)
+                both, up, down = (upper - lower) * (ft(0.5) * inv_cell), (upper - h) * inv_cell, (h - lower) * inv_cell
+                return np.where(l & u, both, np.where(u, up, np.where(l, down, ft(0.0)))).astype(ft)
+
+            gx, gy = one_sided(shifted(0, -1), shifted(0, 1)), one_sided(shifted(-1, 0), shifted(1, 0))
+            slope = np.sqrt((gx * gx) + (gy * gy))
+            kmin, kmax = np.full(h.shape, 0xFFFFFFFF, dtype=np.uint32), np.zeros(h.shape, dtype=np.uint32)
+            support, acc = np.zeros(h.shape, dtype=np.int64), np.zeros(h.shape, dtype=ft)
+            for di in range(-r, r + 1):
+                for dj in range(-r, r + 1):
+                    hd = shifted(di, dj)
+                    ok = np.isfinite(hd)
+                    k = self.keys(hd)
+                    kmin, kmax = np.where(ok, np.minimum(kmin, k), kmin), np.where(ok, np.maximum(kmax, k), kmax)
+                    support += ok
+                    if di or dj:
+                        res = (hd - h) - ((gx * (ft(dj) * cell)) + (gy * (ft(di) * cell)))
+                        acc = np.where(ok, acc + res * res, acc).astype(ft)
+            step = self.values(kmax) - self.values(kmin)
+            cnt = support - 1
+            rough = np.where(cnt == 0, ft(0.0), np.sqrt(acc / cnt.astype(ft))).astype(ft)
+            sc, tc, rc = ft(t.slope_crit), ft(t.step_crit), ft(t.rough_crit)
+            lethal = ~((slope < sc) & (step < tc) & (rough < rc))
+            total = ((ft(t.w_slope) * (slope / sc)) + (ft(t.w_step) * (step / tc))) + (ft(t.w_rough) * (rough / rc))
+            cost = np.where(lethal, ft(1.0), np.fmin(total, ft(1.0))).astype(ft)
+        verdict = np.isfinite(h) & (support >= int(t.min_support))
+        cls = np.where(verdict, np.where(lethal, 2, 1), 0).astype(np.uint8)
+        out = []
+        for layer in (slope, step, rough, cost):
+            slots = np.empty((n, G, G), dtype=ft)
+            slots[at] = np.where(verdict, layer, nan)
+            out.append(slots)
+        cls_slots = np.empty((n, G, G), dtype=np.uint8)
+        cls_slots[at] = cls
+        return (*out, cls_slots)
+
+    def traverse(self, pos, quat, heights=None, scan_out=None, class_out=None, count_out=None, slope_out=None, step_out=None,
+                 rough_out=None, cost_out=None, cfg=None):
+        """The layers of ``heights`` (``None``: the map) and the scan of the cost (include/rover_elevation_traverse.h); ``cfg``
+        defaults to the map cfg's ``traverse``.  Returns (cost scan (n, rays), class (n, rays) uint8, lethal count (n,) int32, slope,
+        step, rough, cost (n, G, G))."""
+        t = self._traverse_cfg(cfg)
+        slope, step, rough, cost, cls = self.traverse_window(heights, cfg)
+        pos, quat, ok = self._pose(pos, quat)
+        inside, at = self._columns(self.origin, pos, quat, ok)
+        col_cls = np.where(inside, cls[at], 0).astype(np.uint8)
+        scan = np.where(col_cls > 0, cost[at], np.float32(t.unknown_cost)).astype(np.float32)
+        n = self.num_envs
+        res = (scan.reshape(n, -1), col_cls.reshape(n, -1), (col_cls == 2).reshape(n, -1).sum(1).astype(np.int32), slope, step, rough, cost)
+        return self._emit(res, scan_out, class_out, count_out, slope_out, step_out, rough_out, cost_out)
 
     @staticmethod
     def _emit(res, *outs):
@@ -410,6 +499,49 @@ class ElevationMap(_ElevationBase):
                       self.ray_x.data_ptr(), self.nx, self.ray_y.data_ptr(), self.ny, s_ptr, int(s_pitch), _fused.ptr(outs[1]),
                       _fused.ptr(outs[2]), _fused.ptr(filled_out), _fused.ptr(cell_dist_out), n)
         return (*outs, filled_out, cell_dist_out)
+
+    def traverse(self, pos, quat, heights=None, scan_out=None, class_out=None, count_out=None, slope_out=None, step_out=None,
+                 rough_out=None, cost_out=None, cfg=None):
+        """One asynchronous ``rover_elevation_traverse`` launch: slope, step height, roughness and cost of ``heights`` (a contiguous
+        float32 (n, G, G) cuda tensor in the map's slot order, such as ``fill``'s ``filled_out``; ``None``: the map) under ``cfg``
+        (default: the map cfg's ``traverse``), and the scan of the cost.  ``heights``, ``map`` and ``origin`` are only read.
+        ``scan_out`` (the cost under each scan column, ``unknown_cost`` where there is none) / ``class_out`` (uint8: 0 no verdict,
+        1 free, 2 lethal) / ``count_out`` (the lethal columns) as ``update``'s three, allocated where the caller gives none;
+        ``scan_out=False``: no scan, the three are ``None``.  The four window outputs, contiguous (n, G, G) float32 in slot order,
+        NaN where a cell has no verdict, are written only where given (``True``: allocated here).  Returns (scan, class, count,
+        slope, step, rough, cost)."""
+        n, G, dev = self.num_envs, self.grid, self.map.device
+        if cfg is None:
+            cfg = self.map_cfg.traverse
+        if cfg is None:
+            raise ValueError("traverse needs a TraverseCfg (ElevationMapCfg.traverse or cfg=)")
+        tc = cfg.to_native()
+        if heights is None:
+            heights = self.map
+        elif not isinstance(heights, torch.Tensor) or not heights.is_cuda or heights.device != dev or heights.dtype != torch.float32 or \
+                not heights.is_contiguous() or heights.numel() != n * G * G:
+            raise ValueError(f"heights must be a contiguous float32 cuda tensor of {n * G * G} values on the map's device")
+        p_ptr, q_ptr, cs, es = self._pose(pos, quat)
+        if scan_out is False:
+            if class_out is not None or count_out is not None:
+                raise ValueError("class_out and count_out are written only with a scan")
+            outs, s_ptr, s_pitch = (None, None, None), None, self.columns
+        else:
+            outs, s_ptr, s_pitch = self._outs(scan_out, class_out, count_out)
+        layers = []
+        for t, nm in ((slope_out, "slope_out"), (step_out, "step_out"), (rough_out, "rough_out"), (cost_out, "cost_out")):
+            if t is True:
+                t = torch.empty((n, G, G), dtype=torch.float32, device=dev)
+            if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev or t.dtype != torch.float32 or
+                                  not t.is_contiguous() or t.numel() != n * G * G):
+                raise ValueError(f"{nm} must be a contiguous float32 cuda tensor of {n * G * G} values on the map's device")
+            layers.append(t)
+        if s_ptr is None and all(t is None for t in layers):
+            raise ValueError("traverse needs the scan or one of the four window outputs")
+        _fused.launch("rover_elevation_traverse", dev, self.cfg, tc, p_ptr, q_ptr, cs, es, heights.data_ptr(), self.origin.data_ptr(),
+                      self.ray_x.data_ptr(), self.nx, self.ray_y.data_ptr(), self.ny, s_ptr, int(s_pitch), _fused.ptr(outs[1]),
+                      _fused.ptr(outs[2]), *(_fused.ptr(t) for t in layers), n)
+        return (*outs, *layers)
 
     def clear(self, mask=None):
         """All maps (or those of ``mask``) back to unknown."""

@@ -16,6 +16,7 @@ from ..obs_post import DEPTH_TAG, LIDAR_TAG, ObsPost, image_segments, lidar_segm
 
 KEYS = ("depth", "depth_valid", "rgb", "lidar_range", "lidar_hits_w", "elevation_scan", "elevation_known", "elevation_count")
 FILL_KEYS = ("elevation_scan_filled", "elevation_fill_dist", "elevation_filled_count")      # only under ElevationMapCfg.fill
+TRAVERSE_KEYS = ("elevation_cost", "elevation_cost_class", "elevation_lethal_count")        # only under ElevationMapCfg.traverse
 
 
 class Rotating:
@@ -36,19 +37,23 @@ class SensorRig:
     """``host`` (the env) has ``extras``, ``common_step_counter`` and ``call_counter``; ``for_env`` builds the device parts, which
     are plain attributes: a bench switches a stage off by setting it to ``None``.  ``render(camera_cfg, workspace, buf)`` fills the
     (N, H, W) ``buf``; ``image``: (H, W); ``pose``: the (pos, quat) views the map reads; ``map_source``: "camera" or "lidar"; ``fill_iterations``: 0, or the sweeps
-    of the min-fill launch that follows every map launch (``elevation.fill``) into buffers of its own."""
+    of the min-fill launch that follows every map launch (``elevation.fill``) into buffers of its own; ``traverse``: ``None``, or the
+    ``TraverseCfg`` of the launch behind the two (``elevation.traverse``), which reads the fill's window where there is a fill and
+    the map where there is none, and writes into buffers of its own."""
 
     def __init__(self, host, device="cpu", num_envs: int = 0, nbuf: int = 2, render=None, camera_cfg=None, workspace=None, image=None,
                  depth_sensor=None, depth_post=None, camera_every: int = 1, lidar=None, lidar_post=None, lidar_hits: bool = False,
-                 lidar_every: int = 1, elevation=None, map_source: str = "camera", unknown_value: float = 0.0, pose=None, fill_iterations: int = 0):
+                 lidar_every: int = 1, elevation=None, map_source: str = "camera", unknown_value: float = 0.0, pose=None, fill_iterations: int = 0,
+                 traverse=None):
         self.host, self._render, self.camera_cfg, self.workspace = host, render, camera_cfg, workspace
         self.depth_sensor, self.depth_post, self.camera_every = depth_sensor, depth_post, int(camera_every)
         self.lidar, self.lidar_post, self.lidar_every = lidar, lidar_post, int(lidar_every)
         self.elevation, self.map_source, self._pose = elevation, map_source, pose
         self.fill_iterations = int(fill_iterations) if elevation is not None else 0
+        self.traverse = traverse if elevation is not None else None
         self.active = camera_cfg is not None or lidar is not None
         ex, n, inf = host.extras, int(num_envs), float("inf")
-        for key in KEYS + FILL_KEYS:                                       # what the rig before this one published
+        for key in KEYS + FILL_KEYS + TRAVERSE_KEYS:                       # what the rig before this one published
             ex.pop(key, None)
         full = lambda shape, value, dtype=torch.float32: torch.full(shape, value, dtype=dtype, device=device)      # noqa: E731
         if camera_cfg is not None:       # extras["depth"]: the (N, W, H) view of the row-major (N, H, W) image the kernels write
@@ -65,6 +70,11 @@ class SensorRig:
         if self.fill_iterations:
             self._fills = Rotating(ex, FILL_KEYS, lambda: (full((n, elevation.columns), float(unknown_value)),
                                                            full((n, elevation.columns), 255, torch.uint8), full((n,), 0, torch.int32)), nbuf)
+        if self.traverse is not None:
+            self._costs = Rotating(ex, TRAVERSE_KEYS, lambda: (full((n, elevation.columns), float(self.traverse.unknown_cost)),
+                                                               full((n, elevation.columns), 0, torch.uint8), full((n,), 0, torch.int32)), nbuf)
+            # the fill's window, handed on to the traverse launch on the same stream: one buffer is enough
+            self._filled = full((n, elevation.grid, elevation.grid), float("nan")) if self.fill_iterations else None
 
     @classmethod
     def for_env(cls, env) -> "SensorRig":
@@ -76,7 +86,8 @@ class SensorRig:
         kw = {"pose": (env.state[_lib.POS:_lib.POS + 3].t(), env.state[_lib.QUAT:_lib.QUAT + 4].t())}
         if emc is not None:
             kw.update(map_source=getattr(emc, "source", "camera"), unknown_value=emc.unknown_value,
-                      fill_iterations=emc.fill_iterations if getattr(emc, "fill", "none") != "none" else 0)
+                      fill_iterations=emc.fill_iterations if getattr(emc, "fill", "none") != "none" else 0,
+                      traverse=getattr(emc, "traverse", None))
         if cam is not None:
             native, noisy = cam.to_native(), cam.noise is not None or cam.clip is not None
             kw.update(camera_cfg=native, image=(int(cam.height), int(cam.width)), camera_every=cam.every_n_steps,
@@ -141,7 +152,11 @@ class SensorRig:
         self.elevation.update(frame, *self._pose, reset=reset, scan_out=scan, known_out=known, count_out=count)
         if self.fill_iterations:                                           # the same pose, the map the launch above left
             scan, dist, count = self._fills.next()
-            self.elevation.fill(*self._pose, scan_out=scan, dist_out=dist, count_out=count, iterations=self.fill_iterations)
+            window = {} if self.traverse is None else {"filled_out": self._filled}
+            self.elevation.fill(*self._pose, scan_out=scan, dist_out=dist, count_out=count, iterations=self.fill_iterations, **window)
+        if self.traverse is not None:                                      # the fill's window, or the map itself
+            scan, cls, count = self._costs.next()
+            self.elevation.traverse(*self._pose, heights=self._filled, scan_out=scan, class_out=cls, count_out=count, cfg=self.traverse)
 
     def _lidar_update(self, force: bool, reset):
         buf = None
