@@ -33,9 +33,16 @@ enum {
     LIFT_ACTION = 40,      /* 8  action_manager.action                                                */
     LIFT_PREV_ACTION = 48, /* 8  action_manager.prev_action                                           */
     LIFT_EP_SUM = 56,      /* 6  per-term episodic reward sums                                        */
-    LIFT_RESET_COUNT = 62, /* 1  uint32                                                               */
+    LIFT_RESET_COUNT = 62, /* 1  uint32: resets of this env so far                                    */
+    LIFT_CMD_COUNT = 63,   /* 1  uint32: timer resamples of the command since the env's last reset    */
     LIFT_STATE_WORDS = 64
 };
+/* Draws: Philox4x32-10 under the key (seed_lo, seed_hi), counter (global env id, LIFT_RESET_COUNT, stream, index).  A reset draws
+ * the cube's offset at (id, count, 0, 0) and its command at (id, count, 1, 0), then adds 1 to the count and zeroes
+ * LIFT_CMD_COUNT.  The k-th timer resample of the episode that follows (k = LIFT_CMD_COUNT = 0, 1, ...) draws the command at
+ * (id, count, 1, 1 + k), with the count as that reset left it, and stores k + 1: every resample of an episode is a fresh
+ * draw, as ORBIT's UniformPoseCommand makes it.  The state words and the key are therefore the whole environment; a state
+ * saved before word 63 had a meaning holds 0 there, which is the right value for an episode without a timer resample yet. */
 enum { LIFT_NUM_REW = 6, LIFT_NUM_TERM = 2, LIFT_OBS = 36, LIFT_ACT = 8, LIFT_LOG_WORDS = 16 };
 
 /* FrankaCubeLiftEnvCfg in the shape the kernels consume */

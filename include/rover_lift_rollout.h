@@ -29,9 +29,9 @@
  *     rho = sqrt(-2 ln u1),  eps[2p] = rho cos(2 pi u2),  eps[2p + 1] = rho sin(2 pi u2)
  * (w2, w3 unused; an odd action width uses the cosine of its last pair).  The values depend on (seed, g, counter, c) only: not on
  * how the envs are split over calls or ranks, and a checkpoint is the counter.  Word 3 of the lift env's own draws is 0 (the
- * reset draw, and the command draw of a reset) or 1 (the command resample of a step) -- lift_kernels.hip passes `stream` in
- * {0, 1} or a literal 0 there -- and word 3 of the rover collector's draws is 0x524F4C00 | p, so the three streams never meet,
- * even under the same seed.
+ * reset draw, and the command draw of a reset) or 1 + k (the k-th timer resample of the command since the env's last reset,
+ * rover_lift.h: k stays far below this tag, which it would take 1.28e9 resamples within one episode to reach) and word 3 of the
+ * rover collector's draws is 0x524F4C00 | p, so the three streams never meet, even under the same seed.
  *
  * Conventions as in rover_rollout.h: plain C, caller-owned device buffers, int return codes, rover_last_error(), asynchronous on
  * `stream`, no allocation, no host synchronisation, no atomics.

@@ -331,7 +331,7 @@ class RoverHipError(RuntimeError):
 LIFT_NUM_REW, LIFT_OBS, LIFT_ACT, LIFT_STATE_WORDS, LIFT_LOG_WORDS = 6, 36, 8, 64, 16
 # lift state word offsets (include/rover_lift.h)
 LIFT_Q, LIFT_QD, LIFT_OBJ_POS, LIFT_OBJ_QUAT, LIFT_OBJ_LIN, LIFT_OBJ_ANG, LIFT_CMD = 0, 9, 18, 21, 25, 28, 31
-LIFT_TIME_LEFT, LIFT_EP_LEN, LIFT_ACTION, LIFT_PREV_ACTION, LIFT_EP_SUM, LIFT_RESET_COUNT = 38, 39, 40, 48, 56, 62
+LIFT_TIME_LEFT, LIFT_EP_LEN, LIFT_ACTION, LIFT_PREV_ACTION, LIFT_EP_SUM, LIFT_RESET_COUNT, LIFT_CMD_COUNT = 38, 39, 40, 48, 56, 62, 63
 
 
 class LiftConfig(C.Structure):

@@ -690,7 +690,8 @@ LF_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, ui
 }
 LF_DEV float uniform01(uint32_t u) { return (float)(u >> 8) * (1.0f / 16777216.0f); }
 
-// UniformPoseCommand._resample_command (manipulation_env_cfg.py:163-172)
+// UniformPoseCommand._resample_command (manipulation_env_cfg.py:163-172).  Word 3 of the counter: 0 for the draw of a reset,
+// 1 + k for the k-th timer resample since it (LIFT_CMD_COUNT), so every resample of an episode draws afresh.
 LF_DEV void resample_command(const lift_config &c, float *S, uint32_t gid, uint32_t count, uint32_t stream)
 {
     uint32_t r[4];
@@ -722,6 +723,7 @@ LF_DEV void reset_env(const lift_config &c, float *S, uint32_t gid)
     resample_command(c, S, gid, count, 0u);
     S[LIFT_EP_LEN] = u2f(0u);
     S[LIFT_RESET_COUNT] = u2f(count + 1u);
+    S[LIFT_CMD_COUNT] = u2f(0u);
 }
 // ObservationsCfg.PolicyCfg (manipulation_env_cfg.py:101-116)
 LF_DEV void write_observation(const float *S, float *o)
@@ -1074,9 +1076,11 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
         float R[LIFT_STATE_WORDS];
 #pragma unroll
         for (int i = LIFT_CMD; i <= LIFT_TIME_LEFT; ++i) R[i] = S[i];
-        resample_command(c, R, gid, f2u(S[LIFT_RESET_COUNT]), 1u);
+        const uint32_t k = f2u(S[LIFT_CMD_COUNT]);
+        resample_command(c, R, gid, f2u(S[LIFT_RESET_COUNT]), 1u + k);
 #pragma unroll
         for (int i = LIFT_CMD; i <= LIFT_TIME_LEFT; ++i) S[i] = resample ? R[i] : S[i];
+        S[LIFT_CMD_COUNT] = resample ? u2f(k + 1u) : S[LIFT_CMD_COUNT];
     }
     LIFT_STAMP(16);
     // ---- stores.  State: lane 0 lays the 64 words out transposed in the LDS slot ([word % 8][word / 8]), every lane picks

@@ -26,7 +26,7 @@ from ._fused import f32_cuda, holds, launch, ptr
 from .lift_ppo import OBS_DIM
 from .rollout import _FLAG, _transition, standard_normals
 
-LIFT_ROLLOUT_TAG = 0x4C524F00     # "LRO\0": word 3 of the Philox counter, | action pair (the lift env's draws have word 3 in {0, 1})
+LIFT_ROLLOUT_TAG = 0x4C524F00     # "LRO\0": word 3 of the Philox counter, | action pair (the lift env's draws have word 3 = 0 or 1 + resample index)
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
 LOG_WORDS = 9                     # log[0:8]: means / counts of the envs reset in a step, log[8]: their number
 

@@ -36,7 +36,7 @@
 /* ------------------------------------------------------------------------------------------------ layout, config */
 enum {
     W_Q = 0, W_QD = 9, W_OBJ_POS = 18, W_OBJ_QUAT = 21, W_OBJ_LIN = 25, W_OBJ_ANG = 28, W_CMD = 31, W_TIME_LEFT = 38,
-    W_EP_LEN = 39, W_ACTION = 40, W_PREV_ACTION = 48, W_EP_SUM = 56, W_RESET_COUNT = 62, N_WORDS = 64
+    W_EP_LEN = 39, W_ACTION = 40, W_PREV_ACTION = 48, W_EP_SUM = 56, W_RESET_COUNT = 62, W_CMD_COUNT = 63, N_WORDS = 64
 };
 enum { N_REW = 6, N_TERM = 2, N_OBS = 36, N_ACT = 8, N_LOG = 16 };
 
@@ -649,7 +649,8 @@ static uint32_t word_u32(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 static float u32_word(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 
 /* UniformPoseCommand._resample_command (manipulation_env_cfg.py:163-172): position uniform in the ranges, roll = pitch =
- * yaw = 0 -> identity quaternion; timer = resampling time */
+ * yaw = 0 -> identity quaternion; timer = resampling time.  Counter (gid, resets so far, 1, stream): stream 0 is the draw of a
+ * reset, 1 + k the k-th timer resample since that reset (W_CMD_COUNT), so every resample of an episode is a fresh draw. */
 static void resample_command(const lfo_config *c, float *S, uint32_t gid, uint32_t count, uint32_t stream)
 {
     uint32_t r[4];
@@ -674,6 +675,7 @@ static void reset_env(const lfo_config *c, float *S, uint32_t gid)
     resample_command(c, S, gid, count, 0u);
     S[W_EP_LEN] = u32_word(0u);
     S[W_RESET_COUNT] = u32_word(count + 1u);
+    S[W_CMD_COUNT] = u32_word(0u);
 }
 /* ObservationsCfg.PolicyCfg (manipulation_env_cfg.py:101-116): joint_pos_rel 9, joint_vel_rel 9, object position in the
  * robot root frame 3 (root at the origin, identity), generated_commands 7, last_action 8 */
@@ -741,7 +743,11 @@ static void step_env(const lfo_config *c, float *S, const float *action, uint32_
         reset_env(c, S, gid);
     }
     S[W_TIME_LEFT] -= step_dt;                        /* CommandTerm.compute: timer, resample, (no body-frame update needed) */
-    if (S[W_TIME_LEFT] <= 0.0f) resample_command(c, S, gid, word_u32(S[W_RESET_COUNT]), 1u);
+    if (S[W_TIME_LEFT] <= 0.0f) {
+        const uint32_t k = word_u32(S[W_CMD_COUNT]);
+        resample_command(c, S, gid, word_u32(S[W_RESET_COUNT]), 1u + k);
+        S[W_CMD_COUNT] = u32_word(k + 1u);
+    }
     write_observation(S, obs);
 }
 

@@ -11,8 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # ROVER_ORACLE_DIR: load the library from another directory (the sanitizer builds of `make -C oracle sanitized`)
 _LIB_PATH = os.path.join(os.environ.get("ROVER_ORACLE_DIR") or _HERE, "liblift_oracle.so")
 NUM_REW, NUM_TERM, OBS, ACT, LOG_WORDS, STATE_WORDS = 6, 2, 36, 8, 16, 64
-Q, QD, OBJ_POS, OBJ_QUAT, OBJ_LIN, OBJ_ANG, CMD, TIME_LEFT, EP_LEN, ACTION, PREV_ACTION, EP_SUM, RESET_COUNT = \
-    0, 9, 18, 21, 25, 28, 31, 38, 39, 40, 48, 56, 62
+Q, QD, OBJ_POS, OBJ_QUAT, OBJ_LIN, OBJ_ANG, CMD, TIME_LEFT, EP_LEN, ACTION, PREV_ACTION, EP_SUM, RESET_COUNT, CMD_COUNT = \
+    0, 9, 18, 21, 25, 28, 31, 38, 39, 40, 48, 56, 62, 63
 Q_DEFAULT = np.array([0.0, -0.569, 0.0, -2.810, 0.0, 3.037, 0.741, 0.04, 0.04], np.float32)
 
 

@@ -202,3 +202,114 @@ def test_arm_dynamics_match_an_independent_lagrangian_restatement(lo):
         qdd = rng.uniform(-2, 2, 7)
         tau = lo.inverse_dynamics(q, qd, qdd) - lo.inverse_dynamics(q, qd, np.zeros(7))
         assert np.abs(tau - M @ qdd).max() < 2e-4
+
+
+# ---------------------------------------------------------------------------------------------- off the defaults (tests/lift_cases.py)
+def test_timer_resamples_of_one_episode_draw_afresh(lo):
+    """command_resampling_time = 0.3 s: the timer fires every fifteenth step, about sixteen times per episode.  Each firing draws
+    at Philox counter (global id, resets so far, 1, 1 + k), k = word 63 = the firings since the env's last reset: the commands of
+    one episode are pairwise distinct, lie inside the ranges, differ between envs, and each equals the value worked out by hand
+    from the package's numpy Philox to 1 ulp (lift_cases.by_hand_command); the word returns to 0 at a reset.  The firings are
+    found from the timer word, not from word 63."""
+    import lift_cases as LC
+    n, offset = 61, 5
+    cfg = lo.default_config(cmd_resample_time=0.3, seed_lo=11, seed_hi=3)
+    S = lo.new_state(n)
+    lo.reset(cfg, S, offset)
+    assert (S[:, lo.CMD_COUNT].view(np.uint32) == 0).all()
+    rng = np.random.RandomState(0)
+    gid = offset + np.arange(n)
+    episodes = {}                                      # (env, resets so far) -> commands of the timer firings
+    time_outs = 0
+    for k in range(300):
+        before = S[:, lo.CMD_COUNT].view(np.uint32).copy()
+        _, _, term, trunc, _ = lo.step(cfg, S, LC.actions(rng, k, n), offset)
+        reset = (term | trunc).astype(bool)
+        fired = S[:, lo.TIME_LEFT] == np.float32(0.3)            # a resample leaves the full time; a reset's is one step short
+        assert not (fired & reset).any()
+        count, index = S[:, lo.RESET_COUNT].view(np.uint32), S[:, lo.CMD_COUNT].view(np.uint32)
+        assert np.array_equal(index, np.where(reset, 0, before + fired)), k
+        time_outs += int(trunc.sum())
+        if fired.any():
+            want = LC.by_hand_command(cfg, gid[fired], count[fired], index[fired])       # 1 + k, k = the index before this firing
+            got = S[fired, lo.CMD:lo.CMD + 3]
+            assert (np.abs(got - want) <= np.spacing(np.abs(want))).all(), k
+            assert (S[fired, lo.CMD + 3:lo.CMD + 7] == np.array([1, 0, 0, 0], np.float32)).all()
+            assert len(np.unique(got, axis=0)) == int(fired.sum()), "two envs drew the same command"
+            for e in np.nonzero(fired)[0]:
+                episodes.setdefault((int(e), int(count[e])), []).append(tuple(got[e]))
+    assert time_outs == n
+    firings = [len(v) for v in episodes.values()]
+    # 0.3 s in steps of 0.02 s runs out after 15 or 16 steps (float32 rounding decides): 15 or 16 firings in 250 steps, 3 in the last 50
+    assert len(episodes) == 2 * n and max(firings) in (15, 16) and sum(firings) >= 18 * n
+    for cmds in episodes.values():
+        assert len(set(cmds)) == len(cmds), "a timer resample repeated a command of its episode"
+        c = np.array(cmds)
+        assert (c[:, :2] >= 0.3).all() and (c[:, :2] <= 0.7).all() and (c[:, 2] == 0).all()
+
+
+@pytest.mark.parametrize("n,seed", [(64, 0), (333, 5), (61, 2), (64, 3), (13, 6)])
+def test_default_configuration_never_draws_on_the_timer(lo, n, seed):
+    """The 300 steps of tests/test_gpu_lift.py's rollout: the time-out reset refills the timer before it runs out, so the
+    resample index stays 0 and the default configuration's bits are what they were."""
+    cfg = lo.default_config(seed_lo=seed)
+    S = lo.new_state(n)
+    lo.reset(cfg, S)
+    rng = np.random.RandomState(seed)
+    for k in range(300):
+        a = rng.uniform(-1, 1, (n, 8)).astype(np.float32)
+        if k % 50 < 25:
+            a[:, 7] = -1.0
+        lo.step(cfg, S, a)
+    assert (S[:, lo.CMD_COUNT].view(np.uint32) == 0).all() and (S[:, lo.RESET_COUNT].view(np.uint32) == 2).all()
+
+
+def test_lift_cases_reach_what_the_default_never_does(lo):
+    """Every case of tests/lift_cases.py on the oracle alone: finite throughout, every field of lift_config moved by some case,
+    and over all cases each of drop, time-out, timer resample, timer resample in the step of a reset, a wave of eight envs with
+    mixed reset lanes / mixed resample lanes, a step with both a drop and a time-out happens at least 5 times; the staggered
+    case alone has at least 5 wave-steps of each mixed kind."""
+    import lift_cases as LC
+    assert LC.moved_fields(lo) == set(LC.CONFIG_FIELDS) == {name for name, _ in lo.Config._fields_}
+    total = {}
+    for case in LC.CASES:
+        run = LC.case_run(lo, case)
+        assert 7 <= case.n <= 37 and 40 <= case.steps <= 120
+        for s in run.steps:
+            assert np.isfinite(s["S"][:, :lo.RESET_COUNT]).all() and np.isfinite(s["obs"]).all() and np.isfinite(s["rew"]).all(), case.name
+        counts = LC.reach_counts(run)
+        print(case.name, case.n, case.steps, counts)
+        for k, v in counts.items():
+            total[k] = total.get(k, 0) + v
+        if case.name == "stagger":
+            assert counts["mixed_reset_waves"] >= 5 and counts["mixed_resample_waves"] >= 5, counts
+            assert counts["drops"] >= 5 and counts["time_outs"] >= 5, counts
+    print("all cases", total)
+    assert all(v >= 5 for v in total.values()) and len(total) == 7, total
+    by_name = {c.name: LC.reach_counts(LC.case_run(lo, c)) for c in LC.NAMED}
+    assert by_name["no_sweeps"]["drops"] >= 50                                     # the cube sinks through the table
+    assert by_name["reset_every_step"]["resample_with_reset"] == 11 * 40           # every env, every step
+    # a resampling time of one step: once an env's staggered timer (at most 15 steps) has run out, it fires every step
+    assert all(s["resampled"].all() for s in LC.case_run(lo, LC.BY_NAME["commands"]).steps[15:])
+
+
+def test_lift_shards_equal_the_whole(lo):
+    """RNG keyed by the global env id: reset and 40 staggered steps of 17 envs at env_id_offset = 64 equal 8 envs at 64 next
+    to 9 at 72, bit for bit -- state, observations, rewards, flags."""
+    import lift_cases as LC
+    over = {"cmd_resample_time": 0.3, "seed_lo": 9, **LC.episode(30)}
+    whole = LC.oracle_run(lo, over, 17, 40, seed=4, env_id_offset=64)
+    assert LC.reach_counts(whole)["resamples"] >= 17 and LC.reach_counts(whole)["time_outs"] >= 17
+    cfg = LC.oracle_config(lo, over)
+    for lo_row, hi_row, offset in ((0, 8, 64), (8, 17, 72)):
+        m = hi_row - lo_row
+        S = lo.new_state(m)
+        obs = lo.reset(cfg, S, offset)
+        assert np.array_equal(obs.view(np.int32), whole.obs_reset[lo_row:hi_row].view(np.int32))
+        assert np.array_equal(S.view(np.int32), whole.S_reset[lo_row:hi_row].view(np.int32))
+        S[:] = whole.S0[lo_row:hi_row]
+        for k, s in enumerate(whole.steps):
+            obs, rew, term, trunc, _ = lo.step(cfg, S, s["a"][lo_row:hi_row], offset)
+            for got, want in ((obs, s["obs"]), (rew, s["rew"]), (S, s["S"])):
+                assert np.array_equal(got.view(np.int32), want[lo_row:hi_row].view(np.int32)), (offset, k)
+            assert np.array_equal(term.astype(bool), s["term"][lo_row:hi_row]) and np.array_equal(trunc.astype(bool), s["trunc"][lo_row:hi_row])

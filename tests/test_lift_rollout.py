@@ -96,7 +96,7 @@ def test_draws_come_from_a_stream_of_their_own(setup):
         assert (want != R.standard_normals((7 << 32) | 5, ids, k, LP.ACT_DIM)).all()      # the rover collector's tag
         assert np.array_equal(R.standard_normals((7 << 32) | 5, ids, k, LP.ACT_DIM), R.standard_normals((7 << 32) | 5, ids, k, LP.ACT_DIM, tag=R.ROLLOUT_TAG))
     assert LR.LIFT_ROLLOUT_TAG == TAG != R.ROLLOUT_TAG
-    # word 3 of the Philox input: the tag | pair, never 0 or 1 (the lift env's reset / command draws)
+    # word 3 of the Philox input: the tag | pair, never 0 or a small 1 + k (the lift env's reset / command draws)
     c3 = np.asarray(R.rollout_counter(ids.reshape(-1, 1), 5, np.arange(4).reshape(1, -1), TAG)[3])
     assert set(int(x) for x in c3.ravel()) == {TAG | p for p in range(4)}
     col.counter = 0
