@@ -1064,7 +1064,7 @@ int rover_policy_default_desc(rover_policy_desc *d, int32_t out_dim, int32_t fin
         d->layers[i].act = ROVER_ACT_LEAKY_RELU;
         d->layers[i].split_k = 0;
     }
-    d->layers[0].split_k = 1;   // 307 KB of weights: a quarter per wave
+    d->layers[0].split_k = 1;   // 307 KB of weights: an eighth per wave
     d->layers[5].split_k = 1;   // one column tile only
     d->layers[5].act = final_tanh ? ROVER_ACT_TANH : ROVER_ACT_NONE;
     return ROVER_OK;

@@ -99,10 +99,12 @@ class RoverNet:
             raise ValueError(f"obs must be a float32 cuda tensor of shape (n, {self.obs_dim})")
         obs = obs.contiguous()
         n = int(obs.shape[0])
+        if obs.device != self.packed.device:
+            raise ValueError(f"obs / out must live on the network's device {self.packed.device}")
         if out is None:
             out = torch.empty((n, self.out_dim), dtype=torch.float32, device=obs.device)
-        if obs.device != self.packed.device or out.device != obs.device:
-            raise ValueError(f"obs / out must live on the network's device {self.packed.device}")
+        else:
+            check_out(out, n, self.out_dim, obs.device, "out")
         stream = _fused.stream(obs.device)
         with torch.cuda.device(obs.device):     # the entry point launches on the thread's current device
             _lib.check(self._lib.rover_policy_forward(C.byref(self.desc), self.packed.data_ptr(), self.n_copies, obs.data_ptr(),
@@ -132,8 +134,12 @@ def forward_pair(net_a: RoverNet, net_b: RoverNet, obs: torch.Tensor, out_a: tor
     n = int(obs.shape[0])
     if out_a is None:
         out_a = torch.empty((n, net_a.out_dim), dtype=torch.float32, device=obs.device)
+    else:
+        check_out(out_a, n, net_a.out_dim, obs.device, "out_a")
     if out_b is None:
         out_b = torch.empty((n, net_b.out_dim), dtype=torch.float32, device=obs.device)
+    else:
+        check_out(out_b, n, net_b.out_dim, obs.device, "out_b")
     if net_a.n_copies != net_b.n_copies or obs.device != net_a.packed.device or obs.device != net_b.packed.device:
         return net_a(obs, out_a), net_b(obs, out_b)
     stream = _fused.stream(obs.device)
@@ -144,6 +150,21 @@ def forward_pair(net_a: RoverNet, net_b: RoverNet, obs: torch.Tensor, out_a: tor
         return net_a(obs, out_a), net_b(obs, out_b)
     _lib.check(rc, "rover_policy_forward_pair")
     return out_a, out_b
+
+
+def check_out(out, n: int, out_dim: int, device, name: str = "out") -> None:
+    """A caller's output buffer is handed to the kernel as a bare pointer to ``n * out_dim`` contiguous floats: anything else (another
+    shape or dtype, a strided view, another device) is refused here, before any launch."""
+    if not isinstance(out, torch.Tensor):
+        raise ValueError(f"{name} must be a torch tensor")
+    if tuple(out.shape) != (n, out_dim):
+        raise ValueError(f"{name} has shape {tuple(out.shape)}, expected ({n}, {out_dim})")
+    if out.dtype != torch.float32:
+        raise ValueError(f"{name} is {out.dtype}, expected torch.float32")
+    if not out.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (strides {tuple(out.stride())})")
+    if out.device != torch.device(device):
+        raise ValueError(f"{name} lives on {out.device}, the observations on {device}")
 
 
 HIDDEN_ACTS = {"leaky_relu": _lib.ACT_LEAKY_RELU, "elu": _lib.ACT_ELU, "tanh": _lib.ACT_TANH, "none": _lib.ACT_NONE}
@@ -166,7 +187,7 @@ def make_desc(shapes, n_enc: int, final_act: str, obs_dim: int, prop_dim: int, l
     for i, (n, k) in enumerate(shapes):
         lay = d.layers[i]
         lay.K, lay.N, lay.act = int(k), int(n), HIDDEN_ACTS[hidden_act]
-        # numerics contract (rover_policy.h): wide-K layers with few column tiles split K over the four waves
+        # numerics contract (rover_policy.h): wide-K layers with few column tiles split K over the eight waves
         tiles = (int(n) + 15) // 16
         lay.split_k = 1 if tiles <= 6 and (int(k) >= 512 or (tiles < 4 and int(k) >= 128)) else 0
     d.layers[nl - 1].act = {"tanh": _lib.ACT_TANH, "none": _lib.ACT_NONE}[final_act]

@@ -154,3 +154,84 @@ def test_pack_rejects_inconsistent_descriptors():
     assert lib.rover_policy_packed_floats(C.byref(d)) > 0
     assert lib.rover_policy_pack(C.byref(d), None, None, None) != 0
     assert b"chain" in lib.rover_last_error()
+
+
+# ------------------------------------------------------------------------------------------------ the contract in plain words
+# The same statements tests/test_gpu_policy_edges.py makes about the HIP kernels, made here about the oracle: against a numpy float64
+# restatement of models.py (policy_cases.reference64) on hard data, on subnormal data, and on rows that carry one bad value.
+def _t(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def test_oracle_within_the_rule_on_hard_data(po):
+    """td3_helpers.check with its defaults: the oracle's error norm against float64 within 4 x torch fp32's plus 1e-5 of the
+    reference's norm, on `synthetic`, `big`, `tiny` and `cancel` at n = 1, 17, 33 (policy_cases.hard_cases)."""
+    import policy_cases as pc
+    from td3_helpers import check, err
+    for name, ws, bs, final_tanh, obs in pc.hard_cases():
+        out_dim = ws[-1].shape[0]
+        got = po.forward(po.default_desc(out_dim, final_tanh), ws, bs, obs)
+        r64 = pc.reference64(ws, bs, obs, final_tanh)
+        t32 = torch_policy_reference(ws, bs, obs, final_tanh)
+        print(f"{name}: oracle err {err(_t(got), _t(r64)):.3e} torch fp32 err {err(_t(t32), _t(r64)):.3e} norm {np.linalg.norm(r64):.3e}")
+        if final_tanh:
+            assert np.mean(np.abs(r64) < 0.99) > 0.5, f"{name}: a saturated head compares nothing"
+        check(_t(got), _t(r64), _t(t32), what=name)
+
+
+@pytest.mark.parametrize("n", [1, 17, 33])
+def test_oracle_keeps_subnormal_values(po, n):
+    """Rows of 1e-38 through zero biases: every intermediate and every output is a subnormal, none is flushed to zero.  Relative 1e-2
+    against float64 is loose on purpose: one rounding of a subnormal is a large relative step."""
+    import policy_cases as pc
+    ws, bs, obs = pc.subnormal_case(n)
+    assert np.mean((np.abs(obs[:, 4:]) < pc.FLT_MIN) & (obs[:, 4:] != 0)) > 0.99
+    got = po.forward(po.default_desc(1, False), ws, bs, obs)
+    r64 = pc.reference64(ws, bs, obs, False)
+    assert (got != 0).all() and (np.abs(got) < pc.FLT_MIN).all()
+    assert (np.abs(got - r64) <= 1e-2 * np.abs(r64)).all(), np.abs(got / r64 - 1).max()
+
+
+@pytest.mark.parametrize("out_dim,final_tanh", [(2, True), (1, False)])
+def test_oracle_bad_rows_and_the_column_nothing_reads(po, out_dim, final_tanh):
+    """One NaN / inf / -inf / 3e38 in rows 5 and 32 of 33: the other rows keep their bits, the bad rows have a NaN wherever torch fp32
+    has one -- and a bad value in column 964 (models.py:95 drops the last ray) changes nothing at all."""
+    import policy_cases as pc
+    ws, bs = random_policy_weights(seed=20 + out_dim, out_dim=out_dim, scale=3.0)
+    desc = po.default_desc(out_dim, final_tanh)
+    obs = synthetic_obs(pc.BAD_N, seed=9)
+    clean = po.forward(desc, ws, bs, obs)
+    assert np.isfinite(clean).all()
+    others = [r for r in range(pc.BAD_N) if r not in pc.BAD_ROWS]
+    for col in pc.bad_columns(4, 965):
+        for value in pc.BAD_VALUES:
+            bad = pc.with_bad(obs, col, value)
+            got = po.forward(desc, ws, bs, bad)
+            what = f"column {col}, {value}"
+            assert pc.bits_equal(got[others], clean[others]), what
+            if col == 964:
+                assert pc.bits_equal(got, clean), what
+                continue
+            tor = torch_policy_reference(ws, bs, bad[list(pc.BAD_ROWS)], final_tanh)
+            assert np.isnan(got[list(pc.BAD_ROWS)])[np.isnan(tor)].all(), what
+            if value != value:
+                assert np.isnan(got[list(pc.BAD_ROWS)]).all(), what
+
+
+def test_check_out_refuses_what_the_kernel_cannot_write():
+    """policy.check_out (RoverNet.forward's `out`, forward_pair's `out_a` / `out_b`): shape (n, out_dim), float32, contiguous, on the
+    observations' device -- anything else is a ValueError, a correct view passes."""
+    import torch
+    from isaac_rover_orbit_amd.policy import check_out
+    n, w = 5, 2
+    wide = torch.zeros(n, w + 1)
+    assert check_out(torch.zeros(n, w), n, w, "cpu") is None
+    assert check_out(torch.zeros(n * w + 3)[1:1 + n * w].view(n, w), n, w, torch.device("cpu")) is None
+    for bad in (torch.zeros(n + 1, w), torch.zeros(n - 1, w), torch.zeros(n, w + 1), torch.zeros(n * w), torch.zeros(n, w, 1),
+                torch.zeros(n, w, dtype=torch.float64), torch.zeros(n, w, dtype=torch.float16), wide[:, :w], wide[:, 1:],
+                torch.zeros(w, n).t(), torch.zeros(2 * n, w)[::2], np.zeros((n, w), np.float32)):
+        with pytest.raises(ValueError):
+            check_out(bad, n, w, "cpu")
+    with pytest.raises(ValueError, match="lives on"):
+        check_out(torch.zeros(n, w), n, w, "cuda:0")
